@@ -6,13 +6,6 @@ the hand-written HIP kernels of ``libbehavenet_hip.so`` (see ``include/behavenet
 
 import os as _os
 
-# The step runs on up to six HIP streams (main, weight-gradient side stream, chunk stream, feed
-# prefetch, collective launch + RCCL's own).  The HIP runtime multiplexes streams onto
-# GPU_MAX_HW_QUEUES hardware queues (default 4); two streams that share a queue serialise, and a
-# stream waiting on an event then blocks its queue-mate (measured: +0.4 ms per step once the
-# collective streams exist).  Read by the runtime when it initialises, i.e. at the first HIP call.
-_os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
-
 __version__ = '0.1.0'
 
 

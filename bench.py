@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: conv-AE training frames/s, 128x128x1 frames, batch (= trial) 256.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--shard trial|frames]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--shard trial|frames] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Started plainly with --gpus N > 1 (no WORLD_SIZE in the environment) the script launches its own
@@ -617,6 +617,28 @@ def error_line(message, **extra):
     return json.dumps(out)
 
 
+DUMP_GRAD_SAMPLE = 1 << 20     # gradient elements --dump-outputs writes (4 MB; the 35 MB of parameters go out whole)
+
+
+def dump_outputs(out_dir, model, loss):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files in ``out_dir``: ``<key>.npy`` for
+    every value of its loss dict (float64 scalars); ``parameters.npy``, every trainable parameter after the optimizer
+    step, flattened and concatenated in ``model.parameters()`` order (float32); ``gradient_sample.npy``, the step's
+    gradient in the same order at DUMP_GRAD_SAMPLE positions drawn with a fixed seed, in ascending order (float32)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for key, value in loss.items():
+        if value is not None:
+            np.save(os.path.join(out_dir, '%s.npy' % key), np.asarray(float(value), dtype=np.float64))
+    params = [p for p in model.parameters() if p.requires_grad]
+    with torch.no_grad():
+        flat_p = torch.cat([p.reshape(-1) for p in params]).cpu().numpy()
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1)
+                            for p in params]).cpu().numpy()
+    np.save(os.path.join(out_dir, 'parameters.npy'), flat_p.astype(np.float32))
+    pick = np.sort(np.random.RandomState(0).choice(flat_g.size, min(DUMP_GRAD_SAMPLE, flat_g.size), replace=False))
+    np.save(os.path.join(out_dir, 'gradient_sample.npy'), flat_g[pick].astype(np.float32))
+
+
 def first_to_report():
     """Several ranks may notice a failure: the first one to claim the job's marker file prints the line."""
     path = os.path.join('/tmp', 'bn_bench_error_%s_%s' % (os.environ.get('MASTER_PORT', '0'),
@@ -768,7 +790,14 @@ def main():
                     help="N > 1: 'trial' = one 256-frame trial per rank per step (weak scaling), "
                          "'frames' = the ranks share ONE trial, each takes its slice of every "
                          "200-frame chunk (strong scaling, parity-exact)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0): its '
+                         'loss values, the updated parameters and a fixed sample of the gradient; the untimed '
+                         'priming then takes a fixed number of steps, so that runs with the same arguments get '
+                         'the same inputs')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         if not torch.cuda.is_available():
             raise SystemExit('bench.py needs an MI355X: torch.cuda.is_available() is False')
@@ -889,10 +918,11 @@ def run(args):
     # Single process: in blocks of 8 steps until two blocks in a row run within 3 % of the best block
     # seen (at least PRIME_STEPS, at most PRIME_MAX steps -- half a second); N > 1: a fixed count, the
     # ranks' steps are collective.
-    # BN_BENCH_PRIME=<count>: exactly that many (tests that compare the training trajectories of runs).
+    # BN_BENCH_PRIME=<count>: exactly that many (tests that compare the training trajectories of runs);
+    # --dump-outputs: the fixed count too, so that the dumped step sees the same model state and trial every run.
     fixed = os.environ.get('BN_BENCH_PRIME')
     primed = 0
-    if fixed is not None or bdist.is_active():
+    if fixed is not None or bdist.is_active() or args.dump_outputs:
         for _ in range(int(fixed) if fixed is not None else PRIME_STEPS + 16):
             one_step(model, opt, gen)
             primed += 1
@@ -1042,6 +1072,8 @@ def run(args):
             pet('timed steps')
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last)
     pet('report')
     if os.environ.get('BN_BENCH_TRACE') == '1' and rank == 0:
         print('host ms per step: ' + ' '.join(

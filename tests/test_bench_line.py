@@ -89,3 +89,46 @@ def test_write_detail_roundtrip(bench, full, tmp_path, monkeypatch):
     rel = bench.write_detail(full)
     with open(os.path.join(REPO, rel)) as f:
         assert json.load(f) == full
+
+
+def test_dump_outputs_writes_the_step_results_as_float_files(bench, tmp_path):
+    """--dump-outputs on the headline model (built on the host, a known gradient): the loss scalars as float64,
+    every parameter and a fixed, sorted sample of the gradient as float32, all of it well under 64 MB, and the same
+    sample on every call."""
+    import numpy as np
+    import torch
+    from behavenet_amd.models import AE
+    hp = bench.build_hparams()
+    hp['device'] = 'cpu'
+    torch.manual_seed(0)
+    model = AE(hp)
+    params = [p for p in model.parameters() if p.requires_grad]
+    n = sum(p.numel() for p in params)
+    position = torch.arange(n, dtype=torch.float32)            # gradient element i holds i (exact below 2**24)
+    off = 0
+    for p in params:
+        p.grad = position[off:off + p.numel()].view_as(p).clone()
+        off += p.numel()
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), model, {'loss': np.float32(0.125)})
+    files = sorted(os.listdir(str(tmp_path / 'a')))
+    assert files == ['gradient_sample.npy', 'loss.npy', 'parameters.npy']
+    assert sum(os.path.getsize(str(tmp_path / 'a' / f)) for f in files) < 64 * 2 ** 20
+    loss = np.load(str(tmp_path / 'a' / 'loss.npy'))
+    assert loss.dtype == np.float64 and loss.shape == () and float(loss) == 0.125
+    p = np.load(str(tmp_path / 'a' / 'parameters.npy'))
+    assert p.dtype == np.float32
+    np.testing.assert_array_equal(p, torch.cat([q.detach().reshape(-1) for q in params]).numpy())
+    g = np.load(str(tmp_path / 'a' / 'gradient_sample.npy'))
+    assert g.dtype == np.float32 and g.shape == (bench.DUMP_GRAD_SAMPLE,)
+    assert np.all(np.diff(g) > 0) and g[0] >= 0 and g[-1] < n
+    for f in files:
+        np.testing.assert_array_equal(np.load(str(tmp_path / 'a' / f)), np.load(str(tmp_path / 'b' / f)))
+
+
+@pytest.mark.parametrize('argv', [['--steps', '0'], ['--warmup', '-1']])
+def test_bad_step_counts_are_refused(bench, argv, monkeypatch):
+    monkeypatch.setattr(sys, 'argv', ['bench.py'] + argv)
+    with pytest.raises(SystemExit) as exc:
+        bench.main()
+    assert exc.value.code == 2

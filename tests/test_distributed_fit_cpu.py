@@ -7,6 +7,7 @@ oracle model stands in for the HIP model, a torch Adam over a flat arena for the
   averages the same groups itself.
 * ``export_latents``: trials are owned by identity, gathered on rank 0, none missing."""
 
+import contextlib
 import copy
 import os
 import pickle
@@ -87,6 +88,18 @@ class _Exp(object):
         pass
 
 
+@contextlib.contextmanager
+def _rank_threads(n=2):
+    """The single-process reference runs with the ranks' intra-op thread count: the CPU kernels split their sums
+    by thread, and Adam turns a last-bit difference of a near-zero gradient into a step of up to lr."""
+    prev = torch.get_num_threads()
+    torch.set_num_threads(n)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(prev)
+
+
 def _setup(tmp, l2=1e-3):
     arch = load_handcrafted_arch(list(DIM), 4, None, check_memory=False)
     hp = base_hparams(arch, 'ae', None)
@@ -146,23 +159,24 @@ def test_fit_trial_mode_two_ranks(tmp_path):
     assert rows0 == rows1 and len(rows0) == 3
 
     # single process doing the same by hand: groups of W trials, averaged gradient, one step
-    hp, gen, model = _setup(os.path.join(str(tmp_path), 'ref'))
-    opt = _CpuFlatAdam(model.get_parameters(), hp['learning_rate'], hp['l2_reg'])
-    tr_rows = []
-    for epoch in range(3):
-        torch.manual_seed(3 + epoch)
-        np.random.seed(3 + epoch)
-        gen.reset_iterators('train')
-        tot = 0.0
-        for _ in range(4):
-            opt.zero_grad()
-            for _ in range(world):
-                data, ds = gen.next_batch('train')
-                tot += model.loss(data, dataset=ds, accumulate_grad=True)['loss']
-            if epoch > 0:
-                opt.flat_g.div_(world)
-                opt.step()
-        tr_rows.append(tot / 8)
+    with _rank_threads():
+        hp, gen, model = _setup(os.path.join(str(tmp_path), 'ref'))
+        opt = _CpuFlatAdam(model.get_parameters(), hp['learning_rate'], hp['l2_reg'])
+        tr_rows = []
+        for epoch in range(3):
+            torch.manual_seed(3 + epoch)
+            np.random.seed(3 + epoch)
+            gen.reset_iterators('train')
+            tot = 0.0
+            for _ in range(4):
+                opt.zero_grad()
+                for _ in range(world):
+                    data, ds = gen.next_batch('train')
+                    tot += model.loss(data, dataset=ds, accumulate_grad=True)['loss']
+                if epoch > 0:
+                    opt.flat_g.div_(world)
+                    opt.step()
+            tr_rows.append(tot / 8)
     np.testing.assert_allclose(p0, opt.flat_p.numpy(), rtol=1e-5, atol=1e-7)
     np.testing.assert_allclose([r['tr_loss'] for r in rows0], tr_rows, rtol=1e-6)
 
@@ -311,23 +325,24 @@ def test_fit_trial_mode_short_last_group_with_overlapped_reducer(tmp_path):
     assert rows0 == rows1 == rows2 and len(rows0) == 3
 
     # single process doing the same by hand: groups of 3, 3, 2 trials, mean gradient, one step
-    hp, gen, model = _setup(os.path.join(str(tmp_path), 'ref'))
-    opt = _CpuFlatAdam(model.get_parameters(), hp['learning_rate'], hp['l2_reg'])
-    tr_rows = []
-    for epoch in range(3):
-        torch.manual_seed(3 + epoch)
-        np.random.seed(3 + epoch)
-        gen.reset_iterators('train')
-        tot = 0.0
-        for n_group in (3, 3, 2):
-            opt.zero_grad()
-            for _ in range(n_group):
-                data, ds = gen.next_batch('train')
-                tot += model.loss(data, dataset=ds, accumulate_grad=True)['loss']
-            if epoch > 0:
-                opt.flat_g.div_(n_group)
-                opt.step()
-        tr_rows.append(tot / 8)
+    with _rank_threads():
+        hp, gen, model = _setup(os.path.join(str(tmp_path), 'ref'))
+        opt = _CpuFlatAdam(model.get_parameters(), hp['learning_rate'], hp['l2_reg'])
+        tr_rows = []
+        for epoch in range(3):
+            torch.manual_seed(3 + epoch)
+            np.random.seed(3 + epoch)
+            gen.reset_iterators('train')
+            tot = 0.0
+            for n_group in (3, 3, 2):
+                opt.zero_grad()
+                for _ in range(n_group):
+                    data, ds = gen.next_batch('train')
+                    tot += model.loss(data, dataset=ds, accumulate_grad=True)['loss']
+                if epoch > 0:
+                    opt.flat_g.div_(n_group)
+                    opt.step()
+            tr_rows.append(tot / 8)
     np.testing.assert_allclose(p0, opt.flat_p.numpy(), rtol=1e-5, atol=1e-7)
     np.testing.assert_allclose([r['tr_loss'] for r in rows0], tr_rows, rtol=1e-6)
 

@@ -252,15 +252,31 @@ def _claim_version(args):
     return Experiment(name='e', save_dir=save_dir).version
 
 
+def _claim_versions(save_dir, n, out):
+    import multiprocessing as mp
+    flag = os.path.join(save_dir, 'go')
+    with mp.get_context('fork').Pool(n) as pool:
+        res = pool.map_async(_claim_version, [(save_dir, flag)] * n, chunksize=1)
+        open(flag, 'w').close()
+        out.put(res.get(timeout=60))
+
+
 def test_experiment_versions_are_claimed_atomically(tmp_path):
     """The ranks of a grid search create their experiments at the same moment under one name
     (one grid point per rank): every process must get its own version_K."""
     import multiprocessing as mp
-    flag = os.path.join(str(tmp_path), 'go')
-    with mp.get_context('fork').Pool(8) as pool:
-        res = pool.map_async(_claim_version, [(str(tmp_path), flag)] * 8, chunksize=1)
-        open(flag, 'w').close()
-        versions = res.get(timeout=60)
+    # (the claimants are forked from a fresh process: this one may hold the GPU open -- conftest's
+    # GPU probe -- and forks of it would hold it too)
+    ctx = mp.get_context('spawn')
+    out = ctx.Queue()
+    proc = ctx.Process(target=_claim_versions, args=(str(tmp_path), 8, out))
+    proc.start()
+    try:
+        versions = out.get(timeout=120)
+    finally:
+        proc.join(timeout=30)
+        if proc.is_alive():
+            proc.kill()
     assert sorted(versions) == list(range(8))
 
 
