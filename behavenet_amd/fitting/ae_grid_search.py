@@ -125,10 +125,14 @@ def main(hparams, *args):
     print('done')
     print(model)
 
-    fit(hparams, model, data_generator, exp, method='ae')
+    try:
+        fit(hparams, model, data_generator, exp, method='ae')
 
-    hparams['training_completed'] = True
-    export_hparams(hparams, exp)
+        hparams['training_completed'] = True
+        export_hparams(hparams, exp)
+    finally:
+        if hasattr(exp, 'release'):
+            exp.release()           # (resume_training: the version's claim)
     _clean_tt_dir(hparams)
     if hparams.get('export_train_plots', False):
         # plotting is outside the hot path; metrics.csv holds the curves

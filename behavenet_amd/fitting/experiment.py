@@ -8,12 +8,15 @@ without that dependency:
     <save_dir>/<name>/version_<K>/metrics.csv      one row per logged dict, union of all keys
     <save_dir>/<name>/version_<K>/meta_tags.csv    key,value rows of the tagged hparams
 
-``version`` is the smallest unused K unless given.  ``get_best_model_version`` and the
+``version`` is the smallest unused K unless given.  ``claim()`` takes a version for the lifetime of
+the process (an advisory lock): the grid search reopens an unfinished version to resume it only if
+nobody else holds it.  ``get_best_model_version`` and the
 reference's plotting read ``metrics.csv`` by column name (``val_loss``, ``tr_loss``, ``epoch``,
 ``dataset`` ...), which is all that is relied on here.
 """
 
 import csv
+import fcntl
 import os
 import time
 
@@ -48,8 +51,32 @@ class Experiment(object):
         elif version is None:
             version = self._next_version(root)
         self.version = int(version)
+        self._claim = None
         if not self.debug:
             os.makedirs(self.get_data_path(self.name, self.version), exist_ok=True)
+
+    _CLAIM_FILE = '.claim'
+
+    def claim(self):
+        """Take this version for as long as this process runs (or until ``release()``): an exclusive
+        ``flock`` on a file in the version directory -- atomic, and dropped by the kernel when the
+        process dies, so a version whose run was killed can be claimed again.  -> True if taken
+        (or held already), False if another process holds it."""
+        if self._claim is not None:
+            return True
+        f = open(os.path.join(self.get_data_path(self.name, self.version), self._CLAIM_FILE), 'a')
+        try:
+            fcntl.flock(f.fileno(), fcntl.LOCK_EX | fcntl.LOCK_NB)
+        except OSError:
+            f.close()
+            return False
+        self._claim = f
+        return True
+
+    def release(self):
+        if self._claim is not None:
+            self._claim.close()
+            self._claim = None
 
     @staticmethod
     def _next_version(root):

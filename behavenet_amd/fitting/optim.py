@@ -106,6 +106,73 @@ class FlatAdamAMSGrad(object):
                 'FlatAdamAMSGrad.step: parameters are on %s; the optimizer kernel only runs on '
                 'the GPU (no CPU fallback)' % self.flat_p.device)
 
+    def param_group(self):
+        """The hyperparameters in ``torch.optim.Adam``'s param-group layout (every key the installed
+        torch writes, so that ``torch.optim.Adam.load_state_dict`` finds none missing)."""
+        probe = torch.optim.Adam([torch.zeros(1, requires_grad=True)], lr=self.lr, betas=self.betas,
+                                 eps=self.eps, weight_decay=self.weight_decay, amsgrad=True)
+        group = dict(probe.state_dict()['param_groups'][0])
+        group['params'] = list(range(len(self.params)))
+        return group
+
+    def state_dict(self):
+        """The state in ``torch.optim.Adam(amsgrad=True)``'s layout: ``{'state': {i: {'step',
+        'exp_avg', 'exp_avg_sq', 'max_exp_avg_sq'}}, 'param_groups': [...]}``, one entry per
+        parameter in ``params`` order, each moment shaped like its parameter (no arena padding, no
+        shard layout).  Like torch's, the moments are REFERENCES (views into the arenas), not copies.
+
+        Sharded (``shard_over`` > 1 under a process group): this rank's arenas hold current moments
+        in its own shard only -- ``fitting.distributed.gather_optimizer_state_`` (a collective, on
+        every rank) first."""
+        step = torch.tensor(float(self.step_count), dtype=torch.float32)
+        state = {}
+        for i in range(len(self.params)):
+            m, v, vmax = self.state_tensors(i)
+            state[i] = {'step': step.clone(), 'exp_avg': m, 'exp_avg_sq': v, 'max_exp_avg_sq': vmax}
+        return {'state': state, 'param_groups': [self.param_group()]}
+
+    def load_state_dict(self, state_dict):
+        """Load a state written by :meth:`state_dict` or by ``torch.optim.Adam(amsgrad=True)`` over the
+        same parameter list.  Every rank of a sharded optimizer loads the whole state (its own shard
+        is what it steps)."""
+        groups = state_dict['param_groups']
+        if len(groups) != 1:
+            raise ValueError('FlatAdamAMSGrad.load_state_dict: %d param groups (one expected)'
+                             % len(groups))
+        group = groups[0]
+        if not group.get('amsgrad', False) or group.get('maximize', False):
+            raise ValueError('FlatAdamAMSGrad.load_state_dict: the state is not of Adam(amsgrad=True)')
+        if len(group['params']) != len(self.params):
+            raise ValueError('FlatAdamAMSGrad.load_state_dict: %d parameters in the state, %d here'
+                             % (len(group['params']), len(self.params)))
+        state = state_dict['state']
+        steps, dst, src = set(), [], []
+        for i, pid in enumerate(group['params']):
+            p = self.params[i]
+            entry = state.get(pid)
+            if entry is None:           # torch.optim.Adam before its first step
+                steps.add(0)
+                continue
+            steps.add(int(float(entry['step'])))
+            for name, view in zip(('exp_avg', 'exp_avg_sq', 'max_exp_avg_sq'), self.state_tensors(i)):
+                t = entry[name]
+                if tuple(t.shape) != tuple(p.shape):
+                    raise ValueError('FlatAdamAMSGrad.load_state_dict: %s of parameter %d has shape '
+                                     '%s, the parameter %s' % (name, i, tuple(t.shape), tuple(p.shape)))
+                dst.append(view)
+                src.append(t.detach().to(device=view.device, dtype=view.dtype))
+        if len(steps) != 1:
+            raise ValueError('FlatAdamAMSGrad.load_state_dict: the parameters have different step '
+                             'counts %s (one step count for the arena)' % sorted(steps))
+        with torch.no_grad():
+            for arena in (self.exp_avg, self.exp_avg_sq, self.max_exp_avg_sq):
+                arena.zero_()
+            if dst:
+                torch._foreach_copy_(dst, src)
+        self.step_count = steps.pop()
+        self.lr, self.betas = group['lr'], tuple(group['betas'])
+        self.eps, self.weight_decay = group['eps'], group['weight_decay']
+
     def state_tensors(self, index):
         """(exp_avg, exp_avg_sq, max_exp_avg_sq) views for parameter ``index`` (for tests)."""
         p, off = self.params[index], self.offsets[index]

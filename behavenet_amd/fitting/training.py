@@ -163,19 +163,63 @@ def _snapshot(model, hparams, into=None):
     return snap
 
 
+class _Leaf(object):
+    """Placeholder for the i-th device tensor of an object on its way to the disk."""
+    __slots__ = ('i',)
+
+    def __init__(self, i):
+        self.i = i
+
+
+def _map_tensors(obj, fn):
+    """``obj`` with every tensor (or _Leaf) ``t`` in its dicts / lists / tuples replaced by ``fn(t)``
+    (dict classes kept, and an OrderedDict's ``_metadata``: a state dict's module versions)."""
+    if torch.is_tensor(obj) or isinstance(obj, _Leaf):
+        return fn(obj)
+    if isinstance(obj, dict):
+        out = obj.__class__()
+        for k, v in obj.items():
+            out[k] = _map_tensors(v, fn)
+        if getattr(obj, '_metadata', None) is not None:
+            out._metadata = obj._metadata
+        return out
+    if isinstance(obj, (list, tuple)):
+        return obj.__class__(_map_tensors(v, fn) for v in obj)
+    return obj
+
+
+def _atomic_save(obj, path, durable=False):
+    """``torch.save`` next to ``path``, then renamed over it: a reader -- or a run killed mid-write --
+    finds the previous file or the new one, never half of one.  ``durable``: on the disk before the
+    rename (the file has to outlive a reset of the machine, not only of the process)."""
+    tmp = '%s.tmp.%d' % (path, os.getpid())
+    try:
+        with open(tmp, 'wb') as f:
+            torch.save(obj, f)
+            if durable:
+                f.flush()
+                os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+
+
 class _CheckpointWriter(object):
     """``model.save(path)`` without stalling the device: the state dict is copied device-side on
     the compute stream (microseconds), brought to pinned host memory on a side stream, and pickled
     to ``path`` by a background thread (written next to it, then renamed: a reader never sees a
     half-written file).  The reference writes the same file synchronously
     (training.py:388-397); nothing says the device has to wait for the disk.  ``wait()`` before
-    anybody reads the file; one write at a time per writer."""
+    anybody reads the file; one write at a time per writer.  ``save_state`` does the same for any
+    nested dict / list of tensors (the training state of a resumable fit)."""
 
     def __init__(self):
         self._thread = None
         self._error = None
         self._stream = None
-        self._plan = None           # (dtype, ((key, shape), ...)) groups the flat buffers were laid out for
+        self._plan = None           # (dtype, (shape, ...)) groups the flat buffers were laid out for
         self._flat = {}             # dtype -> (flat device buffer, flat pinned host buffer)
 
     def wait(self, reraise=True):
@@ -190,50 +234,39 @@ class _CheckpointWriter(object):
             if reraise:
                 raise err
 
-    def save(self, model, path):
-        from behavenet_amd.models.base import BaseModel
-        state = model.state_dict()
-        plain = getattr(type(model), 'save', None) is BaseModel.save
-        if not plain or not any(t.is_cuda for t in state.values()):
-            # classes whose ``save`` does more than write the state dict (AEMSP), host models
-            self.wait()
-            model.save(path)
-            return
-        self.wait()
-        import threading
-        dev = next(t.device for t in state.values() if t.is_cuda)
+    def _stage(self, tensors):
+        """Bring the device tensors ``tensors`` to pinned host memory behind the work queued so far.
+        -> (event the host copies are complete at, fetch(i) -> plain host clone of tensor i)."""
+        dev = tensors[0].device
         main = torch.cuda.current_stream(dev)
-        # ONE flat device buffer and ONE flat pinned host buffer per dtype, kept across saves: the state
-        # dict is packed device-side by a multi-tensor copy in stream order (the snapshot), crosses
-        # PCIe as one transfer per dtype on the side stream, and is cut back into tensors by the
+        # ONE flat device buffer and ONE flat pinned host buffer per dtype, kept across saves: the
+        # tensors are packed device-side by a multi-tensor copy in stream order (the snapshot), cross
+        # PCIe as one transfer per dtype on the side stream, and are cut back into tensors by the
         # writer thread.  (Round 5, first form: a clone and a pinned allocation PER TENSOR -- 7 ms of
         # host time per checkpoint with the device idle, tools/gaps.py on the rocprofv3 trace of fit().)
-        names = list(state.keys())
         groups = {}
-        for k in names:
-            v = state[k]
-            if v.is_cuda:
-                groups.setdefault(v.dtype, []).append(k)
-        plan = tuple((dt, tuple((k, tuple(state[k].shape)) for k in ks)) for dt, ks in groups.items())
+        for i, v in enumerate(tensors):
+            groups.setdefault(v.dtype, []).append(i)
+        plan = tuple((dt, tuple(tuple(tensors[i].shape) for i in ix)) for dt, ix in groups.items())
         if self._plan != plan:
             self._plan = plan
             self._flat = {}
-            for dt, ks in groups.items():
-                n = sum(state[k].numel() for k in ks)
+            for dt, ix in groups.items():
+                n = sum(tensors[i].numel() for i in ix)
                 self._flat[dt] = (torch.empty(n, dtype=dt, device=dev),
                                   torch.empty(n, dtype=dt, pin_memory=True))
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=dev)
         layout = {}
         with torch.no_grad():
-            for dt, ks in groups.items():
+            for dt, ix in groups.items():
                 flat_d, _ = self._flat[dt]
                 views, srcs, pos = [], [], 0
-                for k in ks:
-                    v = state[k].detach()
+                for i in ix:
+                    v = tensors[i]
                     views.append(flat_d[pos:pos + v.numel()].view(v.shape))
                     srcs.append(v)
-                    layout[k] = (dt, pos, v.numel(), tuple(v.shape))
+                    layout[i] = (dt, pos, v.numel(), tuple(v.shape))
                     pos += v.numel()
                 torch._foreach_copy_(views, srcs)
         ev = torch.cuda.Event()
@@ -247,27 +280,29 @@ class _CheckpointWriter(object):
             done.record(self._stream)
         # (the next save's packing copy cannot overtake this transfer: save() starts with wait(), and the
         # writer thread has waited for `done` by then)
-        on_host = {k: state[k].detach().clone() for k in names if not state[k].is_cuda}
-        metadata = getattr(state, '_metadata', None)
         flats = {dt: pair[1] for dt, pair in self._flat.items()}
+
+        def fetch(i):
+            dt, pos, n, shape = layout[i]
+            return flats[dt][pos:pos + n].view(shape).clone()         # plain, unpinned
+        return done, fetch
+
+    def _start(self, path, done, build, durable=False, after=None):
+        """Write ``build()`` to ``path`` on a background thread once ``done`` has completed (and the
+        write in flight on the writer ``after``, if any: a file that must not be newer than another
+        one).  Failures go to ``wait()``."""
+        import threading
+        prior = after._thread if after is not None else None
 
         def write():
             try:
                 done.synchronize()
-                # the structure BaseModel.save writes: an OrderedDict that carries the modules' version
-                # metadata (the file must not depend on which of the two paths wrote it)
-                out = OrderedDict()
-                if metadata is not None:
-                    out._metadata = metadata
-                for k in names:
-                    if k in layout:
-                        dt, pos, n, shape = layout[k]
-                        out[k] = flats[dt][pos:pos + n].view(shape).clone()     # plain, unpinned
-                    else:
-                        out[k] = on_host[k]
-                tmp = '%s.tmp.%d' % (path, os.getpid())
-                torch.save(out, tmp)
-                os.replace(tmp, path)
+                if prior is not None:
+                    prior.join()
+                    if after._error is not None:
+                        raise RuntimeError('not written: the checkpoint write before it failed (%s)'
+                                           % after._error)
+                _atomic_save(build(), path, durable=durable)
             except BaseException as err:            # noqa: BLE001 (re-raised by wait())
                 self._error = err
                 # said at once: if fit() fails before its next save() / wait(), nobody would hear of it
@@ -275,6 +310,58 @@ class _CheckpointWriter(object):
                       file=sys.stderr, flush=True)
         self._thread = threading.Thread(target=write, name='bn-checkpoint', daemon=False)
         self._thread.start()
+
+    def save(self, model, path):
+        from behavenet_amd.models.base import BaseModel
+        state = model.state_dict()
+        plain = getattr(type(model), 'save', None) is BaseModel.save
+        if not plain or not any(t.is_cuda for t in state.values()):
+            # classes whose ``save`` does more than write the state dict (AEMSP), host models
+            self.wait()
+            model.save(path)
+            return
+        self.wait()
+        names = list(state.keys())
+        on_device = [k for k in names if state[k].is_cuda]
+        done, fetch = self._stage([state[k].detach() for k in on_device])
+        index = {k: i for i, k in enumerate(on_device)}
+        on_host = {k: state[k].detach().clone() for k in names if not state[k].is_cuda}
+        metadata = getattr(state, '_metadata', None)
+
+        def build():
+            # the structure BaseModel.save writes: an OrderedDict that carries the modules' version
+            # metadata (the file must not depend on which of the two paths wrote it)
+            out = OrderedDict()
+            if metadata is not None:
+                out._metadata = metadata
+            for k in names:
+                out[k] = fetch(index[k]) if k in index else on_host[k]
+            return out
+        self._start(path, done, build)
+
+    def save_state(self, obj, path, after=None):
+        """Write ``obj`` (dicts / lists / tuples of tensors and plain values) to ``path`` as
+        ``torch.save`` would, durably, after the write in flight on the writer ``after``.  Device
+        tensors are copied in stream order at the call: the caller may go on changing them."""
+        self.wait()
+        leaves = []
+
+        def strip(t):
+            t = t.detach()
+            if t.is_cuda:
+                leaves.append(t)
+                return _Leaf(len(leaves) - 1)
+            return t.clone()
+        skeleton = _map_tensors(obj, strip)
+        if not leaves:                              # host run: nothing to overlap
+            if after is not None:
+                after.wait()
+            _atomic_save(skeleton, path, durable=True)
+            return
+        done, fetch = self._stage(leaves)
+        self._start(path, done,
+                    lambda: _map_tensors(skeleton, lambda t: fetch(t.i) if isinstance(t, _Leaf) else t),
+                    durable=True, after=after)
 
 
 def _save_checkpoint(model, path, is_main, writer=None):
@@ -288,6 +375,129 @@ def _save_checkpoint(model, path, is_main, writer=None):
             model.save(path)
     elif hasattr(model, 'create_orthogonal_matrix'):
         model.create_orthogonal_matrix()
+
+
+# ------------------------------------------------------------------------------------------
+# resumable fits (hparams['resume_training'])
+# ------------------------------------------------------------------------------------------
+TRAINING_STATE_FILE = 'training_state.pt'
+_STATE_FORMAT = 1
+
+# The hparams that steer the trajectory of a fit: a run resumes from a training state only when
+# every one of them equals the value the state was written under (missing keys count as None).
+# `_fit_signature` adds the data-parallel layout the fit actually runs with (world size, shard mode,
+# sharded optimizer).
+RESUME_KEYS = (
+    'model_class', 'model_type', 'n_ae_latents', 'n_input_channels', 'y_pixels', 'x_pixels',
+    'learning_rate', 'l2_reg', 'rng_seed_data', 'rng_seed_model', 'rng_seed_train', 'trial_splits',
+    'train_frac', 'max_n_epochs', 'min_n_epochs', 'val_check_interval', 'enable_early_stop',
+    'early_stop_history', 'ae_batch_norm', 'ae_batch_norm_momentum', 'fit_sess_io_layers',
+    'conditional_encoder', 'n_sessions_per_batch', 'vae.beta', 'vae.beta_anneal_epochs',
+    'beta_tcvae.beta', 'beta_tcvae.beta_anneal_epochs', 'ps_vae.alpha', 'ps_vae.beta',
+    'ps_vae.delta', 'ps_vae.anneal_epochs', 'msp.alpha', 'n_background')
+
+
+def _fit_signature(hparams, world, shard_opt):
+    sig = {k: hparams.get(k) for k in RESUME_KEYS}
+    sig['world_size'] = world
+    sig['dp_shard'] = bdist.shard_mode() if world > 1 else None
+    sig['shard_optimizer'] = bool(shard_opt)
+    return sig
+
+
+def _same(a, b):
+    try:
+        return bool(a == b)
+    except (TypeError, ValueError):
+        return repr(a) == repr(b)
+
+
+def read_training_state(path, mmap=False):
+    """The training state a resumable fit wrote to ``path`` (host tensors), or None if there is none.
+    ``mmap``: tensors are mapped, not read (for a look at the epoch or the metric rows only)."""
+    if not os.path.exists(path):
+        return None
+    return torch.load(path, map_location='cpu', weights_only=False, mmap=mmap)
+
+
+def _agree_on_state(path, signature, world):
+    """Read the training state at ``path`` and check it against ``signature`` -- with every rank's view
+    of it compared before anything else is communicated, so that all ranks load, all start fresh or
+    all raise.  -> the state or None."""
+    state, verdict = None, ('fresh',)
+    try:
+        state = read_training_state(path)
+    except Exception as err:                     # noqa: BLE001 (raised below, on every rank)
+        verdict = ('error', '%s cannot be read (%s: %s)' % (path, type(err).__name__, err))
+    if state is not None:
+        if state.get('format') != _STATE_FORMAT:
+            verdict = ('error', '%s has format %r, this version reads %d'
+                       % (path, state.get('format'), _STATE_FORMAT))
+        else:
+            stored = state['fit_hparams']
+            diff = sorted(k for k in set(stored) | set(signature)
+                          if not _same(stored.get(k), signature.get(k)))
+            if diff:
+                verdict = ('error', 'resume_training: %s was written by a fit with different '
+                           'settings; refusing to resume (%s). Remove the file to start over.'
+                           % (path, ', '.join('%s: stored %r, now %r'
+                                              % (k, stored.get(k), signature.get(k)) for k in diff)))
+            else:
+                verdict = ('resume', int(state['epoch']))
+    if world > 1:
+        import torch.distributed as dist
+        everyone = [None] * world
+        dist.all_gather_object(everyone, verdict)
+        if any(v != everyone[0] for v in everyone):
+            raise RuntimeError('resume_training: the ranks see different training states at %s: %s'
+                               % (path, everyone))
+    if verdict[0] == 'error':
+        raise ValueError(verdict[1])
+    return state if verdict[0] == 'resume' else None
+
+
+def _rng_states():
+    cuda = None
+    if torch.cuda.is_available() and torch.cuda.is_initialized():
+        cuda = torch.cuda.get_rng_state_all()
+    return {'torch': torch.get_rng_state(), 'cuda': cuda, 'numpy': np.random.get_state()}
+
+
+def _set_rng_states(rng):
+    torch.set_rng_state(rng['torch'])
+    if rng['cuda'] is not None and torch.cuda.is_available():
+        torch.cuda.set_rng_state_all(rng['cuda'])
+    np.random.set_state(rng['numpy'])
+
+
+def _save_training_state(path, is_main, state_writer, writer, optimizer, shard_opt, model, exp, logger,
+                         early_stop, signature, loop):
+    """The state of a fit at the end of epoch ``loop['epoch']`` -> ``path`` (main rank; every rank
+    takes part in gathering a sharded optimizer's moments).  ``loop``: the loop's own variables.
+    Written after the checkpoint files queued before it on ``writer`` (the state never points at a
+    best model the disk does not have yet)."""
+    if shard_opt:
+        bdist.gather_optimizer_state_(optimizer)
+    if not is_main:
+        return
+    logger.flush()
+    state = dict(loop)
+    state.update({
+        'format': _STATE_FORMAT,
+        'fit_hparams': signature,
+        'model': model.state_dict(),
+        'optimizer': optimizer.state_dict(),
+        'early_stop': dict(vars(early_stop)) if early_stop is not None else None,
+        'logger': copy.deepcopy((logger.metrics, logger.metrics_by_dataset)),
+        'rows': [dict(row) for row in exp.metrics],
+        'rng': _rng_states(),
+    })
+    if state_writer is not None:
+        state_writer.save_state(state, path, after=writer)
+    else:
+        if writer is not None:
+            writer.wait()
+        _atomic_save(state, path, durable=True)
 
 
 def _merge_rank_metrics(logger, dtype):
@@ -340,26 +550,37 @@ def fit(hparams, model, data_generator, exp, method='ae', optimizer=None):
     The loss dicts of the eager steps are handed to the logger unresolved (hip_functions.set_lazy_losses;
     ``hparams['lazy_losses'] = False`` turns that off): same values in the same order in the metric rows,
     but the host does not wait for the forward pass of a step before it queues the next one.
+
+    ``hparams['resume_training']``: every ``hparams['training_state_interval']``-th epoch (default 1)
+    the whole training state goes to ``training_state.pt`` in the version directory; a fit that finds
+    one continues after its epoch, bit for bit as the unbroken run would have (``optimizer`` then needs
+    ``state_dict`` / ``load_state_dict``, ``exp`` its rows in ``exp.metrics``).  The file is removed
+    when the fit completes.
     """
     from behavenet_amd import hip_functions as hf
     prev = hf.set_lazy_losses(bool(hparams.get('lazy_losses', True)))
     # checkpoints leave through a background writer unless hparams['async_checkpoint'] is False
     writer = _CheckpointWriter() if hparams.get('async_checkpoint', True) else None
+    # the training state has a writer of its own (its buffers, and no wait behind a model checkpoint)
+    state_writer = _CheckpointWriter() if writer is not None and hparams.get('resume_training') else None
+    writers = [w for w in (writer, state_writer) if w is not None]
     try:
-        out = _fit(hparams, model, data_generator, exp, method=method, optimizer=optimizer, writer=writer)
+        out = _fit(hparams, model, data_generator, exp, method=method, optimizer=optimizer, writer=writer,
+                   state_writer=state_writer)
     except BaseException:
-        if writer is not None:
-            writer.wait(reraise=False)          # a write in flight still finishes: the best model so far stays valid
+        for w in writers:
+            w.wait(reraise=False)               # a write in flight still finishes: the best model so far stays valid
         raise
     else:
-        if writer is not None:
-            writer.wait()                       # the checkpoint files are complete before fit() returns
+        for w in writers:
+            w.wait()                            # the checkpoint files are complete before fit() returns
         return out
     finally:
         hf.set_lazy_losses(prev)
 
 
-def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, writer=None):
+def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, writer=None,
+         state_writer=None):
     if hparams.get('dp_shard') is not None:
         bdist.set_shard_mode(hparams['dp_shard'])
     # hparams['shard_optimizer'] (BN_SHARD_OPTIMIZER=0/1): reduce-scatter -> Adam on this rank's 1/R
@@ -426,7 +647,30 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
     best_val_model = None
     best_model_saved = False
 
-    if hparams.get('rng_seed_train', None) is None:
+    expt_dir = os.path.join(hparams['expt_dir'], 'version_%i' % exp.version)
+    is_main = bdist.rank() == 0
+    show_bar = hparams.get('progress_bar', True) and is_main
+
+    resume = bool(hparams.get('resume_training', False))
+    state_path = os.path.join(expt_dir, TRAINING_STATE_FILE)
+    state_every = max(1, int(hparams.get('training_state_interval', 1)))
+    restored = signature = None
+    if resume:
+        for what, obj, attrs in (('optimizer', optimizer, ('state_dict', 'load_state_dict')),
+                                 ('experiment', exp, ('metrics',))):
+            if not all(hasattr(obj, a) for a in attrs):
+                raise ValueError('resume_training: the %s (%s) has no %s' % (
+                    what, type(obj).__name__, ' / '.join(attrs)))
+        signature = _fit_signature(hparams, world, shard_opt)
+        restored = _agree_on_state(state_path, signature, world)
+        if is_main:
+            print('resume_training: %s' % (
+                'no training state at %s, starting fresh' % state_path if restored is None else
+                'resuming after epoch %d from %s' % (restored['epoch'], state_path)))
+
+    if restored is not None:
+        rng_train = int(restored['rng_train'])
+    elif hparams.get('rng_seed_train', None) is None:
         rng_train = np.random.randint(0, 10000)
         if world > 1:       # every rank must walk the same trial order: rank 0's draw
             rng_train = int(bdist.broadcast_object(rng_train))
@@ -435,12 +679,31 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
     torch.manual_seed(rng_train)
     np.random.seed(rng_train)
 
-    expt_dir = os.path.join(hparams['expt_dir'], 'version_%i' % exp.version)
-    is_main = bdist.rank() == 0
-    show_bar = hparams.get('progress_bar', True) and is_main
-
     i_epoch = 0
-    for i_epoch in range(max_epochs + 1):
+    start_epoch = 0
+    if restored is not None:
+        # everything the loop carries from one epoch to the next (the epoch itself reseeds the RNGs)
+        model.load_state_dict(restored['model'])
+        optimizer.load_state_dict(restored['optimizer'])
+        best_val_loss, best_val_epoch = restored['best_val_loss'], restored['best_val_epoch']
+        best_model_saved = restored['best_model_saved']
+        if restored['best_model'] is not None:
+            best_val_model = _snapshot(model, hparams)
+            best_val_model.load_state_dict(restored['best_model'])
+            best_val_model.train(False)             # (it was taken at a validation check)
+            best_val_model.curr_epoch = best_val_epoch
+        if early_stop is not None:
+            early_stop.__dict__.update(restored['early_stop'])
+        logger.metrics, logger.metrics_by_dataset = copy.deepcopy(restored['logger'])
+        exp.metrics = [dict(row) for row in restored['rows']]
+        if is_main:
+            exp.save()                              # metrics.csv as far as the state goes
+        _set_rng_states(restored['rng'])
+        i_epoch = int(restored['epoch'])
+        start_epoch = max_epochs + 1 if early_stop is not None and early_stop.should_stop else i_epoch + 1
+        restored = None
+
+    for i_epoch in range(start_epoch, max_epochs + 1):
         # epoch 0 evaluates the randomly initialised model: forward/backward, no step (:320-322)
         if is_main:
             print_epoch(i_epoch, max_epochs)
@@ -524,8 +787,16 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
 
         if hparams['enable_early_stop']:
             early_stop.on_val_check(i_epoch, logger.get_loss('val'))
-            if early_stop.should_stop:
-                break
+        stopping = hparams['enable_early_stop'] and early_stop.should_stop
+        if resume and (i_epoch % state_every == 0 or stopping):
+            _save_training_state(
+                state_path, is_main, state_writer, writer, optimizer, shard_opt, model, exp, logger,
+                early_stop, signature,
+                {'epoch': i_epoch, 'rng_train': rng_train, 'best_val_loss': best_val_loss,
+                 'best_val_epoch': best_val_epoch, 'best_model_saved': best_model_saved,
+                 'best_model': best_val_model.state_dict() if best_val_model is not None else None})
+        if stopping:
+            break
 
     if not best_model_saved:
         _save_checkpoint(model, os.path.join(expt_dir, 'best_val_model.pt'), is_main, writer)
@@ -557,6 +828,11 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
         export_latents(data_generator, best_val_model)
     elif method == 'nll' and hparams.get('export_predictions', False):
         raise NotImplementedError('neural decoders are outside the MI355X hot path')
+    if resume and is_main:
+        if state_writer is not None:
+            state_writer.wait()
+        if os.path.exists(state_path):
+            os.remove(state_path)                   # the fit is complete: nothing left to resume
     return best_val_model
 
 

@@ -325,12 +325,51 @@ def export_hparams(hparams, exp):
     exp.save()
 
 
+def _reopen_unfinished(hparams):
+    """``resume_training``: the lowest version of this grid point (same ``get_model_params``) whose fit
+    did not complete, that holds a training state and that no other process has claimed -- claimed
+    now, its metric rows read back from the state.  -> Experiment or None."""
+    from behavenet_amd.fitting.experiment import Experiment
+    from behavenet_amd.fitting.training import TRAINING_STATE_FILE, read_training_state
+    want = get_model_params(hparams)
+    try:
+        versions = get_subdirs(hparams['expt_dir'])
+    except StopIteration:
+        return None
+    versions = sorted((v for v in versions if v.startswith('version_') and v[8:].isdigit()),
+                      key=lambda v: int(v[8:]))
+    for version in versions:
+        vdir = os.path.join(hparams['expt_dir'], version)
+        state_path = os.path.join(vdir, TRAINING_STATE_FILE)
+        try:
+            with open(os.path.join(vdir, 'meta_tags.pkl'), 'rb') as f:
+                have = pickle.load(f)
+        except IOError:
+            continue
+        if have.get('training_completed', True) or not os.path.exists(state_path) or \
+                not all(k in have and have[k] == v for k, v in want.items()):
+            continue
+        exp = Experiment(name=hparams['experiment_name'], debug=False, version=int(version[8:]),
+                         save_dir=os.path.dirname(hparams['expt_dir']))
+        if not exp.claim():
+            continue                    # another process is fitting it
+        state = read_training_state(state_path, mmap=True)
+        if state is None:               # completed (and removed) since we looked
+            exp.release()
+            continue
+        exp.metrics = [dict(row) for row in state['rows']]
+        print('resume_training: reopening %s (training state after epoch %d)' % (vdir, state['epoch']))
+        return exp
+    return None
+
+
 def create_experiment(hparams):
     """Prepare the directories of a fit and open a fresh ``version_K`` in them.
 
     -> (hparams, sess_ids, exp), or (None, None, None) if this grid point was fitted already.
     The experiment object is :class:`behavenet_amd.fitting.experiment.Experiment` (csv files in
-    test-tube's layout).
+    test-tube's layout).  With ``hparams['resume_training']`` an unfinished version of the same grid
+    point that holds a training state is reopened (and claimed) instead, if there is one.
     """
     from behavenet_amd.fitting.experiment import Experiment
     from behavenet_amd.fitting import distributed as bdist
@@ -352,9 +391,13 @@ def create_experiment(hparams):
                 export_session_info_to_csv(hparams['session_dir'], sess_ids)
             os.makedirs(hparams['expt_dir'], exist_ok=True)
             if not experiment_exists(hparams):
-                exp = Experiment(name=hparams['experiment_name'], debug=False,
-                                 save_dir=os.path.dirname(hparams['expt_dir']))
-                exp.save()
+                exp = _reopen_unfinished(hparams) if hparams.get('resume_training') else None
+                if exp is None:
+                    exp = Experiment(name=hparams['experiment_name'], debug=False,
+                                     save_dir=os.path.dirname(hparams['expt_dir']))
+                    if hparams.get('resume_training'):
+                        exp.claim()         # (a fresh version: nobody else knows it yet)
+                    exp.save()
                 version = exp.version
         except Exception as err:                     # noqa: BLE001 (re-raised below, on every rank)
             if not dp:
