@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: conv-AE training frames/s, 128x128x1 frames, batch (= trial) 256.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--shard trial|frames] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--shard trial|frames] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Started plainly with --gpus N > 1 (no WORLD_SIZE in the environment) the script launches its own
@@ -24,8 +24,14 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline:     enc.conv0 (the HBM-bound encoder conv BASELINE.json targets): algorithmic bytes
                 (589,824 B/frame = 65,536 in + 524,288 out) / HIP-event time of its launches
                 inside the timed region, vs 8 TB/s.
-  cpu_baseline: the CPU oracle (oracle/ref_cpu.py, the pinned restatement of the reference)
-                running the same step on this host's cores.
+
+A plain run does only what that line needs: setup, priming, the W warm-up and K timed steps,
+--dump-outputs, the line.  ``--full`` adds, after the timed steps, everything else the benchmark
+measures: per-kernel rooflines of the other layers (roofline_other_kernels), the live rocprofv3 PMC
+passes behind roofline.traffic (without them it is read from profiles/conv0_hbm_traffic.json), the
+secondary configs, the CPU baseline (the CPU oracle, oracle/ref_cpu.py, running the same step on
+this host's cores), the detail file (write_detail); with N > 1 also, during setup, the single-GPU
+reference of the job and the all-reduce timed alone.
 """
 
 import argparse
@@ -762,16 +768,20 @@ def measure_allreduce(opt, iters=10):
     return float(t.item()) * 1e3
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure what the headline line does not need: per-kernel '
+                         'rooflines, live PMC traffic, secondary configs, CPU baseline, the detail file (N > 1: '
+                         'the single-GPU reference and the all-reduce alone, during setup)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--no-pmc', action='store_true',
-                    help='skip the live rocprofv3 --pmc passes behind roofline.traffic')
+                    help='--full without the live rocprofv3 --pmc passes behind roofline.traffic')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='skip the secondary configs (PS-VAE, encode-only, PCIe-fed)')
+                    help='--full without the secondary configs (PS-VAE, encode-only, PCIe-fed, ...) and the PMC passes')
     ap.add_argument('--feed', default='device', choices=['device', 'device_u8', 'host_u8', 'host'],
                     help="where the trials live (default 'device': resident float32, the headline "
                          "metric; 'host_u8' = pinned uint8 + prefetch, the PCIe-inclusive rate)")
@@ -795,9 +805,14 @@ def main():
                          'loss values, the updated parameters and a fixed sample of the gradient; the untimed '
                          'priming then takes a fixed number of steps, so that runs with the same arguments get '
                          'the same inputs')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         if not torch.cuda.is_available():
             raise SystemExit('bench.py needs an MI355X: torch.cuda.is_available() is False')
@@ -960,9 +975,9 @@ def run(args):
     # N > 1: what ONE GPU of this job does on its own -- every rank runs the unsharded 256-frame step
     # without any exchange, all ranks at the same time (so the node's power / thermal state is the
     # job's), parameters and optimizer state put back afterwards.  This is the N = 1 figure the
-    # scaling curve is measured against, taken on the same boxes in the same process.
+    # scaling curve is measured against, taken on the same boxes in the same process (--full only).
     single_ref = None
-    if bdist.is_active():
+    if bdist.is_active() and args.full:
         keep = [t.clone() for t in (opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.max_exp_avg_sq)]
         keep_count = opt.step_count
         prev_mode = bdist.set_shard_mode('trial')
@@ -1025,7 +1040,7 @@ def run(args):
                           'ms_per_step_overlapped': round(timing[True] * 1e3, 3),
                           'ms_per_step_behind': round(timing[False] * 1e3, 3)}
     if bdist.is_active():
-        # what the collective library saw, and the exchange timed on its own
+        # what the collective library saw, and (--full) the exchange timed on its own
         allreduce_mode = dict(allreduce_mode or {'chosen': (
             'sharded optimizer: reduce-scatter -> Adam on 1/N of the arena -> all-gather, behind the '
             'backward pass' if shard_opt else 'one flat all-reduce behind the backward pass')})
@@ -1037,13 +1052,14 @@ def run(args):
             'gradient_bytes': int(opt.flat_g.numel() * 4),
             'bucket_bytes': [int((hi - lo) * 4) for lo, hi, _ in reducer.buckets]
             if reducer is not None else [int(opt.flat_g.numel() * 4)],
-            'allreduce_alone_ms': round(measure_allreduce(opt), 3),
             'shard_optimizer': bool(shard_opt),
             'shard_optimizer_decision': (
                 'default for --shard %s at N = %d (fitting/distributed.py default_shard_optimizer): %s'
                 % (args.shard, world, 'on' if shard_default else 'off')
                 if args.shard_optimizer is None else 'command line: %s' % ('on' if shard_opt else 'off')),
             'devices': devices, 'single_gpu_reference': single_ref})
+        if args.full:
+            allreduce_mode['allreduce_alone_ms'] = round(measure_allreduce(opt), 3)
     pet('warm-up')
     for _ in range(args.warmup):
         one_step(model, opt, gen)
@@ -1110,8 +1126,8 @@ def run(args):
     achieved = conv0_bytes / (conv0_ms * 1e-3) / 1e9 if conv0_ms > 0 else 0.0
     traffic = None
     traffic_source = None
-    # (not in the reduced runs of the tools / tests, which may themselves sit under rocprofv3)
-    if rank == 0 and world == 1 and not args.no_pmc and not args.no_secondary:
+    # (--full only, and not in the reduced runs of the tools / tests, which may themselves sit under rocprofv3)
+    if args.full and rank == 0 and world == 1 and not args.no_pmc and not args.no_secondary:
         traffic, info = live_hbm_traffic()
         if traffic is not None:
             traffic_source = ('measured in this run: two child processes `rocprofv3 --kernel-trace --pmc '
@@ -1136,11 +1152,12 @@ def run(args):
         'launches': conv0_n, 'avg_launch_us': round(conv0_ms * 1e3 / max(conv0_n, 1), 2),
         'algorithmic_bytes_per_launch_avg': int(conv0_bytes // max(conv0_n, 1)),
         'traffic': traffic,
-        'traffic_source': traffic_source,
+        'traffic_source': traffic_source}
+    if args.full:
         # what the same dispatch-attached events read around an EMPTY kernel: avg_launch_us is the
         # raw interval (not corrected); rocprofv3's kernel timestamps come out ~1.5-2 us lower
-        'event_interval_of_empty_kernel_us': round(float(_hip.load().bn_prof_dispatch_overhead_us(
-            50, torch.cuda.current_stream().cuda_stream)), 2)}
+        roofline['event_interval_of_empty_kernel_us'] = round(float(_hip.load().bn_prof_dispatch_overhead_us(
+            50, torch.cuda.current_stream().cuda_stream)), 2)
 
     out = {
         'metric': METRIC,
@@ -1182,8 +1199,8 @@ def run(args):
         'roofline': roofline,
     }
 
-    if rank == 0 and world == 1:
-        # FLOP-bound middle layers, profiled over two extra (untimed) steps each
+    if args.full and rank == 0 and world == 1:
+        # FLOP-bound middle layers, profiled over four extra (untimed) steps each
         extra = []
         # (C, K) as the dispatch reports them: gather-down / weight-gradient launches (big,
         # small) channels, gather-up launches (small, big) -- csrc/capi.hip run_down / run_up
@@ -1268,7 +1285,8 @@ def run(args):
                                        'sample': 'failed: %s: %s' % (type(err).__name__, str(err)[:300])}
 
     if rank == 0:
-        out['detail_file'] = write_detail(out)
+        if args.full:
+            out['detail_file'] = write_detail(out)
         sys.stderr.flush()
         print(json.dumps(out) if args.full_line else compact_line(out), flush=True)
     if dog is not None:

@@ -132,3 +132,31 @@ def test_bad_step_counts_are_refused(bench, argv, monkeypatch):
     with pytest.raises(SystemExit) as exc:
         bench.main()
     assert exc.value.code == 2
+
+
+def test_full_is_an_option_off_by_default(bench):
+    args = bench.parse_args(['--steps', '7', '--warmup', '2'])
+    assert args.full is False and args.steps == 7 and args.warmup == 2
+    assert bench.parse_args(['--full']).full is True
+
+
+@pytest.mark.gpu
+def test_plain_run_does_only_the_headline(bench, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the contract's keys and the enc.conv0 roofline of the
+    timed steps, nothing else -- no secondary configs, no CPU baseline, no detail file."""
+    import subprocess
+    detail = str(tmp_path / 'detail.json')
+    env = dict(os.environ, BN_BENCH_DETAIL=detail)
+    proc = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3',
+                           '--warmup', '1'], cwd=REPO, env=env, stdin=subprocess.DEVNULL, stdout=subprocess.PIPE,
+                          stderr=subprocess.PIPE, universal_newlines=True, timeout=240)
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    lines = [ln for ln in proc.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1, proc.stdout[-3000:]
+    d = json.loads(lines[0])
+    assert d['metric'] == bench.METRIC and d['unit'] == 'frames/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'f32' and d['steps'] == 3 and d['warmup'] == 1
+    assert abs(d['value'] - 256e3 / d['ms_per_step']) <= 0.01 * d['value']
+    assert d['roofline']['bound'] == 'hbm' and d['roofline']['avg_launch_us'] > 0
+    assert 'secondary' not in d and 'cpu_baseline' not in d and 'detail_file' not in d
+    assert not os.path.exists(detail)

@@ -393,11 +393,15 @@ def _bench_line(cmd, env, tmp_path, limit_s=240):
         out = f.read()
     lines = [ln for ln in out.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1, out[-3000:]
-    # the line the driver parses stays small; the full record sits in the detail file it names
+    # the line the driver parses stays small; the full record of a --full run sits in the detail file it names
     assert len(lines[0]) < 4096
     d = json.loads(lines[0])
-    with open(os.path.join(REPO, d['detail_file'])) as f:
-        d['detail'] = json.load(f)
+    if '--full' in cmd:
+        with open(os.path.join(REPO, d['detail_file'])) as f:
+            d['detail'] = json.load(f)
+    else:
+        # a plain run prints its line and writes no detail file
+        assert 'detail_file' not in d and not os.path.exists(env['BN_BENCH_DETAIL'])
     return d
 
 
@@ -410,7 +414,7 @@ def test_bench_two_ranks_control_flow(launcher, tmp_path):
     the ranks' trials), barrier-bracketed timing, max over ranks, one JSON line from rank 0 with
     the whole-job value and what the collective library saw."""
     env = _child_env(BN_DIST_BACKEND='gloo')
-    tail = [os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1',
+    tail = [os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--full',
             '--no-cpu-baseline', '--no-secondary']
     if launcher == 'torchrun':
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
@@ -506,7 +510,7 @@ def test_bench_four_ranks_frame_sharded_defaults(tmp_path):
     all-gather -- with four real processes on the one GPU over gloo: the trajectory reports the single-device
     loss, and the line says what ran."""
     env = _child_env(BN_DIST_BACKEND='gloo', BN_BENCH_PRIME='24')
-    tail = ['--steps', '4', '--warmup', '1', '--no-cpu-baseline', '--no-secondary', '--no-pmc']
+    tail = ['--steps', '4', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-secondary', '--no-pmc']
     # (started by torch.distributed.run itself: this process, the launcher and the four ranks are six processes
     # with the GPU open, the most a shared machine allows; a plain `bench.py --gpus 4` would add a seventh -- the
     # script's own launch is covered with two ranks above)
@@ -531,7 +535,7 @@ def test_bench_two_ranks_frame_sharded_mixed_graph_and_eager(tmp_path):
     rank 1's capture raises).  The collectives must still line up -- the job ends, reports the single-device loss --
     and the record says which ranks replay."""
     env = _child_env(BN_DIST_BACKEND='gloo', BN_BENCH_PRIME='24', BN_GRAPH='1', BN_GRAPH_FAULT_RANK='1')
-    tail = ['--steps', '4', '--warmup', '1', '--no-cpu-baseline', '--no-secondary', '--no-pmc']
+    tail = ['--steps', '4', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-secondary', '--no-pmc']
     d2 = _bench_line([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--shard', 'frames'] + tail,
                      env, tmp_path, limit_s=400)
     env1 = _child_env(BN_DIST_BACKEND='gloo', BN_BENCH_PRIME='24')
