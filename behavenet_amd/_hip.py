@@ -651,9 +651,20 @@ def kl_rows(mu, logvar):
     return out
 
 
+# widest latent block the decomposed-KL kernels serve (the grid search's max_latents)
+DECOMPOSED_KL_MAX_D = 64
+
+
+def _check_dkl_width(D):
+    if D > DECOMPOSED_KL_MAX_D:
+        raise ValueError('decomposed KL: %d latent dimensions, the kernels serve at most %d'
+                         % (D, DECOMPOSED_KL_MAX_D))
+
+
 def decomposed_kl_fwd(z, mu, logvar, out3=None):
     """-> (out3, log_qz, lse): the three KL terms and what the backward pass needs."""
     N, D = z.shape
+    _check_dkl_width(D)
     if out3 is None:
         out3 = torch.empty((3,), dtype=torch.float32, device=z.device)
     log_qz = torch.empty((N,), dtype=torch.float32, device=z.device)
@@ -668,6 +679,7 @@ def decomposed_kl_fwd(z, mu, logvar, out3=None):
 
 def decomposed_kl_bwd(z, mu, logvar, log_qz, lse, g3, out=None):
     N, D = z.shape
+    _check_dkl_width(D)
     dz, dmu, dlogvar = out if out is not None else (
         torch.empty_like(z), torch.empty_like(z), torch.empty_like(z))
     _check(load().bn_decomposed_kl_bwd(

@@ -319,7 +319,8 @@ int bn_kl_bwd(const float* mu, const float* logvar, float* dmu, float* dlogvar, 
               float scale, const float* gscale, bn_stream_t stream);
 
 /* Decomposed KL of the beta-TC-VAE / PS-VAE (replaces losses.decomposed_kl, losses.py:284-351,
- * and its autograd graph).  z, mu, logvar: (N, D) fp32, D <= 32.
+ * and its autograd graph).  z, mu, logvar: (N, D) fp32, N >= 1, D <= 64 (BN_E_SHAPE above; one
+ * kernel generation for D <= 32, a second, column-split one for 32 < D <= 64).
  *   fwd: out3 = (index-code MI, total correlation, dimension-wise KL); log_qz (N) and lse (N, D)
  *        are saved for the backward pass; terms is 3N floats of scratch.
  *   bwd: g3 = the three upstream gradients (device); dz, dmu, dlogvar: (N, D). */
