@@ -12,7 +12,7 @@ import os
 import torch
 
 _LIB_NAME = 'libbehavenet_hip.so'
-# BN_HIP_LIB: an alternative build of the same ABI (csrc `make tuning`: experiment hooks compiled in)
+# BN_HIP_LIB: an alternative build of the same ABI (tools/build_variant.sh, A/B of two whole libraries)
 _LIB_PATH = os.environ.get('BN_HIP_LIB') or os.path.join(
     os.path.dirname(os.path.abspath(__file__)), _LIB_NAME)
 _lib = None

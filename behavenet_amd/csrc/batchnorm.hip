@@ -726,9 +726,6 @@ static bool bno_fits(const BnChunks& ch, int C, int HW, const void* a, const voi
         if (cnt > (long)BNO_THREADS * BNO_NV) return false;
         total += ch.end[z] - ch.beg[z];
     }
-    static int off = -1;                                 // BN_BN_OWNED=0: the two-launch forms (tuning builds)
-    if (off < 0) { const char* e = bn_tune_env("BN_BN_OWNED"); off = (e && e[0] == '0') ? 1 : 0; }
-    if (off) return false;
     // few channels: only when the tensor is small anyway (a workgroup per channel must fill the chip)
     return C >= 64 || (size_t)total * C * HW * 4 <= ((size_t)2 << 20);
 }

@@ -195,16 +195,10 @@ static inline BnGeom convT_geom(int N, int Ci, int Hi, int Wi, int Co, int R, in
     return g;
 }
 
-// BN_FORCE_GENERIC=1 in the environment disables every fast path (used by tests to cross-check
-// the specialised kernels against the shape-agnostic ones on the device).
-static int g_force_generic = -1;
-static bool force_generic() {
-    if (g_force_generic < 0) {
-        const char* e = bn_tune_env("BN_FORCE_GENERIC");
-        g_force_generic = (e && e[0] == '1') ? 1 : 0;
-    }
-    return g_force_generic == 1;
-}
+// bn_set_force_generic(1) disables every fast path (used by tests to cross-check the specialised
+// kernels against the shape-agnostic ones on the device).
+static int g_force_generic = 0;
+static bool force_generic() { return g_force_generic == 1; }
 extern "C" int bn_set_force_generic(int on) {
     const int prev = force_generic() ? 1 : 0;
     g_force_generic = on ? 1 : 0;
@@ -468,11 +462,6 @@ struct BigK {
     int sgn;                            // +1: gather-down / weight gradient, -1: gather-up
     int Hy, Wy;                         // the phase maps
 };
-static bool bigk_enabled() {
-    static int mode = -1;                              // BN_BIGK=0: off (the im2col detour, tuning builds)
-    if (mode < 0) { const char* e = bn_tune_env("BN_BIGK"); mode = (e && e[0] == '0') ? 0 : 1; }
-    return mode == 1;
-}
 // one axis: phase rho of the big map meets the taps 2u + k (k = parity of rho + pad, u < U) at small pixel
 // p = i + o - u.  As a stride-1 5-tap kernel with padding p1 that is tap u' = u - o + p1 (gather-down, sgn +1) or
 // u' = o + p1 - u (gather-up, sgn -1); false if no p1 in 0..4 holds both phases in 5 taps
@@ -490,7 +479,7 @@ static bool bigk_phase_axis(int R, int pad, int sgn, int* k, int* of, int* p1) {
     return false;
 }
 static bool bigk_plan(int role, const BnGeom& g, BnGeom* g5, BigK* k) {
-    if (force_generic() || !bigk_enabled() || g.stride != 2 || g.CsS) return false;
+    if (force_generic() || g.stride != 2 || g.CsS) return false;
     if (g.R < 6 || g.R > 10 || g.S < 6 || g.S > 10) return false;
     if ((g.Hb & 1) || (g.Wb & 3)) return false;
     int pt1 = 0, pl1 = 0;
@@ -522,7 +511,7 @@ extern "C" size_t bn_set_bigk1_block_bytes(size_t bytes) {
     return prev;
 }
 static bool bigk1_plan(int role, const BnGeom& g, BnGeom* g5, BigK1* k) {
-    if (force_generic() || !bigk_enabled() || g.stride != 1 || g.CsS || role == 1) return false;
+    if (force_generic() || g.stride != 1 || g.CsS || role == 1) return false;
     if (g.R < 6 || g.R > 10 || g.S < 6 || g.S > 10) return false;
     k->L0r = (g.R + 1) / 2; k->L0c = (g.S + 1) / 2;
     k->dr[0] = -g.pt; k->dr[1] = k->L0r - g.pt;
@@ -575,9 +564,7 @@ static inline size_t bigk_w_bytes(const BnGeom& g) { return align256((size_t)g.C
 // stride == kernel layers between maps other than 8x8 and 2x2 (the last layer of 64x48 / 192x160 frames): the
 // weight gradient as ONE GEMM over the (permuted) windows instead of the first-generation direct kernel
 static bool s5_wgrad_by_col(const BnGeom& g) {
-    static int mode = -1;                              // BN_S5_WGRAD_COL=0: off (tuning build)
-    if (mode < 0) { const char* e = bn_tune_env("BN_S5_WGRAD_COL"); mode = (e && e[0] == '0') ? 0 : 1; }
-    if (!mode || force_generic() || g.stride != 5 || g.R != 5 || g.S != 5) return false;
+    if (force_generic() || g.stride != 5 || g.R != 5 || g.S != 5) return false;
     if (bn_qg2_wgrad_supported(g) || bn_qgemm_supported(g)) return false;
     return bn_s5_wgrad_plan(g).supported && bn_col_ok(g) && (size_t)g.N * g.Hs * g.Ws >= 512;
 }

@@ -554,9 +554,7 @@ BnFastPlan bn_edge_wgrad_plan(const BnGeom& g) {
     if (g.Ws != WC_W || (g.Hs % WC_ROWS) != 0 || g.Hb != 2 * g.Hs || g.Wb != 2 * g.Ws) {
         // round 4: any other map (64x48, 192x160 frames) in row / column blocks on the first-generation
         // kernel -- no zero-padded or tiled copies of the two operands
-        static int off = -1;                          // BN_WGRAD_C1G=0: off
-        if (off < 0) { const char* e = bn_tune_env("BN_WGRAD_C1G"); off = (e && e[0] == '0') ? 1 : 0; }
-        if (off || g.pt > 4 || g.pl > 4 || (g.CsS > 0 && g.CsS != g.Cs)) return p;
+        if (g.pt > 4 || g.pl > 4 || (g.CsS > 0 && g.CsS != g.Cs)) return p;
         p.supported = true;
         p.variant = 1;
         p.d = wgrad_c1_grid(g);
@@ -686,17 +684,11 @@ int bn_launch_edge_wgrad(const BnFastPlan& plan, const float* small, const float
 #define DC_WPE 3
 #endif
 #define DC_HTS 36                        // half-row slab row stride
-#ifndef DC_VARIANT
-#define DC_VARIANT 5                     // product build, float frames, forward, 32 channels: fourth
-                                         // generation on 8-row strips (k_down_c1p_*_s8; 4 = the same on
-                                         // 16-row strips, 3 = third generation k_down_c1w) where the
-                                         // geometry holds, else the first generation (0).  Same bits.
-                                         // tools/lab/e0_lab.hip, 256 frames, inputs and outputs rotated
-                                         // through > 256 MB, behind clean L2s / a 35 MB memset:
-                                         // generation 1 31.5 / 32.8 us, 2 36.6 / 37.1, 3 31.4 / 33.5,
-                                         // 4 on 16-row strips 30.9 / 31.9, on 8-row strips 27.3 / 27.9.
-                                         // uint8 frames and the masked data gradient: second generation
-#endif
+// Float frames, forward: k_down_c1p on 8-row strips (32 channels), else k_down_c1w, else k_down_c1, each
+// where its geometry holds (bn_launch_edge_down).  Same bits.  256 frames, inputs and outputs rotated
+// through > 256 MB, behind clean L2s / a 35 MB memset: k_down_c1 31.5 / 32.8 us, k_down_c1w 31.4 / 33.5,
+// k_down_c1p 27.3 / 27.9 on 8-row strips (30.9 / 31.9 on 16-row strips and k_down_c1s on float 4-row units
+// 36.6 / 37.1: removed).  uint8 frames and the masked data gradient: k_down_c1s.
 
 #ifndef DC_ST_AUX
 #define DC_ST_AUX 16                     // cache policy of the first generation's 16-byte output stores
@@ -1367,8 +1359,8 @@ __global__ __launch_bounds__(64 * DW_WAVES) __attribute__((amdgpu_waves_per_eu(4
 #define DP_ST_AUX 16                         // cache policy of the dword output stores: sc1 (write-through),
                                              // 27.3 / 27.9 us against 29.9 / 31.4 plain (0) behind clean / memset L2s
 #endif
-// STRIP = output rows per strip (16: 35 patch rows in 5 DMA rounds, 4 rows per wave; 8: 19 patch rows in 3
-// rounds, 2 rows per wave)
+// STRIP = output rows per strip (8: 19 patch rows in 3 DMA rounds, 2 rows per wave; the 16-row strips, 35 patch
+// rows in 5 rounds, measured slower and are not instantiated)
 template <int STRIP> struct DpGeom {
     static constexpr int IH = 2 * STRIP + 3;                    // patch rows
     static constexpr int NG = IH * DC_C4;                    // 16-byte groups of the strip image (34 per row)
@@ -1566,19 +1558,16 @@ __device__ __forceinline__ void dp_body(
         float* __restrict__ out, BnGeom g, float slope, int units) {                                   \
         dp_body<ACT, STRIP>(big, w, bias, out, g, slope, units);                                       \
     }
-DP_KERNEL(k_down_c1p_lrelu_s16, BN_ACT_LRELU, 16)
-DP_KERNEL(k_down_c1p_none_s16, BN_ACT_NONE, 16)
 DP_KERNEL(k_down_c1p_lrelu_s8, BN_ACT_LRELU, 8)
 DP_KERNEL(k_down_c1p_none_s8, BN_ACT_NONE, 8)
 #undef DP_KERNEL
 
-template <int ACT, int STRIP>
+template <int ACT>
 static int launch_down_c1p(const float* big, const float* w, const float* bias, float* out,
                            const BnGeom& g, float slope, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
     typedef void (*kernel_t)(const float*, const float*, const float*, float*, BnGeom, float, int);
-    const kernel_t kernel = STRIP == 16
-        ? (ACT == BN_ACT_LRELU ? k_down_c1p_lrelu_s16 : k_down_c1p_none_s16)
-        : (ACT == BN_ACT_LRELU ? k_down_c1p_lrelu_s8 : k_down_c1p_none_s8);
+    constexpr int STRIP = 8;
+    const kernel_t kernel = ACT == BN_ACT_LRELU ? k_down_c1p_lrelu_s8 : k_down_c1p_none_s8;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)kernel,
@@ -1587,10 +1576,8 @@ static int launch_down_c1p(const float* big, const float* w, const float* bias, 
         attr_set = true;
     }
     const int units = g.N * (g.Hs / STRIP);
-    int grid = units;                                  // one strip per workgroup; the dispatcher balances
-    if (const char* e = bn_tune_env("BN_E0_WGRID")) grid = atoi(e);     // (tuning build only)
-    if (grid > units) grid = units;
-    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(64 * DW_WAVES), DpGeom<STRIP>::LDS, st, e0, e1, 0,
+    // one strip per workgroup; the dispatcher balances
+    hipExtLaunchKernelGGL(kernel, dim3(units), dim3(64 * DW_WAVES), DpGeom<STRIP>::LDS, st, e0, e1, 0,
                           big, w, bias, out, g, slope, units);
     BN_LAUNCH_CHECK();
     return 0;
@@ -1599,8 +1586,8 @@ static int launch_down_c1p(const float* big, const float* w, const float* bias, 
 static bool down_c1w_ok(const BnGeom& g) {
     return g.Cb == 1 && (g.Hs % DW_SROWS) == 0 && g.pt <= 2 && DC_ST_AUX >= 0;
 }
-static bool down_c1p_ok(const BnGeom& g, int strip) {
-    return g.Cb == 1 && g.Cs == 32 && (g.Hs % strip) == 0 && g.pt <= 2;
+static bool down_c1p_ok(const BnGeom& g) {          // 8-row strips
+    return g.Cb == 1 && g.Cs == 32 && (g.Hs % 8) == 0 && g.pt <= 2;
 }
 
 template <int ACT>
@@ -1614,9 +1601,7 @@ static int launch_down_c1w(const float* big, const float* w, const float* bias, 
         attr_set = true;
     }
     const int units = g.N * (g.Hs / DW_SROWS);
-    int grid = 256 * 4;                               // 4 workgroups of 38 KB per CU
-    if (const char* e = bn_tune_env("BN_E0_WGRID")) grid = atoi(e);     // (tuning build only)
-    if (grid > units) grid = units;
+    const int grid = units < 256 * 4 ? units : 256 * 4;   // 4 workgroups of 38 KB per CU
     hipExtLaunchKernelGGL((k_down_c1w<ACT>), dim3(grid), dim3(64 * DW_WAVES), DW_LDS, st, e0, e1, 0,
                           big, w, bias, out, g, slope, units);
     BN_LAUNCH_CHECK();
@@ -1634,9 +1619,7 @@ BnFastPlan bn_edge_down_plan(const BnGeom& g) {
         // round 4: single-channel frames of any other size (widths in multiples of 4) on the first-generation
         // kernel in blocks of 64 columns -- no zero-padded / tiled copies (variant 9: no uint8 input, no
         // channel window)
-        static int off = -1;                          // BN_DOWN_C1G=0: off
-        if (off < 0) { const char* e = bn_tune_env("BN_DOWN_C1G"); off = (e && e[0] == '0') ? 1 : 0; }
-        if (off || (g.Ws & 3) || (g.Wb & 3) || (g.CsS > 0 && g.CsS != g.Cs)) return p;
+        if ((g.Ws & 3) || (g.Wb & 3) || (g.CsS > 0 && g.CsS != g.Cs)) return p;
         p.supported = true;
         p.variant = 9;
         p.kernel_name = g.Cb == 2 ? "k_down_c1s<.., 2, 2, gen>" : "k_down_c1<gen>";
@@ -1649,11 +1632,6 @@ BnFastPlan bn_edge_down_plan(const BnGeom& g) {
 
 // grid = waves; every CU should get the same number of units in the fewest rounds
 static int down_c1_grid(int units) {
-#ifdef BN_TUNING
-    static int env_grid = -1;                       // BN_E0_GRID=<waves>
-    if (env_grid < 0) { const char* e = bn_tune_env("BN_E0_GRID"); env_grid = e ? atoi(e) : 0; }
-    if (env_grid > 0) return env_grid < units ? env_grid : units;
-#endif
     const int n_cu = 256;
     const int per_cu = (units + n_cu - 1) / n_cu;
     const int rounds = (per_cu + DC_MAX_WAVES_PER_CU - 1) / DC_MAX_WAVES_PER_CU;
@@ -1667,9 +1645,7 @@ static int launch_down_c1s(const void* big, const float* w, const float* bias, f
                            const float* dact_src, const BnGeom& g, float slope, hipStream_t st,
                            hipEvent_t e0, hipEvent_t e1) {
     const int units = g.N * (g.Hs / ROWS);
-    int grid = 256 * DC_MAX_WAVES_PER_CU;
-    if (const char* e = bn_tune_env("BN_E0_SGRID")) grid = atoi(e);     // (tuning build only)
-    if (grid > units) grid = units;
+    const int grid = units < 256 * DC_MAX_WAVES_PER_CU ? units : 256 * DC_MAX_WAVES_PER_CU;
     hipExtLaunchKernelGGL((k_down_c1s<ACT, MASK, U8, ROWS, CB>), dim3(grid), dim3(64), 0, st, e0, e1,
                           0, big, w, bias, out, dact_src, g, slope, units);
     BN_LAUNCH_CHECK();
@@ -1692,9 +1668,8 @@ const char* bn_edge_down_kernel_name(const BnGeom& g, int act, bool has_dact, bo
         return lrelu ? "k_down_c1s<1, false, true, 2, 1>" : "k_down_c1s<0, false, true, 2, 1>";
     }
     if (has_dact) return "k_down_c1s<0, true, false, 2, 1>";
-    if (DC_VARIANT == 5 && down_c1p_ok(g, 8)) return lrelu ? "k_down_c1p_lrelu_s8" : "k_down_c1p_none_s8";
-    if (DC_VARIANT >= 4 && down_c1p_ok(g, 16)) return lrelu ? "k_down_c1p_lrelu_s16" : "k_down_c1p_none_s16";
-    if (DC_VARIANT >= 3 && down_c1w_ok(g)) return lrelu ? "k_down_c1w<1>" : "k_down_c1w<0>";
+    if (down_c1p_ok(g)) return lrelu ? "k_down_c1p_lrelu_s8" : "k_down_c1p_none_s8";
+    if (down_c1w_ok(g)) return lrelu ? "k_down_c1w<1>" : "k_down_c1w<0>";
     return lrelu ? "k_down_c1<1, false>" : "k_down_c1<0, false>";
 }
 
@@ -1735,9 +1710,10 @@ int bn_launch_edge_down(const float* big, const float* w, const float* bias, flo
         BN_LAUNCH_CHECK();
         return 0;
     }
-    // Product choice, measured INSIDE the training step (rocprofv3, 256 frames; the isolated
-    // ranking differs): plain forward -> first generation (31.7-32.8 us vs 33.7-34.6 us);
-    // data gradient with the LeakyReLU' mask -> second generation, 2-row units (48.2 vs 52.6 us).
+    // Measured INSIDE the training step (rocprofv3, 256 frames; the isolated ranking differs): plain
+    // forward -> k_down_c1 before k_down_c1s (31.7-32.8 us vs 33.7-34.6 us); data gradient with the
+    // LeakyReLU' mask -> k_down_c1s, 2-row units (48.2 us vs 52.6 for k_down_c1 with the mask, which is
+    // instantiated for other maps only: GENW).
     if (g.Cb == 2) {     // two-channel frames: swapped-role kernel, 2-row units
         if (u8) return BN_E_SHAPE;
         if (act == BN_ACT_LRELU && !dact_src)
@@ -1746,11 +1722,8 @@ int bn_launch_edge_down(const float* big, const float* w, const float* bias, flo
             return launch_down_c1s<BN_ACT_NONE, false, false, 2, 2>(big, w, bias, out, nullptr, g, slope, st, e0, e1);
         return launch_down_c1s<BN_ACT_NONE, true, false, 2, 2>(big, w, bias, out, dact_src, g, slope, st, e0, e1);
     }
-    int variant = dact_src ? 1 : DC_VARIANT;
-    if (const char* e = bn_tune_env("BN_E0_V")) variant = atoi(e);   // (tuning build only)
-    if (variant == 2 && (g.Hs % 4) != 0) variant = 1;
     if (u8) {
-        if ((g.Hs % 4) == 0)       // uint8 frames: second generation only, 4-row units
+        if ((g.Hs % 4) == 0)       // uint8 frames: k_down_c1s only, 4-row units
             return act == BN_ACT_LRELU
                 ? launch_down_c1s<BN_ACT_LRELU, false, true, 4>(u8, w, bias, out, nullptr, g, slope, st, e0, e1)
                 : launch_down_c1s<BN_ACT_NONE, false, true, 4>(u8, w, bias, out, nullptr, g, slope, st, e0, e1);
@@ -1758,49 +1731,30 @@ int bn_launch_edge_down(const float* big, const float* w, const float* bias, flo
             ? launch_down_c1s<BN_ACT_LRELU, false, true, 2>(u8, w, bias, out, nullptr, g, slope, st, e0, e1)
             : launch_down_c1s<BN_ACT_NONE, false, true, 2>(u8, w, bias, out, nullptr, g, slope, st, e0, e1);
     }
-    if (variant == 5 && !down_c1p_ok(g, 8)) variant = 4;
-    if ((variant == 4 || variant == 5) && !dact_src && down_c1p_ok(g, variant == 5 ? 8 : 16)) {
-        if (variant == 5)
-            return act == BN_ACT_LRELU
-                ? launch_down_c1p<BN_ACT_LRELU, 8>(big, w, bias, out, g, slope, st, e0, e1)
-                : launch_down_c1p<BN_ACT_NONE, 8>(big, w, bias, out, g, slope, st, e0, e1);
+    if (!dact_src && down_c1p_ok(g))
         return act == BN_ACT_LRELU
-            ? launch_down_c1p<BN_ACT_LRELU, 16>(big, w, bias, out, g, slope, st, e0, e1)
-            : launch_down_c1p<BN_ACT_NONE, 16>(big, w, bias, out, g, slope, st, e0, e1);
-    }
-    if (variant == 4 || variant == 5) variant = 3;
-    // (a channel window in wider frames, BnGeom::CsS: only k_down_c1p and k_down_c1s address it)
-    const bool windowed = g.CsS > 0 && g.CsS != g.Cs;
-    if (windowed && variant != 1 && variant != 2) variant = 1;
-    if (variant == 3 && !dact_src && down_c1w_ok(g))
-        return act == BN_ACT_LRELU
-            ? launch_down_c1w<BN_ACT_LRELU>(big, w, bias, out, g, slope, st, e0, e1)
-            : launch_down_c1w<BN_ACT_NONE>(big, w, bias, out, g, slope, st, e0, e1);
-    if (variant == 3) variant = dact_src ? 1 : 0;
-    if (variant == 2) {
-        if (act == BN_ACT_LRELU && !dact_src)
-            return launch_down_c1s<BN_ACT_LRELU, false, false, 4>(big, w, bias, out, nullptr, g, slope, st, e0, e1);
-        if (!dact_src)
-            return launch_down_c1s<BN_ACT_NONE, false, false, 4>(big, w, bias, out, nullptr, g, slope, st, e0, e1);
-        return launch_down_c1s<BN_ACT_NONE, true, false, 4>(big, w, bias, out, dact_src, g, slope, st, e0, e1);
-    }
-    if (variant == 1) {
+            ? launch_down_c1p<BN_ACT_LRELU>(big, w, bias, out, g, slope, st, e0, e1)
+            : launch_down_c1p<BN_ACT_NONE>(big, w, bias, out, g, slope, st, e0, e1);
+    // the masked data gradient, and a channel window in wider frames (BnGeom::CsS: only k_down_c1p and
+    // k_down_c1s address it): k_down_c1s, 2-row units
+    if (dact_src || (g.CsS > 0 && g.CsS != g.Cs)) {
         if (act == BN_ACT_LRELU && !dact_src)
             return launch_down_c1s<BN_ACT_LRELU, false, false, 2>(big, w, bias, out, nullptr, g, slope, st, e0, e1);
         if (!dact_src)
             return launch_down_c1s<BN_ACT_NONE, false, false, 2>(big, w, bias, out, nullptr, g, slope, st, e0, e1);
         return launch_down_c1s<BN_ACT_NONE, true, false, 2>(big, w, bias, out, dact_src, g, slope, st, e0, e1);
     }
+    if (down_c1w_ok(g))
+        return act == BN_ACT_LRELU
+            ? launch_down_c1w<BN_ACT_LRELU>(big, w, bias, out, g, slope, st, e0, e1)
+            : launch_down_c1w<BN_ACT_NONE>(big, w, bias, out, g, slope, st, e0, e1);
     const int units = g.N * (g.Hs / DC_ROWS);
     const dim3 grid(down_c1_grid(units));
-    if (act == BN_ACT_LRELU && !dact_src) {
+    if (act == BN_ACT_LRELU) {
         hipExtLaunchKernelGGL((k_down_c1<BN_ACT_LRELU, false>), grid, dim3(64), 0, st, e0, e1, 0,
                               big, w, bias, out, dact_src, g, slope, units);
-    } else if (act == BN_ACT_NONE && !dact_src) {
+    } else {
         hipExtLaunchKernelGGL((k_down_c1<BN_ACT_NONE, false>), grid, dim3(64), 0, st, e0, e1, 0,
-                              big, w, bias, out, dact_src, g, slope, units);
-    } else {   // data gradient: no activation of its own, LeakyReLU' mask of the layer below
-        hipExtLaunchKernelGGL((k_down_c1<BN_ACT_NONE, true>), grid, dim3(64), 0, st, e0, e1, 0,
                               big, w, bias, out, dact_src, g, slope, units);
     }
     BN_LAUNCH_CHECK();
@@ -1808,104 +1762,10 @@ int bn_launch_edge_down(const float* big, const float* w, const float* bias, flo
 }
 
 // =============================================================================================
-// gather-up with one big-side channel (dec.convT4 forward):
-//   out[n,0,h,w] = act( b + sum_{c,r,s} small[n,c,p,q] * W[c][0][r][s] ),  2p+r = h+1, 2q+s = w+1
-// Two phases per workgroup (8 small-image rows -> 16 x 128 output pixels):
-//  1. a skinny GEMM on the matrix cores  T[tap][pos] = sum_c W[c][tap] * small[c][pos]
-//     (rows = 25 taps, K = Cs channels, columns = positions incl. a one-pixel halo), small read
-//     straight from HBM in wavefront rows, T kept in LDS;
-//  2. every output pixel gathers its <= 9 contributions T[(r,s)][(p,q)] from LDS, adds the
-//     bias, applies the activation and is stored as float2 (both column parities per lane).
-// =============================================================================================
-#define UC_TH 8
-#define UC_W 64
-#define UC_PW (UC_W + 2)                      // positions per row incl. halo
-#define UC_NPOS ((UC_TH + 2) * UC_PW)         // 660
-#define UC_NBLK ((UC_NPOS + 31) / 32)         // 21
-#define UC_DP (UC_NBLK * 32)                  // 672: row stride of T in LDS
-#define UC_LDS (25 * UC_DP * 4)
-
-__global__ __launch_bounds__(ED_THREADS) void k_up_c1(
-    const float* __restrict__ small, const float* __restrict__ w, const float* __restrict__ bias,
-    float* __restrict__ out, BnGeom g, int act, float slope) {
-    extern __shared__ __attribute__((aligned(16))) float dl[];     // T[25][UC_DP]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 31, kk = lane >> 5;
-    const int tiles_per_frame = g.Hs / UC_TH;
-    const int n = blockIdx.x / tiles_per_frame;
-    const int a0 = (blockIdx.x - n * tiles_per_frame) * UC_TH;
-    const int HWs = g.Hs * g.Ws;
-
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)small, 0, (int)((size_t)g.N * g.Cs * HWs * 4), 0x00020000);
-
-    // A operand: W[c = 2t+kk][tap = li]   (Cs <= 32 -> 16 steps)
-    float av[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-        const int c = 2 * t + kk;
-        av[t] = (li < 25 && c < g.Cs) ? w[(c * g.Cb + blockIdx.y) * 25 + li] : 0.f;
-    }
-
-    for (int blk = wv; blk < UC_NBLK; blk += 4) {
-        const int f = blk * 32 + li;
-        const int py = f / UC_PW, px = f - py * UC_PW;
-        const int p = a0 - 1 + py, q = px - 1;
-        const bool ok = f < UC_NPOS && p >= 0 && p < g.Hs && q >= 0 && q < g.Ws;
-        const int boff = ok ? ((n * g.Cs + kk) * HWs + p * g.Ws + q) * 4 : ED_OOB;
-        float bv[16];
-#pragma unroll
-        for (int t = 0; t < 16; ++t)
-            bv[t] = ed_ld(rs, (ok && 2 * t + kk < g.Cs) ? boff + t * (2 * HWs * 4) : ED_OOB);
-        floatx16 acc;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-        for (int t = 0; t < 16; ++t)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bv[t], acc, 0, 0, 0);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int tap = (e & 3) + 8 * (e >> 2) + 4 * kk;
-            if (tap < 25) dl[tap * UC_DP + f] = acc[e];
-        }
-    }
-    __syncthreads();
-
-    // phase 2: thread -> column pair b (w = 2b, 2b+1), wave -> row h_l = 4k + wv
-    const int b = lane;
-    const float bs = bias ? bias[blockIdx.y] : 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int hl = 4 * k + wv;                 // 0..15
-        const int h = 2 * a0 + hl;
-        const int hh = hl + 1;                     // (h + pt) relative to row 2*a0, pt = 1
-        float o0 = 0.f, o1 = 0.f;
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {
-            const int r = (hh & 1) + 2 * u;
-            if (r >= 5) continue;
-            const int py = ((hh - r) >> 1) + 1;     // position row inside the tile (halo = 1)
-            const float* row = dl + py * UC_PW;
-            // w = 2b   -> ww = 2b+1: s in {1,3}, q = b - {0,1}   -> px = q + 1
-            o0 += row[(r * 5 + 1) * UC_DP + b + 1] + row[(r * 5 + 3) * UC_DP + b];
-            // w = 2b+1 -> ww = 2b+2: s in {0,2,4}, q = b + 1 - {0,1,2}
-            o1 += (row[(r * 5 + 0) * UC_DP + b + 2] + row[(r * 5 + 2) * UC_DP + b + 1]) +
-                  row[(r * 5 + 4) * UC_DP + b];
-        }
-        float2 v;
-        v.x = bn_apply_act(o0 + bs, act, slope);
-        v.y = bn_apply_act(o1 + bs, act, slope);
-        *reinterpret_cast<float2*>(
-            out + (((size_t)n * g.Cb + blockIdx.y) * g.Hb + h) * g.Wb + 2 * b) = v;
-    }
-}
-
-// =============================================================================================
-// gather-up with few big-side channels, second generation (dec.convT4 forward [+ loss epilogue]):
+// gather-up with few big-side channels (dec.convT4 forward [+ loss epilogue]):
 //   out[n,b,h,w] = act( bias[b] + sum_{c,r,s} small[n,c,p,q] * W[c][b][r][s] ),
 //   2p + r = h + 1, 2q + s = w + 1
-// 11 FLOP per byte and ONE output channel: there is no matrix shape to feed, so this generation
+// 11 FLOP per byte and ONE output channel: there is no matrix shape to feed, so k_up_c1v
 // is a register-resident VALU kernel that touches neither LDS nor the matrix cores:
 //  * a workgroup is ONE wave, lane q = column q of the 64-wide small image; a unit is a strip of
 //    R small-image rows of one frame (plus one halo row above and below, of which only the taps
@@ -1922,10 +1782,6 @@ __global__ __launch_bounds__(ED_THREADS) void k_up_c1(
 //    goes to memory unless asked for (reference aes.py:330 + losses.py:56-59).
 // =============================================================================================
 #define UV_W 64
-#ifndef UP_C1_VARIANT
-#define UP_C1_VARIANT 1                  // 1: k_up_c1m (matrix cores) where its geometry holds (in the
-                                         // training step 41.6 us against 51.0 for k_up_c1v on one box)
-#endif
 
 __device__ __forceinline__ float uv_shift_from_left(float v) {      // lane q <- lane q-1, 0 at q=0
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(
@@ -2338,6 +2194,7 @@ __global__ __launch_bounds__(512) void k_up_c1m(
     }
 }
 
+// k_up_c1m (matrix cores) where its geometry holds: in the training step 41.6 us against 51.0 for k_up_c1v
 static bool up_c1m_ok(const BnGeom& g) {
     // (one workgroup per frame and output channel: small batches keep the finer-grained k_up_c1v)
     return g.N * g.Cb >= 128 &&
@@ -2353,9 +2210,6 @@ BnFastPlan bn_edge_up_plan(const BnGeom& g) {
     if (g.Ws != UV_W || (g.Hs % 8) != 0) {
         // round 4: any other small map in blocks of 62 columns (k_up_c1v<8, .., GENW>; variant 9; the fused
         // pixel loss since round 5)
-        static int off = -1;                          // BN_UP_C1G=0: off
-        if (off < 0) { const char* e = bn_tune_env("BN_UP_C1G"); off = (e && e[0] == '0') ? 1 : 0; }
-        if (off) return p;
         p.supported = true;
         p.variant = 9;
         p.kernel_name = "k_up_c1v<8, false, gen>";
@@ -2368,7 +2222,7 @@ BnFastPlan bn_edge_up_plan(const BnGeom& g) {
 
 const char* bn_edge_up_kernel_name(const BnGeom& g, bool loss) {
     if (g.Ws != UV_W || (g.Hs % 8) != 0) return loss ? "k_up_c1v<8, true, gen>" : "k_up_c1v<8, false, gen>";
-    if (UP_C1_VARIANT == 1 && up_c1m_ok(g)) return loss ? "k_up_c1m<true>" : "k_up_c1m<false>";
+    if (up_c1m_ok(g)) return loss ? "k_up_c1m<true>" : "k_up_c1m<false>";
     return loss ? "k_up_c1v<8, true>" : "k_up_c1v<8, false>";
 }
 
@@ -2385,23 +2239,6 @@ int bn_edge_up_parts_per_frame(const BnGeom& g) {
 int bn_launch_edge_up(const float* small, const float* w, const float* bias, float* out,
                       const BnGeom& g, int act, float slope, hipStream_t st, const float* target,
                       const float* mask, float* dpre, float* partial) {
-#ifdef BN_TUNING
-    static int old = -1;
-    if (old < 0) { const char* e = bn_tune_env("BN_UP_C1_OLD"); old = (e && e[0] == '1') ? 1 : 0; }
-    if (old && !target) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute((const void*)k_up_c1,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, UC_LDS);
-            if (e != hipSuccess) return (int)e;
-            attr_set = true;
-        }
-        BN_LAUNCH_MAIN(k_up_c1, dim3(g.N * (g.Hs / UC_TH), g.Cb), dim3(ED_THREADS), UC_LDS, st,
-                           small, w, bias, out, g, act, slope);
-        BN_LAUNCH_CHECK();
-        return 0;
-    }
-#endif
     if (up_c1_gen(g)) {
         const int unitsg = g.N * g.Cb * ((g.Hs + UV_R - 1) / UV_R) * ((g.Ws + 61) / 62);
         // (the loss epilogue reads / writes pixel pairs: 8-byte accesses need an even row length, which
@@ -2417,9 +2254,7 @@ int bn_launch_edge_up(const float* small, const float* w, const float* bias, flo
         BN_LAUNCH_CHECK();
         return 0;
     }
-    int use_m = UP_C1_VARIANT == 1 && up_c1m_ok(g);
-    if (const char* e = bn_tune_env("BN_UP_C1_M")) use_m = atoi(e) && up_c1m_ok(g);     // (tuning build only)
-    if (use_m) {
+    if (up_c1m_ok(g)) {
         const dim3 grid_m(g.N, g.Cb), block_m(64 * (g.Hs / UM_R));
         if (target)
             BN_LAUNCH_MAIN((k_up_c1m<true>), grid_m, block_m, 0, st, small, w, bias, out, target, mask,
@@ -2436,25 +2271,6 @@ int bn_launch_edge_up(const float* small, const float* w, const float* bias, flo
         BN_LAUNCH_MAIN((k_up_c1v<UV_R, true>), dim3(grid), dim3(64), 0, st, small, w, bias, out,
                            target, mask, dpre, partial, g, act, slope, units);
     } else {
-#ifdef BN_TUNING
-        static int r4 = -1;
-        if (r4 < 0) { const char* e = bn_tune_env("BN_UP_C1_R4"); r4 = e ? atoi(e) : 0; }
-        if (r4 == 1) {
-            const int units4 = g.N * g.Cb * (g.Hs / 4);
-            BN_LAUNCH_MAIN((k_up_c1v<4, false>), dim3(units4 < 256 * 24 ? units4 : 256 * 24),
-                               dim3(64), 0, st, small, w, bias, out, nullptr, nullptr, nullptr,
-                               nullptr, g, act, slope, units4);
-            BN_LAUNCH_CHECK();
-            return 0;
-        }
-        if (r4 == 16) {
-            const int units16 = g.N * g.Cb * (g.Hs / 16);
-            BN_LAUNCH_MAIN((k_up_c1v<16, false>), dim3(units16), dim3(64), 0, st, small, w, bias,
-                               out, nullptr, nullptr, nullptr, nullptr, g, act, slope, units16);
-            BN_LAUNCH_CHECK();
-            return 0;
-        }
-#endif
         BN_LAUNCH_MAIN((k_up_c1v<UV_R, false>), dim3(grid), dim3(64), 0, st, small, w, bias, out,
                            nullptr, nullptr, nullptr, nullptr, g, act, slope, units);
     }

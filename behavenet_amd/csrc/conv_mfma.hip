@@ -38,7 +38,6 @@ struct DownTile {
     int xl_floats;
     int c_per_split;     // channels of the reduction handled by one blockIdx.z
     int splits;
-    int dbg;             // BN_DOWN_DBG experiments (0 in production)
 };
 
 // Software pipeline: the global loads of chunk i+1 (input tile + weight slice) are issued into
@@ -148,7 +147,6 @@ __global__ __launch_bounds__(MF_THREADS, 2) void k_down_mfma(
     issue_loads(c_beg);
     for (int c0 = c_beg; c0 < c_end; c0 += CC) {
         __syncthreads();   // the previous chunk's MFMA reads of LDS are complete
-        if (!(t.dbg & 1) || c0 == c_beg) {
 #pragma unroll
         for (int cc = 0; cc < CC; ++cc) {
             const bool cok = c0 + cc < c_end;
@@ -170,9 +168,8 @@ __global__ __launch_bounds__(MF_THREADS, 2) void k_down_mfma(
                 }
             }
         }
-        }
         __syncthreads();
-        if (c0 + CC < c_end && !(t.dbg & 1)) issue_loads(c0 + CC);   // behind the MFMAs below
+        if (c0 + CC < c_end) issue_loads(c0 + CC);   // behind the MFMAs below
 
         // MFMA loop, one (channel pair, kernel row) = S taps per "row".  Operands are double
         // buffered by hand: the LDS reads of row i+1 are issued BEFORE the MFMAs of row i (the
@@ -368,11 +365,9 @@ BnFastPlan bn_fast_down_plan(const BnGeom& g) {
     if (g.Cs == 16 && g.R == 5 && g.S == 5 && (g.stride == 1 || g.stride == 2) && g.K0 == 0) {
         // round 6: a 16-channel small side on the 16-row MFMA tile (k_down2_m16) -- the 32-row tiles below would
         // multiply 16 rows of zeros; the 256-pixel tile unless the 128-pixel one wastes fewer pixels
-        static int off = -1;
-        if (off < 0) { const char* e = bn_tune_env("BN_DOWN_M16"); off = (e && e[0] == '0') ? 1 : 0; }
         float fill = 0.f;
         int bn = 0;
-        for (int nr = 2; nr >= 1 && !off; --nr) {
+        for (int nr = 2; nr >= 1; --nr) {
             if (!bn_down2_m16_supported(g, nr)) continue;
             const float f = bn_down2_fill(g, 1, nr);
             if (f > fill + 0.02f) { fill = f; bn = nr; }
@@ -429,7 +424,7 @@ BnFastPlan bn_fast_down_plan(const BnGeom& g) {
     // 64 ch x 256 px tile halves the per-workgroup prologue / epilogue share and still gives
     // >= 2 workgroups per CU (E1 322 -> 290 us, E2 286 -> 260 us at 256 frames; the 8x8 maps of
     // E3 / D1 are faster with 128-pixel tiles)
-    if (g.stride == 2 && g.Ws >= 16 && g.Cs >= 64 && !bn_tune_env("BN_DOWN_TILE")) {
+    if (g.stride == 2 && g.Ws >= 16 && g.Cs >= 64) {
         int nwg = 0;
         if (down_tile(g, 2, 2, CC, &t, &nwg) && nwg >= 512) {
             best = 1;
@@ -448,16 +443,6 @@ BnFastPlan bn_fast_down_plan(const BnGeom& g) {
         if (best_wg >= want) break;
     }
     if (best >= 0) down_tile(g, cand[best][0], cand[best][1], CC, &t, &best_wg);
-    // tuning hook (tools/kbench.py): BN_DOWN_TILE=<candidate index 0..2> pins the tile shape
-    if (const char* e = bn_tune_env("BN_DOWN_TILE")) {
-        const int i = e[0] - '0';
-        int nwg = 0;
-        if (i >= 0 && i < 3 && !(cand[i][0] == 2 && g.Cs < 64) &&
-            down_tile(g, cand[i][0], cand[i][1], CC, &t, &nwg)) {
-            best = i;
-            best_wg = nwg;
-        }
-    }
     if (best < 0 && g.stride == 2 && g.R == 5 && g.S == 5) {
         // maps whose sizes are no powers of two (64x48 or 192x160 frames): the second-generation kernel
         // takes any even width and any height; the tile shape that wastes the fewest pixels
@@ -495,10 +480,6 @@ BnFastPlan bn_fast_down_plan(const BnGeom& g) {
         if (splits > 16) splits = 16;
         if (splits < 1) splits = 1;
     }
-    if (const char* e = bn_tune_env("BN_DOWN_SPLITS")) {       // tuning hook
-        const int v = atoi(e);
-        if (v >= 1 && v <= 16 && v <= (g.Cb / CC)) splits = v;
-    }
     p.d = splits;
     p.ws_bytes = splits > 1 ? (size_t)splits * g.N * g.Cs * g.Hs * g.Ws * sizeof(float) : 0;
     // names as rocprofv3 prints the instantiations (leading template arguments)
@@ -518,7 +499,7 @@ BnFastPlan bn_fast_down_plan(const BnGeom& g) {
     // small batches: the streamlined kernel on the LARGEST tile that fits, its reduction split over
     // workgroups (round 4; the first generation's split path is 20 % slower per FLOP, and the
     // unsplit 32-channel tile ran 128 workgroups of 54 us for a 32-frame shard)
-    if (g.stride == 2 && CC == 4 && !bn_tune_env("BN_DOWN_SPLITS") && !bn_tune_env("BN_DOWN_TILE")) {
+    if (g.stride == 2 && CC == 4) {
         for (int i = 0; i < 3; ++i) {
             const int mr = cand[i][0], nr = cand[i][1];
             if (mr == 2 && g.Cs < 64) continue;
@@ -566,9 +547,6 @@ int bn_launch_down_fast(const BnFastPlan& plan, const float* big, const float* w
     int nwg = 0;
     if (!down_tile(g, MR, NR, CC, &t, &nwg)) return BN_E_SHAPE;
     t.splits = splits;
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = bn_tune_env("BN_DOWN_DBG"); dbg = e ? atoi(e) : 0; }
-    t.dbg = dbg;
     if (splits > 1) {
         int cps = (g.Cb + splits - 1) / splits;
         cps = (cps + CC - 1) / CC * CC;

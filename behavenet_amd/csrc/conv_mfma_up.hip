@@ -39,7 +39,6 @@ struct UpTile {
     int SWp, FS, CHS;             // LDS strides of the small tile (floats)
     int tiles_per_frame;
     int xl_floats;
-    int dbg;              // BN_UP_DBG experiments (0 in production)
 };
 
 template <int MR, int CC>
@@ -639,17 +638,12 @@ static bool up_tile(const BnGeom& g, int MR, int CC, UpTile* t, int* n_wg) {
 }
 
 // streamlined kernel: square 8x8 / 16x16 / 32x32 small images, whole chunks of channels
-static bool up2_ok(const BnGeom& g, int* cc_out) {
-    static int mode = -1;                 // BN_UP2=0: off; BN_UP2=8: 8-channel chunks
-    if (mode < 0) { const char* e = bn_tune_env("BN_UP2"); mode = e ? atoi(e) : 4; }
-    if (mode == 0) return false;
+static bool up2_ok(const BnGeom& g) {
     const int lgw = ilog2_exact_up(g.Ws);
     if (g.Hs != g.Ws || lgw < 3 || lgw > 5) return false;
-    const int cc = (mode == 8 && (g.Cs % 8) == 0) ? 8 : 4;
-    if ((g.Cs % cc) != 0 || (g.Cb & 3) != 0) return false;
+    if ((g.Cs % 4) != 0 || (g.Cb & 3) != 0) return false;
     if ((size_t)g.N * g.Cb * g.Hb * g.Wb * 4 >= 0x7fffffffull) return false;
     if ((size_t)g.N * g.Cs * g.Hs * g.Ws * 4 >= 0x7fffffffull) return false;
-    *cc_out = cc;
     return true;
 }
 
@@ -806,18 +800,12 @@ BnFastPlan bn_fast_up_plan(const BnGeom& g) {
     if (g.Cb < 16 || g.Cs < 2) return p;
     UpTile t;
     int nwg2 = 0, nwg1 = 0;
-    static int env_mr = -1, env_cc = -1;          // tuning hooks: BN_UP_MR=1|2, BN_UP_CC=4|8
-    if (env_mr < 0) { const char* e = bn_tune_env("BN_UP_MR"); env_mr = e ? atoi(e) : 0; }
-    if (env_cc < 0) { const char* e = bn_tune_env("BN_UP_CC"); env_cc = e ? atoi(e) : 0; }
-    const int cc = (env_cc == 8 && (g.Cs % 8) == 0) ? 8 : 4;
-    const bool ok2 = g.Cb >= 64 && up_tile(g, 2, cc, &t, &nwg2);
-    const bool ok1 = up_tile(g, 1, cc, &t, &nwg1);
+    const bool ok2 = g.Cb >= 64 && up_tile(g, 2, 4, &t, &nwg2);
+    const bool ok1 = up_tile(g, 1, 4, &t, &nwg1);
     if (!ok1 && !ok2) {
         // no power-of-two map: the streamlined kernel with its tile geometry at run time
         Up2Geo tg;
-        static int off = -1;                      // BN_UP2G=0: off
-        if (off < 0) { const char* e = bn_tune_env("BN_UP2G"); off = (e && e[0] == '0') ? 1 : 0; }
-        if (off || !up2g_geo(g, &tg)) return p;
+        if (!up2g_geo(g, &tg)) return p;
         p.supported = true;
         p.a = 1; p.c = 4; p.variant = 3;
         p.kernel_name = tg.CHS > UP2<0>::CHSP ? "k_up2_mfma<1, 4>" : "k_up2_mfma<0, 4>";
@@ -827,20 +815,16 @@ BnFastPlan bn_fast_up_plan(const BnGeom& g) {
     }
     p.supported = true;
     p.a = (ok2 && (nwg2 >= 768 || !ok1)) ? 2 : 1;
-    if (env_mr == 2 && ok2) p.a = 2;
-    if (env_mr == 1 && ok1) p.a = 1;
-    p.c = cc;
-    p.kernel_name = p.a == 2 ? (cc == 8 ? "k_up_mfma<2, 8>" : "k_up_mfma<2, 4>")
-                             : (cc == 8 ? "k_up_mfma<1, 8>" : "k_up_mfma<1, 4>");
+    p.c = 4;
+    p.kernel_name = p.a == 2 ? "k_up_mfma<2, 4>" : "k_up_mfma<1, 4>";
     // the streamlined kernel wherever it applies (round 3: 64-channel big sides used to take the
     // two-block first-generation kernel once the grid was large: 530 against 2 x 206 us)
-    if ((p.a == 1 || (ok1 && env_mr != 2)) && up2_ok(g, &p.c)) {
+    if ((p.a == 1 || ok1) && up2_ok(g)) {
         p.a = 1;
         p.variant = 2;
         const int lgw = ilog2_exact_up(g.Ws);
         static const char* const n4[6] = {"", "", "", "k_up2_mfma<3, 4>", "k_up2_mfma<4, 4>", "k_up2_mfma<5, 4>"};
-        static const char* const n8[6] = {"", "", "", "k_up2_mfma<3, 8>", "k_up2_mfma<4, 8>", "k_up2_mfma<5, 8>"};
-        p.kernel_name = p.c == 8 ? n8[lgw] : n4[lgw];
+        p.kernel_name = n4[lgw];
         p.d = up2_splits(g, lgw, p.c);
         p.ws_bytes = p.d > 1 ? (size_t)p.d * g.N * g.Cb * g.Hb * g.Wb * sizeof(float) : 0;
     }
@@ -870,27 +854,18 @@ int bn_launch_up_fast(const BnFastPlan& plan, const float* small, const float* w
         return launch_up2<L, 4, 4>(small, w, bias, out, dact_src, g, act, dact, slope, st, splits, ws);
         UP2_CASE4(3) UP2_CASE4(4) UP2_CASE4(5)
 #undef UP2_CASE4
-        UP2_CASE(3, 4) UP2_CASE(4, 4) UP2_CASE(5, 4) UP2_CASE(3, 8) UP2_CASE(4, 8) UP2_CASE(5, 8)
+        UP2_CASE(3, 4) UP2_CASE(4, 4) UP2_CASE(5, 4)
 #undef UP2_CASE
         return BN_E_SHAPE;
     }
     UpTile t;
     int nwg = 0;
     if (!up_tile(g, MR, CC, &t, &nwg)) return BN_E_SHAPE;
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = bn_tune_env("BN_UP_DBG"); dbg = e ? atoi(e) : 0; }
-    t.dbg = dbg;
     const int groups = (g.N + t.F - 1) / t.F;
     dim3 grid(groups * t.tiles_per_frame, (g.Cb + 32 * MR - 1) / (32 * MR));
     const size_t lds = up_lds_bytes(t.xl_floats, MR, CC);
-    if (MR == 2 && CC == 8) {
-        BN_LAUNCH_MAIN((k_up_mfma<2, 8>), grid, dim3(MF_THREADS), lds, st, small, w, bias, out,
-                           dact_src, g, t, act, dact, slope);
-    } else if (MR == 2) {
+    if (MR == 2) {
         BN_LAUNCH_MAIN((k_up_mfma<2, 4>), grid, dim3(MF_THREADS), lds, st, small, w, bias, out,
-                           dact_src, g, t, act, dact, slope);
-    } else if (CC == 8) {
-        BN_LAUNCH_MAIN((k_up_mfma<1, 8>), grid, dim3(MF_THREADS), lds, st, small, w, bias, out,
                            dact_src, g, t, act, dact, slope);
     } else {
         BN_LAUNCH_MAIN((k_up_mfma<1, 4>), grid, dim3(MF_THREADS), lds, st, small, w, bias, out,

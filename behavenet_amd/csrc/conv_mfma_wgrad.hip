@@ -53,7 +53,6 @@ struct WgradTile {
     int rows_per_b;                // F * IH
     int splits;                    // reduction splits (gridDim.y)
     int buf_floats;                // one LDS stage image: WG_TA*WG_SP + WG_TB*BCH (16-B multiple)
-    int dbg;                       // BN_WGRAD_DBG experiments (0 in production)
 };
 
 template <int LGQ>
@@ -143,8 +142,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void k_wgrad_mfma(
         // own DMAs of this stage have landed; after the barrier everyone's have, and every wave
         // is done reading the other image (it was computed from in the previous trip)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (!(t.dbg & 2)) __syncthreads();
-        const bool more = (st + t.splits < t.n_stages) && !(t.dbg & 1);
+        __syncthreads();
+        const bool more = st + t.splits < t.n_stages;
 
         const float* ap = smem + cur * t.buf_floats + a_off;
         const float* bp = smem + cur * t.buf_floats + b_off;
@@ -277,9 +276,6 @@ int bn_launch_wgrad_fast(const BnFastPlan& plan, const float* small, const float
     size_t lds = 0;
     if (!wgrad_tile(g, &t, &lds)) return BN_E_SHAPE;
     t.splits = plan.d;
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = bn_tune_env("BN_WGRAD_DBG"); dbg = e ? atoi(e) : 0; }
-    t.dbg = dbg;
     const int tiles = ((g.Cs + WG_TA - 1) / WG_TA) * ((g.Cb + WG_TB - 1) / WG_TB);
     dim3 grid(tiles, t.splits);
     int rc = BN_E_SHAPE;

@@ -605,9 +605,6 @@ static int wgrad4_splits(const BnGeom& g, const Wgrad4Tile& t) {
 
 // stages inside one frame, geometry = the compile-time one of W4S<LGQ>
 static bool wgrad4s_ok(const BnGeom& g, const Wgrad4Tile& t) {
-    static int disabled = -1;                          // BN_WGRAD4S=0: the general kernel only
-    if (disabled < 0) { const char* e = bn_tune_env("BN_WGRAD4S"); disabled = (e && e[0] == '0') ? 1 : 0; }
-    if (disabled) return false;
     const int lgq = ilog2_exact_w4(g.Ws);
     if (t.F != 1 || lgq < 3 || lgq > 5) return false;
     if (g.Hb != 2 * g.Hs) return false;                // the row classes of the DMA assume it
@@ -633,9 +630,6 @@ static inline int w4g_pth(const BnGeom& g) {
 // instantiated for, any height, big map exactly twice the small one
 static const int W4G_WIDTHS[] = {4, 6, 8, 10, 12, 14, 16, 20, 24, 28, 32, 36, 40, 44};   // (4: maps of at most four rows)
 static bool wgrad4g_ok(const BnGeom& g) {
-    static int disabled = -1;                          // BN_WGRAD4G=0: off
-    if (disabled < 0) { const char* e = bn_tune_env("BN_WGRAD4G"); disabled = (e && e[0] == '0') ? 1 : 0; }
-    if (disabled) return false;
     if (g.pt != 1 || g.pl != 1 || g.Hb != 2 * g.Hs || g.Wb != 2 * g.Ws) return false;
     bool width = w4g_window(g) != 0;
     for (int q : W4G_WIDTHS) width = width || q == g.Ws;
@@ -650,9 +644,6 @@ static bool wgrad4g_ok(const BnGeom& g) {
 }
 // stride 1 (5x5 taps, offsets up to 4): power-of-two widths up to 64, any height
 static bool wgrad4g1_ok(const BnGeom& g) {
-    static int disabled = -1;                          // BN_WGRAD4G1=0: off
-    if (disabled < 0) { const char* e = bn_tune_env("BN_WGRAD4G1"); disabled = (e && e[0] == '0') ? 1 : 0; }
-    if (disabled) return false;
     if (g.stride != 1 || g.R != 5 || g.S != 5 || g.pt > 4 || g.pl > 4) return false;
     static const int widths[] = {8, 12, 16, 20, 24, 32, 40, 48, 64};
     bool width = false;
@@ -674,9 +665,7 @@ static int wgrad4g_stages(const BnGeom& g) {
 // on 16- / 32- / 64-pixel-wide maps; 1 = none
 static int w4g1_groups(const BnGeom& g, int* na, int* nb) {
     *na = 4; *nb = 2;
-    static int off = -1;                               // BN_W4_GROUPS=0: off (tuning build)
-    if (off < 0) { const char* e = bn_tune_env("BN_W4_GROUPS"); off = (e && e[0] == '0') ? 1 : 0; }
-    if (off || g.Cs > 32) return 1;
+    if (g.Cs > 32) return 1;
     // (stride 2: the power-of-two instantiations, 8 / 16 / 32-wide small maps -- the caller has checked wgrad4s_ok)
     if (g.stride == 1 ? (g.Ws != 16 && g.Ws != 32 && g.Ws != 64) : (g.Ws != 8 && g.Ws != 16 && g.Ws != 32)) return 1;
     if (g.KV == 4 && g.K0 != 1) return 1;              // (4x4 kernels: instantiated without groups; 3x3: with)
@@ -689,9 +678,6 @@ BnFastPlan bn_wgrad4_plan(const BnGeom& g) {
     BnFastPlan p = {false, "k_wgrad_generic", 0, 0, 0, 0, 0, 0};
     if (g.R != 5 || g.S != 5 || (g.stride != 2 && g.stride != 1)) return p;
     if (g.Cs < 16 || g.Cb < 16) return p;
-    static int disabled = -1;                          // BN_WGRAD4=0: fall back to the dword-DMA kernel
-    if (disabled < 0) { const char* e = bn_tune_env("BN_WGRAD4"); disabled = (e && e[0] == '0') ? 1 : 0; }
-    if (disabled) return p;
     Wgrad4Tile t;
     size_t lds = 0;
     if (g.stride == 1) {

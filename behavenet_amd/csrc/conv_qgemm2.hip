@@ -205,9 +205,6 @@ __global__ __launch_bounds__(Q2_THREADS, 1) void k_qg2_up(
 }
 
 bool bn_qg2_up_supported(const BnGeom& g, int act, int dact) {
-    static int disabled = -1;                          // BN_QG2=0: first generation (conv_qgemm.hip)
-    if (disabled < 0) { const char* e = bn_tune_env("BN_QG2"); disabled = (e && e[0] == '0') ? 1 : 0; }
-    if (disabled) return false;
     if (!bn_qgemm_supported(g)) return false;
     if (act == BN_ACT_SIGMOID || dact == BN_ACT_SIGMOID) return false;
     if ((g.Cs % Q2U_KS) != 0 || (g.Cb & 7) != 0) return false;
@@ -453,9 +450,6 @@ __global__ __launch_bounds__(Q2_THREADS, 1) void k_qg2_wgrad(
 }
 
 bool bn_qg2_wgrad_supported(const BnGeom& g) {
-    static int disabled = -1;                          // BN_QG2=0: first generation (conv_qgemm.hip)
-    if (disabled < 0) { const char* e = bn_tune_env("BN_QG2"); disabled = (e && e[0] == '0') ? 1 : 0; }
-    if (disabled) return false;
     if (!bn_qgemm_supported(g)) return false;
     return (g.Cs % 64) == 0 && (g.Cb % 8) == 0;
 }

@@ -404,9 +404,6 @@ __global__ __launch_bounds__(256) void k_s5w_finish_down(
 // host side
 // ---------------------------------------------------------------------------------------------
 bool bn_s5win_supported(const BnGeom& g) {
-    static int disabled = -1;                          // BN_S5WIN=0: the previous paths (tuning builds)
-    if (disabled < 0) { const char* e = bn_tune_env("BN_S5WIN"); disabled = (e && e[0] == '0') ? 1 : 0; }
-    if (disabled) return false;
     if (g.R != 5 || g.S != 5 || g.stride != 5 || g.CsS != 0 || g.KV != 0 || g.K0 != 0) return false;
     if (g.pt > 4 || g.pl > 4 || g.Hs < 1 || g.Ws < 1) return false;
     // the windows tile the big map: every big pixel in exactly one window (what TF-"same" padding plans),

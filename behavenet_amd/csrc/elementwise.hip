@@ -380,11 +380,7 @@ int bn_launch_adam(float* p, const float* g, float* m, float* v, float* vmax, si
     const float step_size = (float)((double)lr / bc1);
     const float bc2_sqrt = (float)sqrt(bc2);
     int vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(vmax);
-    if (vec && n * 4 < 0x7fffffffull) {
-        vec = 2;                                   // arenas addressable by a buffer descriptor
-        const char* e = bn_tune_env("BN_ADAM_WT");
-        if (e && e[0] == '0') vec = 1;
-    }
+    if (vec && n * 4 < 0x7fffffffull) vec = 2;     // arenas addressable by a buffer descriptor
     BN_LAUNCH_MAIN(k_adam_amsgrad, dim3(ew_blocks(vec ? n / 4 + 1 : n)), dim3(EW_THREADS), 0,
                        st, p, g, m, v, vmax, n, step_size, b1, b2, bc2_sqrt, eps, wd, vec);
     BN_LAUNCH_CHECK();

@@ -67,8 +67,7 @@ const char* bn_error_string(int code);        /* static string for a BN_E_* / hi
 #define BN_OP_CONVT_BWD_D 5
 #define BN_OP_CONVT_BWD_W 6
 /* Test hook: on != 0 routes every convolution through the shape-agnostic kernels (so the
- * specialised ones can be cross-checked on the device).  Returns the previous setting.  The
- * environment variable BN_FORCE_GENERIC=1 sets the initial value. */
+ * specialised ones can be cross-checked on the device).  Returns the previous setting (initially 0). */
 int bn_set_force_generic(int on);
 /* Test hook: stride-1 layers with kernels larger than 5x5 run on four shifted copies of their big map, frames in
  * blocks whose copies stay below `bytes` (default and maximum 0x70000000: the kernels' 32-bit offsets); a small value

@@ -1,12 +1,12 @@
-// Stand-alone laboratory for enc.conv0 forward (conv_edge.hip is #included as it is):
-//   e0_lab [variant 0|1|2|3 ...]      0 = k_down_c1, 1 / 2 = k_down_c1s with 2- / 4-row units, 3 = k_down_c1w
+// Stand-alone laboratory for enc.conv0 forward (conv_edge.hip is #included as it is): the kernel
+// bn_launch_edge_down serves the layer with (k_down_c1p on 8-row strips).
 // 256 frames, 1x128x128 -> 32x64x64, LeakyReLU.  Every timed launch follows a kernel that streams
 // 140 MB of plain stores through the L2s (what Adam leaves behind in the training step); times are
-// the dispatch-attached event intervals bench.py uses.  The outputs of all variants are compared
-// word for word with variant 0.  Built with -DE0_TRACE the kernels also leave per-wave
+// the dispatch-attached event intervals bench.py uses.  A checksum of the output is printed (two
+// builds of the source must agree).  Built with -DE0_TRACE the kernel also leaves per-wave
 // s_memrealtime marks (start, first patch in LDS, first row multiplied, first row stored, first
 // unit done, all stores issued, all stores acknowledged): the ramp of the store stream.
-// build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -DBN_TUNING [-DE0_TRACE] tools/lab/e0_lab.hip -o tools/lab/bin/e0_lab
+// build: hipcc -O3 -std=c++17 --offload-arch=gfx950 [-DE0_TRACE] tools/lab/e0_lab.hip -o tools/lab/bin/e0_lab
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void k_heat(float* sink, int iters, float seed
     if (t == 12345.678f) sink[threadIdx.x] = t;
 }
 
-int main(int argc, char** argv) {
+int main() {
     const int N = 256;
     BnGeom g; g.CsS = 0;
     g.N = N; g.R = g.S = 5; g.stride = 2; g.pt = 1; g.pl = 1;
@@ -66,14 +66,14 @@ int main(int argc, char** argv) {
     for (auto& v : hb) v = (float)(rand() % 256) / 255.f;
     for (auto& v : hw) v = ((rand() / (float)RAND_MAX) - 0.5f) * 0.4f;
     for (auto& v : hbias) v = (rand() / (float)RAND_MAX) - 0.5f;
-    float *db, *dw, *dbias, *o_ref, *o; float4* dirty;
+    float *db, *dw, *dbias, *o_ref; float4* dirty;
     const size_t dirty_n4 = 140u * 1000 * 1000 / 16;
     // E0_RING=K (default 20): K copies of the input and 3 output buffers, rotated per launch, so that the
     // 256 MB Infinity Cache serves neither the reads nor the writes (in the training step 20 trials of
     // 16.8 MB and gigabytes of other traffic pass between two launches)
     const int ring = getenv("E0_RING") ? atoi(getenv("E0_RING")) : 20;
     CK(hipMalloc(&db, nb * 4 * ring)); CK(hipMalloc(&dw, 800 * 4)); CK(hipMalloc(&dbias, 32 * 4));
-    CK(hipMalloc(&o_ref, ns * 4 * 3)); CK(hipMalloc(&o, ns * 4)); CK(hipMalloc(&dirty, dirty_n4 * 16));
+    CK(hipMalloc(&o_ref, ns * 4 * 3)); CK(hipMalloc(&dirty, dirty_n4 * 16));
     for (int r = 0; r < ring; ++r) CK(hipMemcpy(db + r * nb, hb.data(), nb * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(dw, hw.data(), 800 * 4, hipMemcpyHostToDevice));
     CK(hipMemcpy(dbias, hbias.data(), 32 * 4, hipMemcpyHostToDevice));
@@ -84,11 +84,9 @@ int main(int argc, char** argv) {
     unsigned long long* dtrace; CK(hipMalloc(&dtrace, trace_words * 8));
     CK(hipMemcpyToSymbol(HIP_SYMBOL(e0_trace), &dtrace, sizeof(dtrace)));
 #endif
-    std::vector<float> h_ref(ns), h(ns);
-    for (int a = 1; a < (argc > 1 ? argc : 2); ++a) {
-        const char* variant = argc > 1 ? argv[a] : "0";
-        setenv("BN_E0_V", variant, 1);
-        float* out = a == 1 ? o_ref : o;
+    std::vector<float> h_ref(ns);
+    {
+        float* out = o_ref;
         CK(hipMemsetAsync(out, 0xff, ns * 4, st));
         std::vector<float> ts;
         for (int i = 0; i < 23; ++i) {
@@ -115,30 +113,12 @@ int main(int argc, char** argv) {
         }
         std::sort(ts.begin(), ts.end());
         const double bytes = (double)N * (65536 + 524288);
-        printf("variant %s: median %.2f us (min %.2f, max %.2f)  %.2f TB/s = %.3f of 8 TB/s\n", variant, ts[ts.size() / 2],
+        printf("%s: median %.2f us (min %.2f, max %.2f)  %.2f TB/s = %.3f of 8 TB/s\n",
+               bn_edge_down_kernel_name(g, BN_ACT_LRELU, false, false), ts[ts.size() / 2],
                ts[0], ts.back(), bytes / ts[ts.size() / 2] / 1e6, bytes / ts[ts.size() / 2] / 1e6 / 8.0);
-        CK(hipMemcpy(a == 1 ? h_ref.data() : h.data(), out, ns * 4, hipMemcpyDeviceToHost));
-        if (a > 1) {
-            size_t diff = 0;
-            for (size_t i = 0; i < ns; ++i) if (memcmp(&h_ref[i], &h[i], 4)) ++diff;
-            printf("  output vs first variant: %zu of %zu words differ\n", diff, ns);
-            if (diff) {      // where: (frame, row) pairs with differences, and a sample
-                int shown = 0;
-                for (int n = 0; n < N && shown < 12; ++n)
-                    for (int p = 0; p < 64 && shown < 12; ++p) {
-                        size_t cnt = 0, first = 0;
-                        for (int c = 0; c < 32; ++c)
-                            for (int q = 0; q < 64; ++q) {
-                                const size_t i = (((size_t)n * 32 + c) * 64 + p) * 64 + q;
-                                if (memcmp(&h_ref[i], &h[i], 4)) { if (!cnt) first = i; ++cnt; }
-                            }
-                        if (cnt) { printf("    frame %d row %d: %zu words, e.g. [%zu] %g vs %g\n", n, p, cnt, first, h_ref[first], h[first]); ++shown; }
-                    }
-            }
-        } else {
-            double cs = 0; for (size_t i = 0; i < ns; i += 997) cs += h_ref[i];
-            printf("  checksum %.6f\n", cs);
-        }
+        CK(hipMemcpy(h_ref.data(), out, ns * 4, hipMemcpyDeviceToHost));
+        double cs = 0; for (size_t i = 0; i < ns; i += 997) cs += h_ref[i];
+        printf("  checksum %.6f\n", cs);
 #ifdef E0_TRACE
         std::vector<unsigned long long> tr(trace_words);
         CK(hipMemcpy(tr.data(), dtrace, trace_words * 8, hipMemcpyDeviceToHost));
