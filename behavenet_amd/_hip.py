@@ -110,6 +110,14 @@ SIGNATURES = {
         [_c_int] * 4 + [_c_void_p]),
     'bn_adam_amsgrad_step': (
         _c_int, [_c_void_p] * 5 + [_c_size_t] + [_c_float] * 5 + [_c_int, _c_void_p]),
+    'bn_conv2d_first_bf16_ok': (_c_int, _CONV_GEOM),
+    'bn_conv2d_bf16_ok': (_c_int, _CONV_GEOM),
+    'bn_conv_pack_w_bf16_bytes': (_c_size_t, [_c_int] * 4),
+    'bn_conv_pack_w_bf16': (_c_int, [_c_void_p] * 2 + [_c_int] * 4 + [_c_void_p]),
+    'bn_conv2d_first_bf16': (
+        _c_int, [_c_void_p, _c_int] + [_c_void_p] * 3 + _CONV_GEOM + [_c_int, _c_float, _c_void_p]),
+    'bn_conv2d_fwd_bf16': (
+        _c_int, [_c_void_p] * 4 + [_c_int] + _CONV_GEOM + [_c_int, _c_float, _c_void_p]),
     'bn_u8_to_unit_float': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
@@ -328,6 +336,69 @@ def convT2d_bwd_weight(x, dy, dw, db, geom, accumulate):
     _check(lib_call('bn_convT2d_bwd_weight')(
         _ptr(x, 'x'), _ptr(dy, 'dy'), _ptr(dw, 'dw'), _ptr(db, 'db', allow_none=True), *geom,
         int(accumulate), ws, nb, _stream()), 'bn_convT2d_bwd_weight')
+
+
+# ------------------------------------------------------------------------------------------
+# inference-only bf16 encoder stack (csrc/conv_bf16.hip).  Activations between its layers are
+# torch.bfloat16 tensors of shape (N, P, Q, K): the library's private channels-last layout.
+# ------------------------------------------------------------------------------------------
+def conv2d_bf16_ok(geom, first=False):
+    """Host-only: does the bf16 path serve this layer (as the first layer / as a body layer)?"""
+    lib = load()
+    return bool((lib.bn_conv2d_first_bf16_ok if first else lib.bn_conv2d_bf16_ok)(*[int(v) for v in geom]))
+
+
+def conv_pack_w_bf16_bytes(w_shape):
+    K, C, R, S = [int(v) for v in w_shape]
+    return int(load().bn_conv_pack_w_bf16_bytes(K, C, R, S))
+
+
+def conv_pack_w_bf16(w, out):
+    """fp32 (K, C, R, S) weights -> bf16 operand layout in ``out`` (a uint8 device buffer of
+    ``conv_pack_w_bf16_bytes`` bytes, 16-byte aligned)."""
+    K, C, R, S = w.shape
+    if out.numel() * out.element_size() < conv_pack_w_bf16_bytes(w.shape):
+        raise HipLibraryError('conv_pack_w_bf16: output buffer too small')
+    _check(load().bn_conv_pack_w_bf16(_ptr(w, 'w'), out.data_ptr(), K, C, R, S, _stream()),
+           'bn_conv_pack_w_bf16')
+    return out
+
+
+def _bf16_out(out, shape, dtype, device, what):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype:
+        raise HipLibraryError('%s: out must be %s of shape %s' % (what, dtype, tuple(shape)))
+    return out
+
+
+def conv2d_first_bf16(x, w, b, geom, act, slope, out=None):
+    """Layer 1 from fp32 or uint8 NCHW frames -> bf16 (N, P, Q, K)."""
+    N, C, H, W, K, R, S, st, pt, pl, P, Q = geom
+    u8 = x.dtype == torch.uint8
+    y = _bf16_out(out, (N, P, Q, K), torch.bfloat16, x.device, 'conv2d_first_bf16')
+    _check(load().bn_conv2d_first_bf16(
+        _ptr(x, 'x', dtype=torch.uint8 if u8 else torch.float32), int(u8), _ptr(w, 'w'),
+        _ptr(b, 'b', allow_none=True), _ptr(y, 'y', dtype=torch.bfloat16), *geom, act, slope, _stream()),
+        'bn_conv2d_first_bf16')
+    return y
+
+
+def conv2d_fwd_bf16(x, wp, b, geom, act, slope, out_f32, out=None):
+    """Body layer: x bf16 (N, H, W, C), wp packed weights -> bf16 (N, P, Q, K), or fp32 (N, K, P, Q)."""
+    N, C, H, W, K, R, S, st, pt, pl, P, Q = geom
+    if tuple(x.shape) != (N, H, W, C):
+        raise HipLibraryError('conv2d_fwd_bf16: expected activations (N,H,W,C)=%s, got %s'
+                              % ((N, H, W, C), tuple(x.shape)))
+    if out_f32:
+        y = _bf16_out(out, (N, K, P, Q), torch.float32, x.device, 'conv2d_fwd_bf16')
+    else:
+        y = _bf16_out(out, (N, P, Q, K), torch.bfloat16, x.device, 'conv2d_fwd_bf16')
+    _check(load().bn_conv2d_fwd_bf16(
+        _ptr(x, 'x', dtype=torch.bfloat16), wp.data_ptr(), _ptr(b, 'b', allow_none=True),
+        _ptr(y, 'y', dtype=y.dtype),
+        int(bool(out_f32)), *geom, act, slope, _stream()), 'bn_conv2d_fwd_bf16')
+    return y
 
 
 def set_force_generic(on):

@@ -166,3 +166,14 @@ size_t bn_s5_down_small_ws_bytes(const BnGeom& g);
 int bn_launch_s5_down_small(const float* big, const float* w, const float* bias, float* out,
                           const float* dact_src, const BnGeom& g, int act, int dact, float slope,
                           void* ws, size_t ws_bytes, hipStream_t st);
+
+// conv_bf16.hip: the inference-only bf16 encoder stack (operands bf16, accumulation fp32).  The twelve integers
+// of the C ABI as they are: (C, H, W) -> (K, P, Q), padding (pt, pl) on top / left, bottom / right implied.
+struct BnBf16Geom { int N, C, H, W, K, R, S, stride, pt, pl, P, Q; };
+bool bn_bf16_first_ok(const BnBf16Geom& g);
+bool bn_bf16_conv_ok(const BnBf16Geom& g);
+int bn_launch_bf16_pack_w(const float* w, void* wp, const BnBf16Geom& g, hipStream_t st);
+int bn_launch_bf16_first(const void* x, int x_is_u8, const float* w, const float* bias, void* y, const BnBf16Geom& g,
+                         int act, float slope, hipStream_t st);
+int bn_launch_bf16_conv(const void* x, const void* wp, const float* bias, void* y, int out_f32, const BnBf16Geom& g,
+                        int act, float slope, hipStream_t st);

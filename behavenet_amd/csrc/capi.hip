@@ -1784,3 +1784,63 @@ extern "C" int bn_u8_to_unit_float(const unsigned char* in, float* out, size_t n
     if (n == 0) return 0;
     return bn_launch_u8_to_unit_float(in, out, n, (hipStream_t)stream);
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// Inference-only bf16 encoder stack (conv_bf16.hip): bf16 operands, fp32 accumulation.  Separate entry points:
+// nothing above dispatches to them, and they dispatch to nothing above.
+static BnBf16Geom bf16_geom(int N, int C, int H, int W, int K, int R, int S, int stride, int pad_t, int pad_l, int P,
+                            int Q) {
+    return BnBf16Geom{N, C, H, W, K, R, S, stride, pad_t, pad_l, P, Q};
+}
+static bool bf16_geom_valid(const BnBf16Geom& g) {
+    if (!(g.N > 0 && g.C > 0 && g.H > 0 && g.W > 0 && g.K > 0 && g.R > 0 && g.S > 0 && g.stride > 0 && g.pt >= 0 &&
+          g.pl >= 0 && g.P > 0 && g.Q > 0))
+        return false;
+    // every output pixel's window starts inside the padded map (bottom / right padding is whatever P, Q imply)
+    return (long)(g.P - 1) * g.stride - g.pt < g.H && (long)(g.Q - 1) * g.stride - g.pl < g.W;
+}
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int bn_conv2d_bf16_ok(int N, int C, int H, int W, int K, int R, int S, int stride, int pad_t, int pad_l,
+                                 int P, int Q) {
+    const BnBf16Geom g = bf16_geom(N, C, H, W, K, R, S, stride, pad_t, pad_l, P, Q);
+    return (bf16_geom_valid(g) && bn_bf16_conv_ok(g)) ? 1 : 0;
+}
+extern "C" int bn_conv2d_first_bf16_ok(int N, int C, int H, int W, int K, int R, int S, int stride, int pad_t,
+                                       int pad_l, int P, int Q) {
+    const BnBf16Geom g = bf16_geom(N, C, H, W, K, R, S, stride, pad_t, pad_l, P, Q);
+    return (bf16_geom_valid(g) && bn_bf16_first_ok(g)) ? 1 : 0;
+}
+
+extern "C" size_t bn_conv_pack_w_bf16_bytes(int K, int C, int R, int S) {
+    if (K <= 0 || C <= 0 || R <= 0 || S <= 0) return 0;
+    return (((size_t)K * C * R * S * 2) + 255) & ~(size_t)255;
+}
+
+extern "C" int bn_conv_pack_w_bf16(const float* w, void* wp, int K, int C, int R, int S, bn_stream_t stream) {
+    if (!w || !wp || K <= 0 || C <= 0 || R <= 0 || S <= 0) return BN_E_BADARG;
+    const BnBf16Geom g = bf16_geom(1, C, 1, 1, K, R, S, 1, 0, 0, 1, 1);
+    return bn_launch_bf16_pack_w(w, wp, g, (hipStream_t)stream);
+}
+
+extern "C" int bn_conv2d_first_bf16(const void* x, int x_is_u8, const float* w, const float* b, void* y, int N, int C,
+                                    int H, int W, int K, int R, int S, int stride, int pad_t, int pad_l, int P, int Q,
+                                    int act, float slope, bn_stream_t stream) {
+    if (!x || !w || !y) return BN_E_BADARG;
+    const BnBf16Geom g = bf16_geom(N, C, H, W, K, R, S, stride, pad_t, pad_l, P, Q);
+    if (!bf16_geom_valid(g)) return BN_E_BADARG;
+    if (!bn_bf16_first_ok(g) || (act != BN_ACT_NONE && act != BN_ACT_LRELU) || !aligned16(y) || !aligned16(w))
+        return BN_E_SHAPE;
+    return bn_launch_bf16_first(x, x_is_u8, w, b, y, g, act, slope, (hipStream_t)stream);
+}
+
+extern "C" int bn_conv2d_fwd_bf16(const void* x, const void* wp, const float* b, void* y, int out_f32, int N, int C,
+                                  int H, int W, int K, int R, int S, int stride, int pad_t, int pad_l, int P, int Q,
+                                  int act, float slope, bn_stream_t stream) {
+    if (!x || !wp || !y) return BN_E_BADARG;
+    const BnBf16Geom g = bf16_geom(N, C, H, W, K, R, S, stride, pad_t, pad_l, P, Q);
+    if (!bf16_geom_valid(g)) return BN_E_BADARG;
+    if (!bn_bf16_conv_ok(g) || (act != BN_ACT_NONE && act != BN_ACT_LRELU) || !aligned16(x) || !aligned16(wp))
+        return BN_E_SHAPE;
+    return bn_launch_bf16_conv(x, wp, b, y, out_f32, g, act, slope, (hipStream_t)stream);
+}

@@ -16,6 +16,7 @@ import torch
 
 from behavenet_amd import _hip
 from behavenet_amd.fitting import distributed as bdist
+from behavenet_amd.hip_functions import ENCODE_DTYPES, encode_precision
 
 __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconstruction']
 
@@ -25,9 +26,25 @@ def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
     return encode_trial_device(model, y, sess, labels_2d, chunk_size).cpu().numpy()
 
 
+def encode_dtype_of(model):
+    """'f32' (default) or 'bf16': ``hparams['hip_encode_dtype']``, else the environment's BN_ENCODE_DTYPE.
+    bf16 runs the conv encoder on bf16 operands with fp32 accumulation (hip_functions.conv_stack_bf16)
+    for a model in eval mode; it costs about 1e-3 of max|z|."""
+    dtype = model.hparams.get('hip_encode_dtype', os.environ.get('BN_ENCODE_DTYPE', 'f32'))
+    if dtype not in ENCODE_DTYPES:
+        raise ValueError("hparams['hip_encode_dtype'] (or BN_ENCODE_DTYPE) must be one of %s, got %r"
+                         % (ENCODE_DTYPES, dtype))
+    return dtype
+
+
 def encode_trial_device(model, y, sess=None, labels_2d=None, chunk_size=200):
     """The same latents as a DEVICE tensor: nothing waits for the host (``export_latents`` keeps
     the trials' latents on the device and fetches them once at the end)."""
+    with encode_precision(encode_dtype_of(model)):
+        return _encode_trial_device(model, y, sess, labels_2d, chunk_size)
+
+
+def _encode_trial_device(model, y, sess, labels_2d, chunk_size):
     mc = model.hparams['model_class']
     if y.dtype == torch.uint8 and (labels_2d is not None or
                                    model.hparams.get('model_type', 'conv') != 'conv'):
@@ -82,7 +99,7 @@ class _GraphedTrialEncoder(object):
         if not self.enabled or labels_2d is not None or not y.is_cuda or not y.is_contiguous():
             self.n_eager += 1
             return encode_trial_device(self.model, y, sess, labels_2d, self.chunk)
-        key = (tuple(y.shape), y.dtype, repr(sess))
+        key = (tuple(y.shape), y.dtype, repr(sess), encode_dtype_of(self.model))
         rec = self._graphs.get(key)
         if rec is None:
             n = self._seen[key] = self._seen.get(key, 0) + 1

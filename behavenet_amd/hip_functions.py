@@ -14,7 +14,10 @@ calls the C ABI (behavenet_amd/_hip.py) for both directions; torch autograd only
 """
 
 import collections.abc
+import contextlib
 import os
+import threading
+import warnings
 
 import torch
 
@@ -636,6 +639,84 @@ def _stack_backward(ctx, dpre, first_param):
 
 def conv_stack(plan, x, params, h1=None):
     return ConvStackFn.apply(plan, x, h1, *params)
+
+
+# -- opt-in bf16 encoder (inference only) -------------------------------------------------------
+ENCODE_DTYPES = ('f32', 'bf16')
+_encode_tls = threading.local()
+
+
+def encode_dtype():
+    """The arithmetic the calling thread asked of the conv encoder: 'f32' (default) or 'bf16'."""
+    return getattr(_encode_tls, 'dtype', 'f32')
+
+
+@contextlib.contextmanager
+def encode_precision(dtype):
+    """Within the block a ``ConvAEEncoder`` in eval mode under ``no_grad`` runs its conv stack on bf16
+    operands with fp32 accumulation (``conv_stack_bf16``) where the stack is served; 'f32' restores the
+    default inside an outer 'bf16' block.  Thread-local; nothing in training enters it."""
+    if dtype not in ENCODE_DTYPES:
+        raise ValueError("encode_precision: dtype must be one of %s, got %r" % (ENCODE_DTYPES, dtype))
+    prev = encode_dtype()
+    _encode_tls.dtype = dtype
+    try:
+        yield
+    finally:
+        _encode_tls.dtype = prev
+
+
+def warn_bf16_unserved(owner, reason):
+    """One warning per model object: bf16 was asked for and the more exact fp32 path runs instead."""
+    if getattr(owner, '_bf16_warned', False):
+        return
+    owner._bf16_warned = True
+    warnings.warn('bf16 encoding was requested but this model runs its fp32 encoder: %s' % reason)
+
+
+def stack_unserved_reason_bf16(plan):
+    """None if ``conv_stack_bf16`` serves the stack, else why not (host only: bn_conv2d_bf16_ok)."""
+    if len(plan) < 2:
+        return 'a stack of one layer has no matrix-core layer'
+    for i, layer in enumerate(plan):
+        if layer.kind != 'conv' or layer.act not in (_hip.ACT_NONE, _hip.ACT_LRELU):
+            return 'layer %d (%r) is not a convolution with a LeakyReLU / no activation' % (i, layer)
+        if not _hip.conv2d_bf16_ok(layer.geom(1), first=(i == 0)):
+            return 'layer %d (%r) is not served by the bf16 kernels' % (i, layer)
+    return None
+
+
+def stack_served_bf16(plan):
+    return stack_unserved_reason_bf16(plan) is None
+
+
+def conv_stack_bf16(plan, x, params):
+    """The conv stack on bf16 operands / fp32 accumulation -> fp32 (N, C, H, W) output of the last layer.
+    Inference only.  The weights are converted at the start of EVERY call (the HIP Adam updates
+    parameters in place without touching torch's version counter, so no cache could notice); the bf16
+    activations between the layers never leave this function."""
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+        raise RuntimeError('conv_stack_bf16 is inference only: call it under torch.no_grad()')
+    if x.shape[1:] != (plan[0].cin, plan[0].hin, plan[0].win):
+        raise ValueError('conv stack expects input (N,%d,%d,%d), got %s' % (
+            plan[0].cin, plan[0].hin, plan[0].win, tuple(x.shape)))
+    reason = stack_unserved_reason_bf16(plan)
+    if reason is not None:
+        raise RuntimeError('conv_stack_bf16: %s' % reason)
+    x = x.contiguous()
+    n = x.shape[0]
+    sizes = [_hip.conv_pack_w_bf16_bytes(params[2 * i].shape) for i in range(1, len(plan))]
+    packed = torch.empty(sum(sizes), dtype=torch.uint8, device=x.device)
+    wps, o = [None], 0
+    for i, sz in zip(range(1, len(plan)), sizes):
+        wps.append(_hip.conv_pack_w_bf16(params[2 * i].detach(), packed[o:o + sz]))
+        o += sz
+    h = _hip.conv2d_first_bf16(x, params[0].detach(), params[1].detach(), plan[0].geom(n), plan[0].act,
+                               LRELU_SLOPE)
+    for i in range(1, len(plan)):
+        h = _hip.conv2d_fwd_bf16(h, wps[i], params[2 * i + 1].detach(), plan[i].geom(n), plan[i].act,
+                                 LRELU_SLOPE, out_f32=(i == len(plan) - 1))
+    return h
 
 
 _frame_scale_cache = {}

@@ -20,7 +20,7 @@ from behavenet_amd.fitting import distributed as bdist
 from behavenet_amd.models.base import BaseModule, BaseModel
 from behavenet_amd.hip_functions import (
     ChunkScalars, ConvLayerPlan, FusedPixelLoss, Readback, activation, backward_chunks, bn_chunks,
-    capturing, finish_loss,
+    capturing, finish_loss, conv_stack_bf16, encode_dtype, stack_unserved_reason_bf16, warn_bf16_unserved,
     chunked_sq_err, conv_stack, conv_stack_bn, conv_stack_sq_err, first_layer_forward,
     join_side_streams, linear, begin_chunks, chunk_stream, max_pool, max_pool_act, max_unpool, conv_pool_act,
     pixel_loss_scales, reserve_device_pools)
@@ -204,6 +204,9 @@ class ConvAEEncoder(BaseModule):
         (see :meth:`_pool_out`)."""
         hp = self.hparams
         self._pool_state = ([], [])
+        if encode_dtype() == 'bf16' and self._bf16_eligible(x):
+            h = conv_stack_bf16(self._plan, x, self._stack_params(dataset))
+            return h.view(h.size(0), -1)
         if any(p is not None for p in self._pool_after):
             return self._features_pooled(x, dataset)
         if hp['ae_batch_norm']:
@@ -213,6 +216,27 @@ class ConvAEEncoder(BaseModule):
             h = conv_stack(self._plan, x, self._stack_params(dataset),
                            h1=self._first_layer_slice(x, dataset))
         return h.view(h.size(0), -1)
+
+    def _bf16_eligible(self, x):
+        """The opt-in bf16 stack (hip_functions.encode_precision) runs only where nothing a training loop
+        calls can reach it: eval mode, no gradients.  A stack it cannot serve runs in fp32, with one warning
+        per model."""
+        if self.training or torch.is_grad_enabled():
+            reason = 'the encoder is in training mode or gradients are enabled'
+        elif any(p is not None for p in self._pool_after):
+            reason = 'max-pooling architectures are not served'
+        elif self.hparams['ae_batch_norm']:
+            reason = 'batch-norm architectures are not served'
+        elif self._plan and self._plan[0].cin != self.hparams['ae_input_dim'][0]:
+            reason = 'extra input channels (conditional_encoder) are not served'
+        elif not x.is_cuda or x.dtype not in (torch.float32, torch.uint8):
+            reason = 'the frames are not fp32 / uint8 device tensors'
+        else:
+            reason = stack_unserved_reason_bf16(self._plan)
+        if reason is None:
+            return True
+        warn_bf16_unserved(self, reason)
+        return False
 
     def _features_pooled(self, x, dataset):
         """conv [-> batch norm] -> max pool (indices kept) -> LeakyReLU, layer by layer
@@ -507,6 +531,8 @@ class LinearAEEncoder(BaseModule):
             out_features=self.n_latents, in_features=int(np.prod(self.input_size)), bias=True)
 
     def forward(self, x, dataset=None):
+        if encode_dtype() == 'bf16':
+            warn_bf16_unserved(self, 'the linear encoder has no conv stack')
         x = x.reshape(x.size(0), -1)
         return linear(x, self.encoder.weight, self.encoder.bias), None, None
 

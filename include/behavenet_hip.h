@@ -408,6 +408,38 @@ int bn_conv2d_fwd_u8(const unsigned char* x, const float* w, const float* b, flo
                      int pad_t, int pad_l, int P, int Q, int act, float slope,
                      void* ws, size_t ws_bytes, bn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Inference-only conv encoder stack on bf16 operands with fp32 accumulation (opt-in; nothing
+ * above dispatches to it).  Between the layers the activations are bf16 in a private layout,
+ * (N, H, W, C) channels last; it never leaves a chain of these calls.  Geometry arguments as
+ * bn_conv2d_fwd.  Fixed-order reductions: the same operands give the same bits.
+ *   bn_conv2d_first_bf16_ok  1 if bn_conv2d_first_bf16 serves the geometry: 1..4 input channels,
+ *                       K a multiple of 16, kernel up to 5x5 (host only, needs no GPU)
+ *   bn_conv2d_bf16_ok   1 if bn_conv2d_fwd_bf16 serves it: C a multiple of 16 (one matrix-core
+ *                       step is 16 channels of one tap), any K, H, W, stride, kernel up to 5x5,
+ *                       x and wp below 2 GiB each
+ *   bn_conv_pack_w_bf16 fp32 weights (K, C, R, S) -> bf16 [K][(r S + s) C + c] in `wp`,
+ *                       bn_conv_pack_w_bf16_bytes(K, C, R, S) bytes (a multiple of 256)
+ *   bn_conv2d_first_bf16 layer 1 from fp32 (x_is_u8 == 0) or uint8 (value / 255 fused) NCHW frames:
+ *                       fp32 arithmetic, bias (nullable) + activation, one rounding to bf16
+ *                       (nearest even), y in the private layout: N P Q K bf16
+ *   bn_conv2d_fwd_bf16  x in the private layout, wp packed; bias + activation in fp32; out_f32 == 0:
+ *                       y in the private layout (one rounding), out_f32 != 0: y fp32 (N, K, P, Q)
+ * BN_E_SHAPE (nothing written) for a geometry that is not served, an activation other than
+ * BN_ACT_NONE / BN_ACT_LRELU or operands that are not 16-byte aligned. */
+int bn_conv2d_first_bf16_ok(int N, int C, int H, int W, int K, int R, int S, int stride,
+                            int pad_t, int pad_l, int P, int Q);
+int bn_conv2d_bf16_ok(int N, int C, int H, int W, int K, int R, int S, int stride,
+                      int pad_t, int pad_l, int P, int Q);
+size_t bn_conv_pack_w_bf16_bytes(int K, int C, int R, int S);
+int bn_conv_pack_w_bf16(const float* w, void* wp, int K, int C, int R, int S, bn_stream_t stream);
+int bn_conv2d_first_bf16(const void* x, int x_is_u8, const float* w, const float* b, void* y,
+                         int N, int C, int H, int W, int K, int R, int S, int stride,
+                         int pad_t, int pad_l, int P, int Q, int act, float slope, bn_stream_t stream);
+int bn_conv2d_fwd_bf16(const void* x, const void* wp, const float* b, void* y, int out_f32,
+                       int N, int C, int H, int W, int K, int R, int S, int stride,
+                       int pad_t, int pad_l, int P, int Q, int act, float slope, bn_stream_t stream);
+
 /* uint8 frames -> float32/255 (replaces the host-side astype(float32)/255 of
  * data_generator.py:251-263 for device-resident uint8 trials) */
 int bn_u8_to_unit_float(const unsigned char* in, float* out, size_t n, bn_stream_t stream);
