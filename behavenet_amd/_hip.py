@@ -118,6 +118,15 @@ SIGNATURES = {
         _c_int, [_c_void_p, _c_int] + [_c_void_p] * 3 + _CONV_GEOM + [_c_int, _c_float, _c_void_p]),
     'bn_conv2d_fwd_bf16': (
         _c_int, [_c_void_p] * 4 + [_c_int] + _CONV_GEOM + [_c_int, _c_float, _c_void_p]),
+    'bn_convT2d_bf16_ok': (_c_int, _CONV_GEOM),
+    'bn_convT2d_last_bf16_ok': (_c_int, _CONV_GEOM),
+    'bn_convT_pack_w_bf16_bytes': (_c_size_t, [_c_int] * 4),
+    'bn_convT_pack_w_bf16': (_c_int, [_c_void_p] * 2 + [_c_int] * 4 + [_c_void_p]),
+    'bn_to_nhwc_bf16': (_c_int, [_c_void_p] * 2 + [_c_int] * 4 + [_c_void_p]),
+    'bn_convT2d_fwd_bf16': (
+        _c_int, [_c_void_p] * 4 + [_c_int] + _CONV_GEOM + [_c_int, _c_float, _c_void_p]),
+    'bn_convT2d_last_bf16': (
+        _c_int, [_c_void_p] * 4 + _CONV_GEOM + [_c_int, _c_float, _c_void_p]),
     'bn_u8_to_unit_float': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
@@ -398,6 +407,79 @@ def conv2d_fwd_bf16(x, wp, b, geom, act, slope, out_f32, out=None):
         _ptr(x, 'x', dtype=torch.bfloat16), wp.data_ptr(), _ptr(b, 'b', allow_none=True),
         _ptr(y, 'y', dtype=y.dtype),
         int(bool(out_f32)), *geom, act, slope, _stream()), 'bn_conv2d_fwd_bf16')
+    return y
+
+
+# ------------------------------------------------------------------------------------------
+# inference-only bf16 decoder stack (csrc/conv_bf16_dec.hip): the same private layout, bf16
+# (N, H, W, C), between its layers; geometry tuples as convT2d_fwd.
+# ------------------------------------------------------------------------------------------
+def convT2d_bf16_ok(geom, last=False):
+    """Host-only: does the bf16 path serve this transposed convolution (as a body layer / as the layer
+    onto the frame)?"""
+    lib = load()
+    return bool((lib.bn_convT2d_last_bf16_ok if last else lib.bn_convT2d_bf16_ok)(*[int(v) for v in geom]))
+
+
+def convT_pack_w_bf16_bytes(w_shape):
+    Ci, Co, R, S = [int(v) for v in w_shape]
+    return int(load().bn_convT_pack_w_bf16_bytes(Ci, Co, R, S))
+
+
+def convT_pack_w_bf16(w, out):
+    """fp32 nn.ConvTranspose2d weights (Ci, Co, R, S) -> bf16 operand layout in ``out`` (a uint8 device
+    buffer of ``convT_pack_w_bf16_bytes`` bytes, 16-byte aligned)."""
+    if w.dim() != 4:
+        raise HipLibraryError('convT_pack_w_bf16: expected weights (Ci, Co, R, S), got %s' % (tuple(w.shape),))
+    Ci, Co, R, S = w.shape
+    if out.numel() * out.element_size() < convT_pack_w_bf16_bytes(w.shape):
+        raise HipLibraryError('convT_pack_w_bf16: output buffer too small')
+    _check(load().bn_convT_pack_w_bf16(_ptr(w, 'w'), out.data_ptr(), Ci, Co, R, S, _stream()),
+           'bn_convT_pack_w_bf16')
+    return out
+
+
+def to_nhwc_bf16(x, out=None):
+    """fp32 (N, C, H, W) -> bf16 (N, H, W, C), one rounding to nearest even."""
+    if x.dim() != 4:
+        raise HipLibraryError('to_nhwc_bf16: expected (N, C, H, W), got %s' % (tuple(x.shape),))
+    N, C, H, W = x.shape
+    y = _bf16_out(out, (N, H, W, C), torch.bfloat16, x.device, 'to_nhwc_bf16')
+    _check(load().bn_to_nhwc_bf16(_ptr(x, 'x'), _ptr(y, 'y', dtype=torch.bfloat16), N, C, H, W, _stream()),
+           'bn_to_nhwc_bf16')
+    return y
+
+
+def convT2d_fwd_bf16(x, wp, b, geom, act, slope, out_f32, out=None):
+    """Body layer: x bf16 (N, Hi, Wi, Ci), wp packed weights -> bf16 (N, Ho, Wo, Co), or fp32 (N, Co, Ho, Wo)."""
+    N, Ci, Hi, Wi, Co, R, S, st, ct, cl, Ho, Wo = geom
+    if tuple(x.shape) != (N, Hi, Wi, Ci):
+        raise HipLibraryError('convT2d_fwd_bf16: expected activations (N,Hi,Wi,Ci)=%s, got %s'
+                              % ((N, Hi, Wi, Ci), tuple(x.shape)))
+    if out_f32:
+        y = _bf16_out(out, (N, Co, Ho, Wo), torch.float32, x.device, 'convT2d_fwd_bf16')
+    else:
+        y = _bf16_out(out, (N, Ho, Wo, Co), torch.bfloat16, x.device, 'convT2d_fwd_bf16')
+    _check(load().bn_convT2d_fwd_bf16(
+        _ptr(x, 'x', dtype=torch.bfloat16), wp.data_ptr(), _ptr(b, 'b', allow_none=True),
+        _ptr(y, 'y', dtype=y.dtype),
+        int(bool(out_f32)), *geom, act, slope, _stream()), 'bn_convT2d_fwd_bf16')
+    return y
+
+
+def convT2d_last_bf16(x, w, b, geom, act, slope, out=None):
+    """The layer onto the frame: x bf16 (N, Hi, Wi, Ci), w fp32 (Ci, Co, R, S) as stored -> fp32 (N, Co, Ho, Wo)."""
+    N, Ci, Hi, Wi, Co, R, S, st, ct, cl, Ho, Wo = geom
+    if tuple(x.shape) != (N, Hi, Wi, Ci):
+        raise HipLibraryError('convT2d_last_bf16: expected activations (N,Hi,Wi,Ci)=%s, got %s'
+                              % ((N, Hi, Wi, Ci), tuple(x.shape)))
+    if tuple(w.shape) != (Ci, Co, R, S):
+        raise HipLibraryError('convT2d_last_bf16: expected weights (Ci,Co,R,S)=%s, got %s'
+                              % ((Ci, Co, R, S), tuple(w.shape)))
+    y = _bf16_out(out, (N, Co, Ho, Wo), torch.float32, x.device, 'convT2d_last_bf16')
+    _check(load().bn_convT2d_last_bf16(
+        _ptr(x, 'x', dtype=torch.bfloat16), _ptr(w, 'w'), _ptr(b, 'b', allow_none=True), _ptr(y, 'y'),
+        *geom, act, slope, _stream()), 'bn_convT2d_last_bf16')
     return y
 
 

@@ -177,3 +177,14 @@ int bn_launch_bf16_first(const void* x, int x_is_u8, const float* w, const float
                          int act, float slope, hipStream_t st);
 int bn_launch_bf16_conv(const void* x, const void* wp, const float* bias, void* y, int out_f32, const BnBf16Geom& g,
                         int act, float slope, hipStream_t st);
+
+// conv_bf16_dec.hip: the inference-only bf16 decoder stack.  BnBf16Geom read as a transposed convolution:
+// (C, H, W) -> (K, P, Q), (pt, pl) the crop on top / left of the full-size map.
+bool bn_bf16_convT_ok(const BnBf16Geom& g);
+bool bn_bf16_lastT_ok(const BnBf16Geom& g);
+int bn_launch_bf16_packT_w(const float* w, void* wp, int Ci, int Co, int R, int S, hipStream_t st);
+int bn_launch_bf16_to_nhwc(const float* x, void* y, int N, int C, int H, int W, hipStream_t st);
+int bn_launch_bf16_convT(const void* x, const void* wp, const float* bias, void* y, int out_f32, const BnBf16Geom& g,
+                         int act, float slope, hipStream_t st);
+int bn_launch_bf16_lastT(const void* x, const float* w, const float* bias, float* y, const BnBf16Geom& g, int act,
+                         float slope, hipStream_t st);

@@ -1844,3 +1844,57 @@ extern "C" int bn_conv2d_fwd_bf16(const void* x, const void* wp, const float* b,
         return BN_E_SHAPE;
     return bn_launch_bf16_conv(x, wp, b, y, out_f32, g, act, slope, (hipStream_t)stream);
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// Inference-only bf16 decoder stack (conv_bf16_dec.hip): the transposed-conv counterpart of the block above, and as
+// separate from everything else.  Geometry as bn_convT2d_fwd: (off_t, off_l) is the crop of the full-size map.
+static bool bf16T_geom_valid(const BnBf16Geom& g) {
+    return g.N > 0 && g.C > 0 && g.H > 0 && g.W > 0 && g.K > 0 && g.R > 0 && g.S > 0 && g.stride > 0 && g.pt >= 0 &&
+           g.pl >= 0 && g.P > 0 && g.Q > 0;
+}
+static bool bf16T_act_ok(int act) { return act == BN_ACT_NONE || act == BN_ACT_LRELU || act == BN_ACT_SIGMOID; }
+
+extern "C" int bn_convT2d_bf16_ok(int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride, int off_t,
+                                  int off_l, int Ho, int Wo) {
+    const BnBf16Geom g = bf16_geom(N, Ci, Hi, Wi, Co, R, S, stride, off_t, off_l, Ho, Wo);
+    return (bf16T_geom_valid(g) && bn_bf16_convT_ok(g)) ? 1 : 0;
+}
+extern "C" int bn_convT2d_last_bf16_ok(int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride, int off_t,
+                                       int off_l, int Ho, int Wo) {
+    const BnBf16Geom g = bf16_geom(N, Ci, Hi, Wi, Co, R, S, stride, off_t, off_l, Ho, Wo);
+    return (bf16T_geom_valid(g) && bn_bf16_lastT_ok(g)) ? 1 : 0;
+}
+
+extern "C" size_t bn_convT_pack_w_bf16_bytes(int Ci, int Co, int R, int S) {
+    return bn_conv_pack_w_bf16_bytes(Co, Ci, R, S);
+}
+
+extern "C" int bn_convT_pack_w_bf16(const float* w, void* wp, int Ci, int Co, int R, int S, bn_stream_t stream) {
+    if (!w || !wp || Ci <= 0 || Co <= 0 || R <= 0 || S <= 0) return BN_E_BADARG;
+    return bn_launch_bf16_packT_w(w, wp, Ci, Co, R, S, (hipStream_t)stream);
+}
+
+extern "C" int bn_to_nhwc_bf16(const float* x, void* y, int N, int C, int H, int W, bn_stream_t stream) {
+    if (!x || !y || N <= 0 || C <= 0 || H <= 0 || W <= 0) return BN_E_BADARG;
+    return bn_launch_bf16_to_nhwc(x, y, N, C, H, W, (hipStream_t)stream);
+}
+
+extern "C" int bn_convT2d_fwd_bf16(const void* x, const void* wp, const float* b, void* y, int out_f32, int N, int Ci,
+                                   int Hi, int Wi, int Co, int R, int S, int stride, int off_t, int off_l, int Ho,
+                                   int Wo, int act, float slope, bn_stream_t stream) {
+    if (!x || !wp || !y) return BN_E_BADARG;
+    const BnBf16Geom g = bf16_geom(N, Ci, Hi, Wi, Co, R, S, stride, off_t, off_l, Ho, Wo);
+    if (!bf16T_geom_valid(g)) return BN_E_BADARG;
+    if (!bn_bf16_convT_ok(g) || !bf16T_act_ok(act) || !aligned16(x) || !aligned16(wp)) return BN_E_SHAPE;
+    return bn_launch_bf16_convT(x, wp, b, y, out_f32, g, act, slope, (hipStream_t)stream);
+}
+
+extern "C" int bn_convT2d_last_bf16(const void* x, const float* w, const float* b, float* y, int N, int Ci, int Hi,
+                                    int Wi, int Co, int R, int S, int stride, int off_t, int off_l, int Ho, int Wo,
+                                    int act, float slope, bn_stream_t stream) {
+    if (!x || !w || !y) return BN_E_BADARG;
+    const BnBf16Geom g = bf16_geom(N, Ci, Hi, Wi, Co, R, S, stride, off_t, off_l, Ho, Wo);
+    if (!bf16T_geom_valid(g)) return BN_E_BADARG;
+    if (!bn_bf16_lastT_ok(g) || !bf16T_act_ok(act) || !aligned16(x)) return BN_E_SHAPE;
+    return bn_launch_bf16_lastT(x, w, b, y, g, act, slope, (hipStream_t)stream);
+}

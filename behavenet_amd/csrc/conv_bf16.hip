@@ -11,18 +11,7 @@
 // Private activation layout: bf16 (N, H, W, C), channels last, so that the 8 input channels a lane feeds to
 // one MFMA are one 16-byte load.  It exists between the layers of one bn_conv2d_*_bf16 chain only.
 // No atomics and no split reductions: two launches on the same operands give the same bits.
-#include "bn_common.h"
-#include "bn_launch.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-
-// round to nearest even, NaN stays NaN
-__device__ __forceinline__ unsigned bn_f32_to_bf16(float f) {
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
+#include "bn_bf16.h"      // the rounding rule, the buffer loads and the tile shape, shared with conv_bf16_dec.hip
 
 // ------------------------------------------------------------------------------------------ weights
 // One workgroup: PACK_CC input channels of one output channel k.  Their C x RS floats are contiguous in the source
@@ -200,21 +189,7 @@ int bn_launch_bf16_first(const void* x, int x_is_u8, const float* w, const float
 // runs on the matrix cores.  C % 16 == 0: one MFMA step is 16 consecutive kk, which then never straddle a tap, and
 // every 16-byte piece (8 channels) is aligned and within one pixel.  Out-of-range pieces (zero padding, the
 // tails of m, k and kk) are staged as zeros and never read from memory (bounds-checked buffer loads).
-#define BFC_BK 64
-#define BFC_LD 72
-#define BFC_BN 64
-
-typedef __amdgpu_buffer_rsrc_t bn_rsrc_t;
-typedef __attribute__((ext_vector_type(4))) unsigned bn_u32x4_t;
-// bounds-checked view of `bytes` bytes at p (raw buffer, no stride: offsets >= bytes read as zero)
-__device__ __forceinline__ bn_rsrc_t bn_make_rsrc(const void* p, size_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ uint4 bn_buf_load16(bn_rsrc_t r, unsigned off) {
-    const bn_u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
+// (BFC_BK / BFC_LD / BFC_BN and the buffer-load helpers: bn_bf16.h)
 bool bn_bf16_conv_ok(const BnBf16Geom& g) {
     // (both operands are addressed with 32-bit byte offsets)
     return g.C % 16 == 0 && g.K >= 1 && g.R <= 5 && g.S <= 5 &&

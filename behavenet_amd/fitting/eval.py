@@ -16,7 +16,7 @@ import torch
 
 from behavenet_amd import _hip
 from behavenet_amd.fitting import distributed as bdist
-from behavenet_amd.hip_functions import ENCODE_DTYPES, encode_precision
+from behavenet_amd.hip_functions import DECODE_DTYPES, ENCODE_DTYPES, decode_precision, encode_precision
 
 __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconstruction']
 
@@ -34,6 +34,18 @@ def encode_dtype_of(model):
     if dtype not in ENCODE_DTYPES:
         raise ValueError("hparams['hip_encode_dtype'] (or BN_ENCODE_DTYPE) must be one of %s, got %r"
                          % (ENCODE_DTYPES, dtype))
+    return dtype
+
+
+def decode_dtype_of(model):
+    """'f32' (default) or 'bf16': ``hparams['hip_decode_dtype']``, else the environment's BN_DECODE_DTYPE.
+    bf16 runs the transposed-conv decoder on bf16 operands with fp32 accumulation
+    (hip_functions.convT_stack_bf16) in ``get_reconstruction``; it costs about one grey level of 255 on a
+    reconstruction."""
+    dtype = model.hparams.get('hip_decode_dtype', os.environ.get('BN_DECODE_DTYPE', 'f32'))
+    if dtype not in DECODE_DTYPES:
+        raise ValueError("hparams['hip_decode_dtype'] (or BN_DECODE_DTYPE) must be one of %s, got %r"
+                         % (DECODE_DTYPES, dtype))
     return dtype
 
 
@@ -267,7 +279,9 @@ def get_reconstruction(model, inputs, dataset=None, return_latents=False, labels
     # (arrays go where the model's parameters are -- the reference sends them to hparams['device'], which a model
     # moved with .to() no longer matches)
     t = inputs if torch.is_tensor(inputs) else torch.Tensor(inputs).to(next(model.parameters()).device)
-    with torch.no_grad():
+    # (the only place that asks for the bf16 decoder; the encoder half of the image branch stays fp32 whatever
+    # hparams['hip_encode_dtype'] says)
+    with torch.no_grad(), decode_precision(decode_dtype_of(model)):
         if t.dim() != 2:
             if cls not in _LATENTS_AT:
                 raise ValueError('Invalid model class %s' % cls)

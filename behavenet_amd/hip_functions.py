@@ -719,6 +719,90 @@ def conv_stack_bf16(plan, x, params):
     return h
 
 
+# -- opt-in bf16 decoder (inference only) -------------------------------------------------------
+DECODE_DTYPES = ('f32', 'bf16')
+_decode_tls = threading.local()
+
+
+def decode_dtype():
+    """The arithmetic the calling thread asked of the conv decoder: 'f32' (default) or 'bf16'."""
+    return getattr(_decode_tls, 'dtype', 'f32')
+
+
+@contextlib.contextmanager
+def decode_precision(dtype):
+    """Within the block a ``ConvAEDecoder`` in eval mode under ``no_grad`` runs its transposed-conv stack on
+    bf16 operands with fp32 accumulation (``convT_stack_bf16``) where the stack is served; 'f32' restores the
+    default inside an outer 'bf16' block.  Thread-local, and a setting of its own: ``encode_precision`` does not
+    switch it on, nor the other way round.  Nothing in training enters it."""
+    if dtype not in DECODE_DTYPES:
+        raise ValueError("decode_precision: dtype must be one of %s, got %r" % (DECODE_DTYPES, dtype))
+    prev = decode_dtype()
+    _decode_tls.dtype = dtype
+    try:
+        yield
+    finally:
+        _decode_tls.dtype = prev
+
+
+def warn_bf16_unserved_dec(owner, reason):
+    """One warning per model object: bf16 decoding was asked for and the more exact fp32 path runs instead."""
+    if getattr(owner, '_bf16_dec_warned', False):
+        return
+    owner._bf16_dec_warned = True
+    warnings.warn('bf16 decoding was requested but this model runs its fp32 decoder: %s' % reason)
+
+
+def stack_unserved_reason_bf16_dec(plan):
+    """None if ``convT_stack_bf16`` serves the stack, else why not (host only: bn_convT2d_*_bf16_ok).  Every
+    layer but the last is a matrix-core body layer; the last is one too if it has more than 4 output channels,
+    else it is the vector-unit layer onto the frame."""
+    if not plan:
+        return 'the decoder has no transposed-conv stack'
+    acts = (_hip.ACT_NONE, _hip.ACT_LRELU, _hip.ACT_SIGMOID)
+    for i, layer in enumerate(plan):
+        if layer.kind != 'convT' or layer.act not in acts:
+            return 'layer %d (%r) is not a transposed convolution with a LeakyReLU / sigmoid / no activation' % (
+                i, layer)
+        last = i == len(plan) - 1 and layer.cout <= 4
+        if not _hip.convT2d_bf16_ok(layer.geom(1), last=last):
+            return 'layer %d (%r) is not served by the bf16 kernels' % (i, layer)
+    return None
+
+
+def convT_stack_bf16(plan, h, params):
+    """The transposed-conv stack on bf16 operands / fp32 accumulation: fp32 (N, C, H, W) input (the dense
+    layer's output) -> fp32 (N, C, H, W) output of the last layer.  Inference only.  The weights are converted
+    at the start of EVERY call, for the reason given in ``conv_stack_bf16``; a last layer of 1..4 channels keeps
+    its fp32 weights.  The bf16 activations between the layers never leave this function."""
+    if torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in params)):
+        raise RuntimeError('convT_stack_bf16 is inference only: call it under torch.no_grad()')
+    if h.shape[1:] != (plan[0].cin, plan[0].hin, plan[0].win):
+        raise ValueError('convT stack expects input (N,%d,%d,%d), got %s' % (
+            plan[0].cin, plan[0].hin, plan[0].win, tuple(h.shape)))
+    reason = stack_unserved_reason_bf16_dec(plan)
+    if reason is not None:
+        raise RuntimeError('convT_stack_bf16: %s' % reason)
+    h = h.contiguous()
+    n = h.shape[0]
+    last = len(plan) - 1
+    body = [i for i in range(len(plan)) if not (i == last and plan[i].cout <= 4)]
+    sizes = [_hip.convT_pack_w_bf16_bytes(params[2 * i].shape) for i in body]
+    packed = torch.empty(sum(sizes), dtype=torch.uint8, device=h.device)
+    wps, o = {}, 0
+    for i, sz in zip(body, sizes):
+        wps[i] = _hip.convT_pack_w_bf16(params[2 * i].detach(), packed[o:o + sz])
+        o += sz
+    a = _hip.to_nhwc_bf16(h)
+    for i, layer in enumerate(plan):
+        w, b = params[2 * i].detach(), params[2 * i + 1].detach()
+        if i in wps:
+            a = _hip.convT2d_fwd_bf16(a, wps[i], b, layer.geom(n), layer.act, LRELU_SLOPE, out_f32=(i == last))
+        else:
+            a = _hip.convT2d_last_bf16(a, w.contiguous(), b, layer.geom(n), layer.act, LRELU_SLOPE)
+    return a
+
+
 _frame_scale_cache = {}
 
 

@@ -21,6 +21,7 @@ from behavenet_amd.models.base import BaseModule, BaseModel
 from behavenet_amd.hip_functions import (
     ChunkScalars, ConvLayerPlan, FusedPixelLoss, Readback, activation, backward_chunks, bn_chunks,
     capturing, finish_loss, conv_stack_bf16, encode_dtype, stack_unserved_reason_bf16, warn_bf16_unserved,
+    convT_stack_bf16, decode_dtype, decode_precision, stack_unserved_reason_bf16_dec, warn_bf16_unserved_dec,
     chunked_sq_err, conv_stack, conv_stack_bn, conv_stack_sq_err, first_layer_forward,
     join_side_streams, linear, begin_chunks, chunk_stream, max_pool, max_pool_act, max_unpool, conv_pool_act,
     pixel_loss_scales, reserve_device_pools)
@@ -480,9 +481,12 @@ class ConvAEDecoder(BaseModule):
                     self._plan, h, params, target, pixel_loss.get('mask'), bounds, scales,
                     pixel_loss.get('want_xhat', False))
                 return FusedPixelLoss(x_hat, terms, kind, bounds)
-            x_hat = self.forward(x, pool_idx, target_output_size, dataset=dataset)
+            with decode_precision('f32'):          # a loss is fp32 arithmetic whoever calls it
+                x_hat = self.forward(x, pool_idx, target_output_size, dataset=dataset)
             return FusedPixelLoss(x_hat, chunked_sq_err(
                 x_hat, target, pixel_loss.get('mask'), bounds, scales), kind, bounds)
+        if decode_dtype() == 'bf16' and self._bf16_eligible(h):
+            return convT_stack_bf16(self._plan, h, params)
         if any(self._unpool_before):
             # max-pooling architectures: MaxUnpool2d with the encoder's indices (last pooled first)
             # in front of its transposed convolution, layer by layer (ref aes.py:460-476)
@@ -510,6 +514,29 @@ class ConvAEDecoder(BaseModule):
                            _hip.ACT_SIGMOID)
             h = h.view(-1, hp['ae_input_dim'][0], hp['ae_input_dim'][1], hp['ae_input_dim'][2])
         return h
+
+
+    def _bf16_eligible(self, h):
+        """The opt-in bf16 stack (hip_functions.decode_precision) runs only where nothing a training loop calls
+        can reach it: eval mode, no gradients (and never with a fused pixel loss: forward() asks before it gets
+        here).  A decoder it cannot serve runs in fp32, with one warning per model."""
+        hp = self.hparams
+        if self.training or torch.is_grad_enabled():
+            reason = 'the decoder is in training mode or gradients are enabled'
+        elif any(self._unpool_before):
+            reason = 'max-pooling architectures (unpooling) are not served'
+        elif hp['ae_batch_norm']:
+            reason = 'batch-norm architectures are not served'
+        elif hp['ae_decoding_last_FF_layer']:
+            reason = 'a dense last layer (ae_decoding_last_FF_layer) is not served'
+        elif not h.is_cuda or h.dtype != torch.float32:
+            reason = 'the latents are not fp32 device tensors'
+        else:
+            reason = stack_unserved_reason_bf16_dec(self._plan)
+        if reason is None:
+            return True
+        warn_bf16_unserved_dec(self, reason)
+        return False
 
 
 class LinearAEEncoder(BaseModule):
@@ -565,6 +592,8 @@ class LinearAEDecoder(BaseModule):
                 torch.zeros(int(np.prod(self.output_size))), requires_grad=True)
 
     def forward(self, x, dataset=None):
+        if decode_dtype() == 'bf16':
+            warn_bf16_unserved_dec(self, 'the linear decoder has no transposed-conv stack')
         if self.encoder is None:
             x = linear(x, self.decoder.weight, self.decoder.bias)
         else:

@@ -440,6 +440,44 @@ int bn_conv2d_fwd_bf16(const void* x, const void* wp, const float* b, void* y, i
                        int N, int C, int H, int W, int K, int R, int S, int stride,
                        int pad_t, int pad_l, int P, int Q, int act, float slope, bn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Inference-only transposed-conv decoder stack on bf16 operands with fp32 accumulation (opt-in;
+ * nothing above dispatches to it).  The same private layout between the layers as the encoder
+ * stack: bf16 (N, H, W, C) channels last.  Geometry arguments as bn_convT2d_fwd: (off_t, off_l)
+ * is the crop, output pixel o is pixel o + off of the full-size map; output pixels past the full
+ * size (output_padding) receive the bias alone.  Gather formulation, fixed-order reductions, no
+ * atomics: the same operands give the same bits.
+ *   bn_convT2d_bf16_ok  1 if bn_convT2d_fwd_bf16 serves the geometry: Ci a multiple of 16, any Co,
+ *                       Hi, Wi, Ho, Wo, kernel up to 5x5, stride up to 5, x and wp below 2 GiB each
+ *                       (host only, needs no GPU)
+ *   bn_convT2d_last_bf16_ok  1 if bn_convT2d_last_bf16 serves it: Co 1..4, Ci a multiple of 16,
+ *                       kernel up to 5x5, stride up to 5, R S Co Ci floats within 48 KiB (host only)
+ *   bn_convT_pack_w_bf16  fp32 nn.ConvTranspose2d weights (Ci, Co, R, S) -> bf16
+ *                       [co][(r S + s) Ci + ci] in `wp`, bn_convT_pack_w_bf16_bytes(Ci, Co, R, S)
+ *                       bytes (a multiple of 256), round to nearest even
+ *   bn_to_nhwc_bf16     the stack's input: fp32 (N, C, H, W) -> bf16 (N, H, W, C), one rounding
+ *   bn_convT2d_fwd_bf16 body layer: x in the private layout, wp packed; bias (nullable) + activation
+ *                       in fp32; out_f32 == 0: y in the private layout (one rounding), out_f32 != 0:
+ *                       y fp32 (N, Co, Ho, Wo)
+ *   bn_convT2d_last_bf16  the layer onto the frame: x in the private layout, w fp32 (Ci, Co, R, S)
+ *                       as stored (not rounded), fp32 arithmetic, bias (nullable) + activation,
+ *                       y fp32 (N, Co, Ho, Wo)
+ * Activations: BN_ACT_NONE / BN_ACT_LRELU / BN_ACT_SIGMOID.  BN_E_SHAPE (nothing written) for a
+ * geometry that is not served, another activation or operands that are not 16-byte aligned. */
+int bn_convT2d_bf16_ok(int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
+                       int off_t, int off_l, int Ho, int Wo);
+int bn_convT2d_last_bf16_ok(int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
+                            int off_t, int off_l, int Ho, int Wo);
+size_t bn_convT_pack_w_bf16_bytes(int Ci, int Co, int R, int S);
+int bn_convT_pack_w_bf16(const float* w, void* wp, int Ci, int Co, int R, int S, bn_stream_t stream);
+int bn_to_nhwc_bf16(const float* x, void* y, int N, int C, int H, int W, bn_stream_t stream);
+int bn_convT2d_fwd_bf16(const void* x, const void* wp, const float* b, void* y, int out_f32,
+                        int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
+                        int off_t, int off_l, int Ho, int Wo, int act, float slope, bn_stream_t stream);
+int bn_convT2d_last_bf16(const void* x, const float* w, const float* b, float* y,
+                         int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
+                         int off_t, int off_l, int Ho, int Wo, int act, float slope, bn_stream_t stream);
+
 /* uint8 frames -> float32/255 (replaces the host-side astype(float32)/255 of
  * data_generator.py:251-263 for device-resident uint8 trials) */
 int bn_u8_to_unit_float(const unsigned char* in, float* out, size_t n, bn_stream_t stream);
