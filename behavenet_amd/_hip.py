@@ -127,6 +127,14 @@ SIGNATURES = {
         _c_int, [_c_void_p] * 4 + [_c_int] + _CONV_GEOM + [_c_int, _c_float, _c_void_p]),
     'bn_convT2d_last_bf16': (
         _c_int, [_c_void_p] * 4 + _CONV_GEOM + [_c_int, _c_float, _c_void_p]),
+    'bn_convT2d_last_bf16_sqerr_ws_bytes': (_c_size_t, _CONV_GEOM),
+    'bn_convT2d_last_bf16_sqerr': (
+        _c_int, [_c_void_p] * 4 + [_c_int] + [_c_void_p] * 2 + _CONV_GEOM +
+        [_c_int, _c_float, _c_float, _c_void_p, _c_size_t, _c_void_p]),
+    'bn_frame_sq_err_ws_bytes': (_c_size_t, [_c_int, _c_size_t]),
+    'bn_frame_sq_err': (
+        _c_int, [_c_void_p] * 2 + [_c_int] + [_c_void_p] * 2 + [_c_int, _c_size_t, _c_float, _c_void_p, _c_size_t,
+                                                                 _c_void_p]),
     'bn_u8_to_unit_float': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
@@ -481,6 +489,62 @@ def convT2d_last_bf16(x, w, b, geom, act, slope, out=None):
         _ptr(x, 'x', dtype=torch.bfloat16), _ptr(w, 'w'), _ptr(b, 'b', allow_none=True), _ptr(y, 'y'),
         *geom, act, slope, _stream()), 'bn_convT2d_last_bf16')
     return y
+
+
+def _err_operands(what, target, mask, out, n, device):
+    """(target pointer, is_u8, mask pointer, out): the target / mask / out checks the two frame-error calls share."""
+    if target.dtype not in (torch.float32, torch.uint8) or not target.is_contiguous():
+        raise HipLibraryError('%s: the target must be a contiguous float32 or uint8 tensor' % what)
+    if mask is not None and tuple(mask.shape) != tuple(target.shape):
+        raise HipLibraryError('%s: the mask must have the target\'s shape %s, got %s'
+                              % (what, tuple(target.shape), tuple(mask.shape)))
+    if out is None:
+        out = torch.empty((n,), dtype=torch.float32, device=device)
+    elif tuple(out.shape) != (n,) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise HipLibraryError('%s: out must be a contiguous float32 tensor of shape (%d,)' % (what, n))
+    return (_ptr(target, 'target', dtype=target.dtype), int(target.dtype == torch.uint8),
+            _ptr(mask, 'mask', allow_none=True), out)
+
+
+def frame_sq_err(xhat, target, mask=None, scale=1.0, out=None):
+    """out[n] = scale * sum over the frame of (xhat[n] - target[n])^2 * mask[n] -> fp32 (N,).  xhat fp32 (N, ...);
+    target fp32 or uint8 (value / 255) of xhat's shape; mask fp32 of that shape or None.  A frame's bits do not
+    depend on N or on its position (csrc/frame_err.hip)."""
+    if xhat.dim() < 2 or tuple(target.shape) != tuple(xhat.shape):
+        raise HipLibraryError('frame_sq_err: xhat %s and target %s must share a shape (N, ...)'
+                              % (tuple(xhat.shape), tuple(target.shape)))
+    n = int(xhat.shape[0])
+    d = xhat[0].numel()
+    tp, is_u8, mp, out = _err_operands('frame_sq_err', target, mask, out, n, xhat.device)
+    lib = load()
+    nbytes = lib.bn_frame_sq_err_ws_bytes(n, d)
+    ws = _arena(xhat.device, nbytes) if nbytes else None
+    _check(lib.bn_frame_sq_err(_ptr(xhat, 'xhat'), tp, is_u8, mp, _ptr(out, 'out'), n, d, float(scale), ws, nbytes,
+                               _stream()), 'bn_frame_sq_err')
+    return out
+
+
+def convT2d_last_bf16_sqerr(x, w, b, target, mask, geom, act, slope, scale=1.0, out=None):
+    """The layer onto the frame (``convT2d_last_bf16``) scored instead of stored: out[n] = scale * sum over the
+    frame of (x_hat[n] - target[n])^2 * mask[n] -> fp32 (N,); x_hat is never written."""
+    N, Ci, Hi, Wi, Co, R, S, st, ct, cl, Ho, Wo = geom
+    if tuple(x.shape) != (N, Hi, Wi, Ci):
+        raise HipLibraryError('convT2d_last_bf16_sqerr: expected activations (N,Hi,Wi,Ci)=%s, got %s'
+                              % ((N, Hi, Wi, Ci), tuple(x.shape)))
+    if tuple(w.shape) != (Ci, Co, R, S):
+        raise HipLibraryError('convT2d_last_bf16_sqerr: expected weights (Ci,Co,R,S)=%s, got %s'
+                              % ((Ci, Co, R, S), tuple(w.shape)))
+    if tuple(target.shape) != (N, Co, Ho, Wo):
+        raise HipLibraryError('convT2d_last_bf16_sqerr: expected a target (N,Co,Ho,Wo)=%s, got %s'
+                              % ((N, Co, Ho, Wo), tuple(target.shape)))
+    tp, is_u8, mp, out = _err_operands('convT2d_last_bf16_sqerr', target, mask, out, N, x.device)
+    lib = load()
+    nbytes = lib.bn_convT2d_last_bf16_sqerr_ws_bytes(*geom)
+    ws = _arena(x.device, nbytes) if nbytes else None
+    _check(lib.bn_convT2d_last_bf16_sqerr(
+        _ptr(x, 'x', dtype=torch.bfloat16), _ptr(w, 'w'), _ptr(b, 'b', allow_none=True), tp, is_u8, mp,
+        _ptr(out, 'out'), *geom, act, slope, float(scale), ws, nbytes, _stream()), 'bn_convT2d_last_bf16_sqerr')
+    return out
 
 
 def set_force_generic(on):

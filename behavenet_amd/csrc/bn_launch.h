@@ -62,6 +62,14 @@ int bn_launch_adam(float* p, const float* g, float* m, float* v, float* vmax, si
                    float b1, float b2, float eps, float wd, int step, hipStream_t st);
 int bn_launch_u8_to_unit_float(const unsigned char* in, float* out, size_t n, hipStream_t st);
 
+// frame_err.hip: per-frame squared error, a frame's summation order a function of D alone
+bool bn_frame_sq_err_ok(int N, size_t D);
+size_t bn_frame_sq_err_ws_bytes_impl(int N, size_t D);
+int bn_launch_frame_sq_err(const float* xhat, const void* target, int target_is_u8, const float* mask, float* out,
+                           int N, size_t D, float scale, void* ws, hipStream_t st);
+// out[n] = scale * (part[n][0] + .. + part[n][P - 1]), left to right
+int bn_launch_frame_err_finish(const float* part, float* out, int N, unsigned P, float scale, hipStream_t st);
+
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);
 int bn_launch_bn_stats(const float* x, float* mean, float* var, int N, int C, int HW, void* ws,
@@ -188,3 +196,9 @@ int bn_launch_bf16_convT(const void* x, const void* wp, const float* bias, void*
                          int act, float slope, hipStream_t st);
 int bn_launch_bf16_lastT(const void* x, const float* w, const float* bias, float* y, const BnBf16Geom& g, int act,
                          float slope, hipStream_t st);
+// the layer onto the frame fused with the per-frame squared error (x_hat is not written); serves what bn_bf16_lastT_ok
+// serves; `ws`: bn_bf16_lastT_sqerr_ws_bytes(g) bytes
+size_t bn_bf16_lastT_sqerr_ws_bytes(const BnBf16Geom& g);
+int bn_launch_bf16_lastT_sqerr(const void* x, const float* w, const float* bias, const void* target, int target_is_u8,
+                               const float* mask, float* out, const BnBf16Geom& g, int act, float slope, float scale,
+                               void* ws, hipStream_t st);

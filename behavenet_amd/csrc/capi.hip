@@ -1898,3 +1898,42 @@ extern "C" int bn_convT2d_last_bf16(const void* x, const float* w, const float* 
     if (!bn_bf16_lastT_ok(g) || !bf16T_act_ok(act) || !aligned16(x)) return BN_E_SHAPE;
     return bn_launch_bf16_lastT(x, w, b, y, g, act, slope, (hipStream_t)stream);
 }
+
+extern "C" size_t bn_convT2d_last_bf16_sqerr_ws_bytes(int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
+                                                      int off_t, int off_l, int Ho, int Wo) {
+    const BnBf16Geom g = bf16_geom(N, Ci, Hi, Wi, Co, R, S, stride, off_t, off_l, Ho, Wo);
+    if (!bf16T_geom_valid(g)) return 0;
+    return bn_bf16_lastT_sqerr_ws_bytes(g);          // the SAME plan the launch cuts a frame up by
+}
+
+extern "C" int bn_convT2d_last_bf16_sqerr(const void* x, const float* w, const float* b, const void* target,
+                                          int target_is_u8, const float* mask, float* out, int N, int Ci, int Hi,
+                                          int Wi, int Co, int R, int S, int stride, int off_t, int off_l, int Ho,
+                                          int Wo, int act, float slope, float scale, void* ws, size_t ws_bytes,
+                                          bn_stream_t stream) {
+    if (!x || !w || !target || !out) return BN_E_BADARG;
+    const BnBf16Geom g = bf16_geom(N, Ci, Hi, Wi, Co, R, S, stride, off_t, off_l, Ho, Wo);
+    if (!bf16T_geom_valid(g)) return BN_E_BADARG;
+    if (!bn_bf16_lastT_ok(g) || !bf16T_act_ok(act) || !aligned16(x)) return BN_E_SHAPE;
+    const size_t need = bn_bf16_lastT_sqerr_ws_bytes(g);
+    if (need && (!ws || ws_bytes < need)) return BN_E_WORKSPACE;
+    return bn_launch_bf16_lastT_sqerr(x, w, b, target, target_is_u8, mask, out, g, act, slope, scale, ws,
+                                      (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Per-frame squared error of a reconstruction (frame_err.hip): out[n] = scale sum_i (xhat - target)^2 mask.
+extern "C" size_t bn_frame_sq_err_ws_bytes(int N, size_t D) { return bn_frame_sq_err_ws_bytes_impl(N, D); }
+
+extern "C" int bn_frame_sq_err(const float* xhat, const void* target, int target_is_u8, const float* mask, float* out,
+                               int N, size_t D, float scale, void* ws, size_t ws_bytes, bn_stream_t stream) {
+    if (!xhat || !target || !out || N <= 0 || D == 0) return BN_E_BADARG;
+    if (!bn_frame_sq_err_ok(N, D)) return BN_E_SHAPE;
+    // (fp32 operands that are not even 4-byte aligned cannot be read at all)
+    if (((uintptr_t)xhat & 3) || ((uintptr_t)out & 3) || (mask && ((uintptr_t)mask & 3)) ||
+        (!target_is_u8 && ((uintptr_t)target & 3)))
+        return BN_E_SHAPE;
+    const size_t need = bn_frame_sq_err_ws_bytes_impl(N, D);
+    if (need && (!ws || ws_bytes < need)) return BN_E_WORKSPACE;
+    return bn_launch_frame_sq_err(xhat, target, target_is_u8, mask, out, N, D, scale, ws, (hipStream_t)stream);
+}

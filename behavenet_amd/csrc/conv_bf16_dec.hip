@@ -308,11 +308,9 @@ bool bn_bf16_lastT_ok(const BnBf16Geom& g) {
            (size_t)g.N * g.H * g.W * g.C * 2 < ((size_t)1 << 31) && (size_t)g.N * g.P * g.Q < ((size_t)1 << 31);
 }
 
+// The whole weight tensor into LDS as [(r * S + s)][co][ci] floats (every thread of the workgroup; a barrier follows)
 template <int CO>
-__global__ __launch_bounds__(256) void k_bf16_lastT(const unsigned short* __restrict__ x, const float* __restrict__ w,
-                                                    const float* __restrict__ bias, float* __restrict__ y,
-                                                    BnBf16Geom g, int act, float slope, int nchunk, unsigned nitems) {
-    extern __shared__ __attribute__((aligned(16))) float s_w[];          // [(r * S + s)][co][ci]
+__device__ __forceinline__ void bfl_stage_weights(const float* __restrict__ w, float* s_w, const BnBf16Geom& g) {
     const int RS = g.R * g.S;
     for (int i = threadIdx.x; i < g.C * CO * RS; i += 256) {
         const int ci = i / (CO * RS), e = i - ci * (CO * RS);          // source order: (Cin, Cout, R, S)
@@ -320,6 +318,88 @@ __global__ __launch_bounds__(256) void k_bf16_lastT(const unsigned short* __rest
         s_w[(tap * CO + co) * g.C + ci] = w[i];
     }
     __syncthreads();
+}
+
+// One work item of k_bf16_lastT -- and of k_bf16_lastT_sqerr, which scores the SAME pre-activations: the BFL_PX x 64
+// pixels number `chunk` of phase `ph` of frame `n`.  acc[t][co] is the bias plus the taps in the order (ty, tx, ci);
+// pixel t of this lane is (jy[t], jx[t]) of the phase where ok[t].  False (nothing set) for a chunk past the phase.
+template <int CO>
+__device__ __forceinline__ bool bfl_item(const bn_rsrc_t& xr, const float* s_w, const float (&bv)[CO],
+                                         const BnBf16Geom& g, int n, int ph, int chunk, int lane, BfTAxis& ay,
+                                         BfTAxis& ax, int (&jy)[BFL_PX], int (&jx)[BFL_PX], bool (&ok)[BFL_PX],
+                                         float (&acc)[BFL_PX][CO]) {
+    const int phy = ph / g.stride, phx = ph - phy * g.stride;
+    ay = bft_axis(phy, g.stride, g.pt, g.P, g.R);
+    ax = bft_axis(phx, g.stride, g.pl, g.Q, g.S);
+    const int JJ = ay.cnt * ax.cnt;
+    if (chunk * (64 * BFL_PX) >= JJ) return false;
+#pragma unroll
+    for (int t = 0; t < BFL_PX; ++t) {
+        const int j = chunk * (64 * BFL_PX) + t * 64 + lane;
+        ok[t] = j < JJ;
+        const int jj = ok[t] ? j : 0;
+        jy[t] = jj / ax.cnt;
+        jx[t] = jj - jy[t] * ax.cnt;
+#pragma unroll
+        for (int co = 0; co < CO; ++co) acc[t][co] = bv[co];
+    }
+    const size_t nbase = (size_t)n * g.H * g.W * g.C;
+    for (int ty = 0; ty < ay.ntap; ++ty) {
+        for (int tx = 0; tx < ax.ntap; ++tx) {
+            const float* wt = s_w + (size_t)((phy + ty * g.stride) * g.S + phx + tx * g.stride) * CO * g.C;
+            unsigned off[BFL_PX];
+            bool in[BFL_PX];
+#pragma unroll
+            for (int t = 0; t < BFL_PX; ++t) {
+                const int ih = ay.b0 + jy[t] - ty, iw = ax.b0 + jx[t] - tx;
+                in[t] = ok[t] && ih >= 0 && ih < g.H && iw >= 0 && iw < g.W;
+                off[t] = (unsigned)((nbase + ((size_t)ih * g.W + iw) * g.C) * 2);
+            }
+            for (int c8 = 0; c8 < g.C; c8 += 8) {
+                float xf[BFL_PX][8];
+#pragma unroll
+                for (int t = 0; t < BFL_PX; ++t) {
+                    // (selected per piece: an out-of-range marker plus a channel offset would wrap into range)
+                    const uint4 v = bn_buf_load16(xr, in[t] ? off[t] + (unsigned)c8 * 2 : 0xffffffffu);
+                    xf[t][0] = __uint_as_float(v.x << 16);
+                    xf[t][1] = __uint_as_float(v.x & 0xffff0000u);
+                    xf[t][2] = __uint_as_float(v.y << 16);
+                    xf[t][3] = __uint_as_float(v.y & 0xffff0000u);
+                    xf[t][4] = __uint_as_float(v.z << 16);
+                    xf[t][5] = __uint_as_float(v.z & 0xffff0000u);
+                    xf[t][6] = __uint_as_float(v.w << 16);
+                    xf[t][7] = __uint_as_float(v.w & 0xffff0000u);
+                }
+#pragma unroll
+                for (int co = 0; co < CO; ++co) {
+                    const float4 w0 = *(const float4*)(wt + co * g.C + c8);
+                    const float4 w1 = *(const float4*)(wt + co * g.C + c8 + 4);
+#pragma unroll
+                    for (int t = 0; t < BFL_PX; ++t) {
+                        float a = acc[t][co];
+                        a = fmaf(xf[t][0], w0.x, a);
+                        a = fmaf(xf[t][1], w0.y, a);
+                        a = fmaf(xf[t][2], w0.z, a);
+                        a = fmaf(xf[t][3], w0.w, a);
+                        a = fmaf(xf[t][4], w1.x, a);
+                        a = fmaf(xf[t][5], w1.y, a);
+                        a = fmaf(xf[t][6], w1.z, a);
+                        a = fmaf(xf[t][7], w1.w, a);
+                        acc[t][co] = a;
+                    }
+                }
+            }
+        }
+    }
+    return true;
+}
+
+template <int CO>
+__global__ __launch_bounds__(256) void k_bf16_lastT(const unsigned short* __restrict__ x, const float* __restrict__ w,
+                                                    const float* __restrict__ bias, float* __restrict__ y,
+                                                    BnBf16Geom g, int act, float slope, int nchunk, unsigned nitems) {
+    extern __shared__ __attribute__((aligned(16))) float s_w[];          // [(r * S + s)][co][ci]
+    bfl_stage_weights<CO>(w, s_w, g);
     float bv[CO];
 #pragma unroll
     for (int co = 0; co < CO; ++co) bv[co] = bias ? bias[co] : 0.f;
@@ -332,71 +412,11 @@ __global__ __launch_bounds__(256) void k_bf16_lastT(const unsigned short* __rest
         const int chunk = (int)(item % nchunk);
         const unsigned rest = item / nchunk;
         const int ph = (int)(rest % nph), n = (int)(rest / nph);
-        const int phy = ph / g.stride, phx = ph - phy * g.stride;
-        const BfTAxis ay = bft_axis(phy, g.stride, g.pt, g.P, g.R), ax = bft_axis(phx, g.stride, g.pl, g.Q, g.S);
-        const int JJ = ay.cnt * ax.cnt;
-        if (chunk * (64 * BFL_PX) >= JJ) continue;
+        BfTAxis ay, ax;
         int jy[BFL_PX], jx[BFL_PX];
         bool ok[BFL_PX];
         float acc[BFL_PX][CO];
-#pragma unroll
-        for (int t = 0; t < BFL_PX; ++t) {
-            const int j = chunk * (64 * BFL_PX) + t * 64 + lane;
-            ok[t] = j < JJ;
-            const int jj = ok[t] ? j : 0;
-            jy[t] = jj / ax.cnt;
-            jx[t] = jj - jy[t] * ax.cnt;
-#pragma unroll
-            for (int co = 0; co < CO; ++co) acc[t][co] = bv[co];
-        }
-        const size_t nbase = (size_t)n * g.H * g.W * g.C;
-        for (int ty = 0; ty < ay.ntap; ++ty) {
-            for (int tx = 0; tx < ax.ntap; ++tx) {
-                const float* wt = s_w + (size_t)((phy + ty * g.stride) * g.S + phx + tx * g.stride) * CO * g.C;
-                unsigned off[BFL_PX];
-                bool in[BFL_PX];
-#pragma unroll
-                for (int t = 0; t < BFL_PX; ++t) {
-                    const int ih = ay.b0 + jy[t] - ty, iw = ax.b0 + jx[t] - tx;
-                    in[t] = ok[t] && ih >= 0 && ih < g.H && iw >= 0 && iw < g.W;
-                    off[t] = (unsigned)((nbase + ((size_t)ih * g.W + iw) * g.C) * 2);
-                }
-                for (int c8 = 0; c8 < g.C; c8 += 8) {
-                    float xf[BFL_PX][8];
-#pragma unroll
-                    for (int t = 0; t < BFL_PX; ++t) {
-                        // (selected per piece: an out-of-range marker plus a channel offset would wrap into range)
-                        const uint4 v = bn_buf_load16(xr, in[t] ? off[t] + (unsigned)c8 * 2 : 0xffffffffu);
-                        xf[t][0] = __uint_as_float(v.x << 16);
-                        xf[t][1] = __uint_as_float(v.x & 0xffff0000u);
-                        xf[t][2] = __uint_as_float(v.y << 16);
-                        xf[t][3] = __uint_as_float(v.y & 0xffff0000u);
-                        xf[t][4] = __uint_as_float(v.z << 16);
-                        xf[t][5] = __uint_as_float(v.z & 0xffff0000u);
-                        xf[t][6] = __uint_as_float(v.w << 16);
-                        xf[t][7] = __uint_as_float(v.w & 0xffff0000u);
-                    }
-#pragma unroll
-                    for (int co = 0; co < CO; ++co) {
-                        const float4 w0 = *(const float4*)(wt + co * g.C + c8);
-                        const float4 w1 = *(const float4*)(wt + co * g.C + c8 + 4);
-#pragma unroll
-                        for (int t = 0; t < BFL_PX; ++t) {
-                            float a = acc[t][co];
-                            a = fmaf(xf[t][0], w0.x, a);
-                            a = fmaf(xf[t][1], w0.y, a);
-                            a = fmaf(xf[t][2], w0.z, a);
-                            a = fmaf(xf[t][3], w0.w, a);
-                            a = fmaf(xf[t][4], w1.x, a);
-                            a = fmaf(xf[t][5], w1.y, a);
-                            a = fmaf(xf[t][6], w1.z, a);
-                            a = fmaf(xf[t][7], w1.w, a);
-                            acc[t][co] = a;
-                        }
-                    }
-                }
-            }
-        }
+        if (!bfl_item<CO>(xr, s_w, bv, g, n, ph, chunk, lane, ay, ax, jy, jx, ok, acc)) continue;
 #pragma unroll
         for (int t = 0; t < BFL_PX; ++t) {
             if (!ok[t]) continue;
@@ -419,19 +439,68 @@ __global__ __launch_bounds__(256) void k_bf16_lastT(const unsigned short* __rest
 // block (padding the taps to 6x6 to drop the branches made them 288 and took 1.55 x as long): several blocks per lane
 // for every weight read is the next thing to measure.
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
+// The 2 x 2 output block q = (qy, qx) of frame n -- shared by k_bf16_lastT_s2 and k_bf16_lastT_s2_sqerr, which scores
+// the SAME pre-activations: acc[py][px][co] holds the (even ci, odd ci) halves of output pixel 2 q + p - crop.
+template <int CO>
+__device__ __forceinline__ void bfl_s2_block(const bn_rsrc_t& xr, const float* s_w, const float (&bv)[CO],
+                                             const BnBf16Geom& g, int nty, int ntx, int n, int qy, int qx,
+                                             f32x2_t (&acc)[2][2][CO]) {
+    // (even ci, odd ci) halves of every sum: the two are one packed FMA (v_pk_fma_f32), added at the end
+#pragma unroll
+    for (int py = 0; py < 2; ++py)
+#pragma unroll
+        for (int px = 0; px < 2; ++px)
+#pragma unroll
+            for (int co = 0; co < CO; ++co) acc[py][px][co] = f32x2_t{bv[co], 0.f};
+    const size_t nbase = (size_t)n * g.H * g.W * g.C;
+    for (int ty = 0; ty < nty; ++ty) {
+        for (int tx = 0; tx < ntx; ++tx) {
+            const int ih = qy - ty, iw = qx - tx;
+            const bool in = ih >= 0 && ih < g.H && iw >= 0 && iw < g.W;
+            const unsigned off = (unsigned)((nbase + ((size_t)ih * g.W + iw) * g.C) * 2);
+            for (int c16 = 0; c16 < g.C; c16 += 16) {
+                // (selected per piece: an out-of-range marker plus a channel offset would wrap into range)
+                const uint4 v0 = bn_buf_load16(xr, in ? off + (unsigned)c16 * 2 : 0xffffffffu);
+                const uint4 v1 = bn_buf_load16(xr, in ? off + (unsigned)c16 * 2 + 16 : 0xffffffffu);
+                f32x2_t xf[8];
+                const unsigned u[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    xf[e] = f32x2_t{__uint_as_float(u[e] << 16), __uint_as_float(u[e] & 0xffff0000u)};
+#pragma unroll
+                for (int py = 0; py < 2; ++py) {
+                    const int r = py + 2 * ty;
+                    if (r >= g.R) continue;
+#pragma unroll
+                    for (int px = 0; px < 2; ++px) {
+                        const int sx = px + 2 * tx;
+                        if (sx >= g.S) continue;
+                        const float* wt = s_w + (size_t)(r * g.S + sx) * CO * g.C + c16;
+#pragma unroll
+                        for (int co = 0; co < CO; ++co) {
+                            f32x2_t a = acc[py][px][co];
+#pragma unroll
+                            for (int e4 = 0; e4 < 4; ++e4) {
+                                const float4 ww = *(const float4*)(wt + co * g.C + 4 * e4);
+                                a = __builtin_elementwise_fma(xf[2 * e4], f32x2_t{ww.x, ww.y}, a);
+                                a = __builtin_elementwise_fma(xf[2 * e4 + 1], f32x2_t{ww.z, ww.w}, a);
+                            }
+                            acc[py][px][co] = a;
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
 template <int CO>
 __global__ __launch_bounds__(256) void k_bf16_lastT_s2(const unsigned short* __restrict__ x,
                                                        const float* __restrict__ w, const float* __restrict__ bias,
                                                        float* __restrict__ y, BnBf16Geom g, int act, float slope,
                                                        int qy0, int nqy, int qx0, int nqx) {
     extern __shared__ __attribute__((aligned(16))) float s_w[];          // [(r * S + s)][co][ci]
-    const int RS = g.R * g.S;
-    for (int i = threadIdx.x; i < g.C * CO * RS; i += 256) {
-        const int ci = i / (CO * RS), e = i - ci * (CO * RS);
-        const int co = e / RS, tap = e - co * RS;
-        s_w[(tap * CO + co) * g.C + ci] = w[i];
-    }
-    __syncthreads();
+    bfl_stage_weights<CO>(w, s_w, g);
     float bv[CO];
 #pragma unroll
     for (int co = 0; co < CO; ++co) bv[co] = bias ? bias[co] : 0.f;
@@ -443,54 +512,8 @@ __global__ __launch_bounds__(256) void k_bf16_lastT_s2(const unsigned short* __r
         const int qx = qx0 + (int)(item % nqx);
         const size_t rest = item / nqx;
         const int qy = qy0 + (int)(rest % nqy), n = (int)(rest / nqy);
-        // (even ci, odd ci) halves of every sum: the two are one packed FMA (v_pk_fma_f32), added at the end
         f32x2_t acc[2][2][CO];
-#pragma unroll
-        for (int py = 0; py < 2; ++py)
-#pragma unroll
-            for (int px = 0; px < 2; ++px)
-#pragma unroll
-                for (int co = 0; co < CO; ++co) acc[py][px][co] = f32x2_t{bv[co], 0.f};
-        const size_t nbase = (size_t)n * g.H * g.W * g.C;
-        for (int ty = 0; ty < nty; ++ty) {
-            for (int tx = 0; tx < ntx; ++tx) {
-                const int ih = qy - ty, iw = qx - tx;
-                const bool in = ih >= 0 && ih < g.H && iw >= 0 && iw < g.W;
-                const unsigned off = (unsigned)((nbase + ((size_t)ih * g.W + iw) * g.C) * 2);
-                for (int c16 = 0; c16 < g.C; c16 += 16) {
-                    // (selected per piece: an out-of-range marker plus a channel offset would wrap into range)
-                    const uint4 v0 = bn_buf_load16(xr, in ? off + (unsigned)c16 * 2 : 0xffffffffu);
-                    const uint4 v1 = bn_buf_load16(xr, in ? off + (unsigned)c16 * 2 + 16 : 0xffffffffu);
-                    f32x2_t xf[8];
-                    const unsigned u[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-                    for (int e = 0; e < 8; ++e)
-                        xf[e] = f32x2_t{__uint_as_float(u[e] << 16), __uint_as_float(u[e] & 0xffff0000u)};
-#pragma unroll
-                    for (int py = 0; py < 2; ++py) {
-                        const int r = py + 2 * ty;
-                        if (r >= g.R) continue;
-#pragma unroll
-                        for (int px = 0; px < 2; ++px) {
-                            const int sx = px + 2 * tx;
-                            if (sx >= g.S) continue;
-                            const float* wt = s_w + (size_t)(r * g.S + sx) * CO * g.C + c16;
-#pragma unroll
-                            for (int co = 0; co < CO; ++co) {
-                                f32x2_t a = acc[py][px][co];
-#pragma unroll
-                                for (int e4 = 0; e4 < 4; ++e4) {
-                                    const float4 ww = *(const float4*)(wt + co * g.C + 4 * e4);
-                                    a = __builtin_elementwise_fma(xf[2 * e4], f32x2_t{ww.x, ww.y}, a);
-                                    a = __builtin_elementwise_fma(xf[2 * e4 + 1], f32x2_t{ww.z, ww.w}, a);
-                                }
-                                acc[py][px][co] = a;
-                            }
-                        }
-                    }
-                }
-            }
-        }
+        bfl_s2_block<CO>(xr, s_w, bv, g, nty, ntx, n, qy, qx, acc);
 #pragma unroll
         for (int py = 0; py < 2; ++py) {
             const int oy = 2 * qy + py - g.pt;
@@ -553,5 +576,180 @@ int bn_launch_bf16_lastT(const void* x, const float* w, const float* bias, float
     }
 #undef BFL_GO
     BN_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ last layer, scored
+// The layer onto the frame fused with the per-frame squared error: the epilogue forms (act(acc) - target)^2 * mask
+// where the kernels above store act(acc), and x_hat is never written.  acc comes from bfl_s2_block / bfl_item, the
+// device code of the unfused kernels.  What differs is the walk: a workgroup's 256 lanes (4 waves) cover ONE piece
+// of ONE frame at a time -- piece blockIdx.x of P, frames blockIdx.y, blockIdx.y + gridDim.y, .. (the weights are
+// still staged once per workgroup) -- and leave that piece's sum in part[n][piece]: lane order (py, px, co) or
+// (t, co), wave shuffle tree, fixed LDS combine.  P and the pieces depend on the geometry of one frame alone, so a
+// frame scored alone gives the bits it gives in a batch.  bn_launch_frame_err_finish adds the P partials left to
+// right (P == 1: the workgroup writes out[n] itself).  No atomics.
+__device__ __forceinline__ float bfl_sq_term(float v, const void* __restrict__ target, bool u8,
+                                             const float* __restrict__ mask, size_t i) {
+    const float t = u8 ? (float)((const unsigned char*)target)[i] / 255.f : ((const float*)target)[i];
+    const float d = v - t;
+    const float e = d * d;
+    return mask ? e * mask[i] : e;
+}
+
+__device__ __forceinline__ float bfl_block_sum(float acc, float* red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+template <int CO, bool U8>
+__global__ __launch_bounds__(256) void k_bf16_lastT_s2_sqerr(const unsigned short* __restrict__ x,
+                                                             const float* __restrict__ w,
+                                                             const float* __restrict__ bias,
+                                                             const void* __restrict__ target,
+                                                             const float* __restrict__ mask, float* __restrict__ dst,
+                                                             BnBf16Geom g, int act, float slope, int qy0, int nqy,
+                                                             int qx0, int nqx, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float s_w[];          // [(r * S + s)][co][ci]
+    __shared__ float red[4];
+    bfl_stage_weights<CO>(w, s_w, g);
+    float bv[CO];
+#pragma unroll
+    for (int co = 0; co < CO; ++co) bv[co] = bias ? bias[co] : 0.f;
+    const bn_rsrc_t xr = bn_make_rsrc(x, (size_t)g.N * g.H * g.W * g.C * 2);
+    const size_t PQ = (size_t)g.P * g.Q;
+    const int nty = (g.R + 1) / 2, ntx = (g.S + 1) / 2;
+    const unsigned q = blockIdx.x * 256 + threadIdx.x;          // this lane's block of every frame
+    const bool have = q < (unsigned)(nqy * nqx);
+    const int qy = qy0 + (int)(q / nqx), qx = qx0 + (int)(q % nqx);
+    for (int n = blockIdx.y; n < g.N; n += gridDim.y) {          // (uniform over the workgroup: barriers inside)
+        float s = 0.f;
+        if (have) {
+            f32x2_t acc[2][2][CO];
+            bfl_s2_block<CO>(xr, s_w, bv, g, nty, ntx, n, qy, qx, acc);
+#pragma unroll
+            for (int py = 0; py < 2; ++py) {
+                const int oy = 2 * qy + py - g.pt;
+                if (oy < 0 || oy >= g.P) continue;
+#pragma unroll
+                for (int px = 0; px < 2; ++px) {
+                    const int ox = 2 * qx + px - g.pl;
+                    if (ox < 0 || ox >= g.Q) continue;
+#pragma unroll
+                    for (int co = 0; co < CO; ++co)
+                        s += bfl_sq_term(bn_apply_act(acc[py][px][co].x + acc[py][px][co].y, act, slope), target, U8,
+                                         mask, ((size_t)n * CO + co) * PQ + (size_t)oy * g.Q + ox);
+                }
+            }
+        }
+        const float tot = bfl_block_sum(s, red);
+        if (threadIdx.x == 0) dst[(size_t)n * gridDim.x + blockIdx.x] = gridDim.x == 1 ? tot * scale : tot;
+        __syncthreads();          // red is written again for the next frame
+    }
+}
+
+template <int CO, bool U8>
+__global__ __launch_bounds__(256) void k_bf16_lastT_sqerr(const unsigned short* __restrict__ x,
+                                                          const float* __restrict__ w, const float* __restrict__ bias,
+                                                          const void* __restrict__ target,
+                                                          const float* __restrict__ mask, float* __restrict__ dst,
+                                                          BnBf16Geom g, int act, float slope, int nchunk,
+                                                          unsigned frame_items, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float s_w[];          // [(r * S + s)][co][ci]
+    __shared__ float red[4];
+    bfl_stage_weights<CO>(w, s_w, g);
+    float bv[CO];
+#pragma unroll
+    for (int co = 0; co < CO; ++co) bv[co] = bias ? bias[co] : 0.f;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bn_rsrc_t xr = bn_make_rsrc(x, (size_t)g.N * g.H * g.W * g.C * 2);
+    const size_t PQ = (size_t)g.P * g.Q;
+    const unsigned item = blockIdx.x * 4 + wave;          // this wave's (phase, chunk) of every frame
+    const int chunk = (int)(item % nchunk), ph = (int)(item / nchunk);
+    for (int n = blockIdx.y; n < g.N; n += gridDim.y) {          // (uniform over the workgroup: barriers inside)
+        float s = 0.f;
+        BfTAxis ay, ax;
+        int jy[BFL_PX], jx[BFL_PX];
+        bool ok[BFL_PX];
+        float acc[BFL_PX][CO];
+        if (item < frame_items && bfl_item<CO>(xr, s_w, bv, g, n, ph, chunk, lane, ay, ax, jy, jx, ok, acc)) {
+#pragma unroll
+            for (int t = 0; t < BFL_PX; ++t) {
+                if (!ok[t]) continue;
+                const size_t pq = (size_t)(ay.o0 + jy[t] * g.stride) * g.Q + ax.o0 + jx[t] * g.stride;
+#pragma unroll
+                for (int co = 0; co < CO; ++co)
+                    s += bfl_sq_term(bn_apply_act(acc[t][co], act, slope), target, U8, mask,
+                                     ((size_t)n * CO + co) * PQ + pq);
+            }
+        }
+        const float tot = bfl_block_sum(s, red);
+        if (threadIdx.x == 0) dst[(size_t)n * gridDim.x + blockIdx.x] = gridDim.x == 1 ? tot * scale : tot;
+        __syncthreads();          // red is written again for the next frame
+    }
+}
+
+// How the scored layer cuts ONE frame up: the ONE plan that the workspace query and the launch both go by.
+struct BflErrPlan { int qy0, nqy, qx0, nqx, nchunk; unsigned frame_items, parts; };
+static BflErrPlan bfl_err_plan(const BnBf16Geom& g) {
+    BflErrPlan p{};
+    if (g.stride == 2) {
+        // blocks q with an output pixel: 2 q + p - crop in [0, P) for p = 0 or 1 (bf16_lastT_s2)
+        p.qy0 = g.pt / 2;
+        p.qx0 = g.pl / 2;
+        p.nqy = (g.pt + g.P - 1) / 2 - p.qy0 + 1;
+        p.nqx = (g.pl + g.Q - 1) / 2 - p.qx0 + 1;
+        p.parts = (unsigned)(((size_t)p.nqy * p.nqx + 255) / 256);
+    } else {
+        const int cy = (g.P + g.stride - 1) / g.stride, cx = (g.Q + g.stride - 1) / g.stride;
+        p.nchunk = (cy * cx + 64 * BFL_PX - 1) / (64 * BFL_PX);
+        p.frame_items = (unsigned)(g.stride * g.stride * p.nchunk);
+        p.parts = (p.frame_items + 3) / 4;
+    }
+    return p;
+}
+
+size_t bn_bf16_lastT_sqerr_ws_bytes(const BnBf16Geom& g) {
+    if (!bn_bf16_lastT_ok(g)) return 0;
+    const unsigned parts = bfl_err_plan(g).parts;
+    return parts == 1 ? 0 : (size_t)g.N * parts * sizeof(float);
+}
+
+int bn_launch_bf16_lastT_sqerr(const void* x, const float* w, const float* bias, const void* target, int target_is_u8,
+                               const float* mask, float* out, const BnBf16Geom& g, int act, float slope, float scale,
+                               void* ws, hipStream_t st) {
+    if (!bn_bf16_lastT_ok(g)) return BN_E_SHAPE;
+    const BflErrPlan p = bfl_err_plan(g);
+    // (bn_bf16_lastT_ok bounds N P Q below 2^31, so parts is far below the grid's limit)
+    const unsigned gy = (unsigned)min(g.N, max(1, (int)(BFL_MAX_BLOCKS / p.parts)));
+    const dim3 grid(p.parts, gy);
+    const size_t lds = (size_t)g.R * g.S * g.K * g.C * sizeof(float);
+    const unsigned short* xs = (const unsigned short*)x;
+    float* dst = p.parts == 1 ? out : (float*)ws;
+#define BFL_ERR2(CO, U8)                                                                                          \
+    BN_LAUNCH_MAIN((k_bf16_lastT_s2_sqerr<CO, U8>), grid, dim3(256), lds, st, xs, w, bias, target, mask, dst, g, act, \
+                   slope, p.qy0, p.nqy, p.qx0, p.nqx, scale)
+#define BFL_ERR(CO, U8)                                                                                           \
+    BN_LAUNCH_MAIN((k_bf16_lastT_sqerr<CO, U8>), grid, dim3(256), lds, st, xs, w, bias, target, mask, dst, g, act,    \
+                   slope, p.nchunk, p.frame_items, scale)
+#define BFL_ERR_CO(GO, U8)                                                                                        \
+    switch (g.K) {                                                                                                \
+        case 1: GO(1, U8); break;                                                                                 \
+        case 2: GO(2, U8); break;                                                                                 \
+        case 3: GO(3, U8); break;                                                                                 \
+        default: GO(4, U8); break;                                                                                \
+    }
+    if (g.stride == 2) {
+        if (target_is_u8) { BFL_ERR_CO(BFL_ERR2, true) } else { BFL_ERR_CO(BFL_ERR2, false) }
+    } else {
+        if (target_is_u8) { BFL_ERR_CO(BFL_ERR, true) } else { BFL_ERR_CO(BFL_ERR, false) }
+    }
+#undef BFL_ERR_CO
+#undef BFL_ERR
+#undef BFL_ERR2
+    BN_LAUNCH_CHECK();
+    if (p.parts > 1) return bn_launch_frame_err_finish(dst, out, g.N, p.parts, scale, st);
     return 0;
 }

@@ -1,4 +1,5 @@
-"""Inference-only encode of every trial -> ``*_latents.pkl`` (BASELINE config 5).
+"""Inference-only passes over every trial: latents -> ``*_latents.pkl`` (BASELINE config 5) and per-frame
+reconstruction errors -> ``*_frame_errors.pkl``.
 
 Mirror of ``export_latents`` in the reference ``behavenet/fitting/eval.py:6-118``: same pickle
 schema ``{'latents': [per-trial (T x D) arrays, empty for gap trials], 'trials': batch_idxs}``
@@ -16,9 +17,11 @@ import torch
 
 from behavenet_amd import _hip
 from behavenet_amd.fitting import distributed as bdist
-from behavenet_amd.hip_functions import DECODE_DTYPES, ENCODE_DTYPES, decode_precision, encode_precision
+from behavenet_amd.hip_functions import (DECODE_DTYPES, ENCODE_DTYPES, decode_precision, encode_precision,
+                                         scoring_frames)
 
-__all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconstruction']
+__all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconstruction', 'export_frame_errors',
+           'frame_errors', 'frame_errors_device']
 
 
 def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -151,19 +154,21 @@ class _GraphedTrialEncoder(object):
         return rec
 
 
-def export_latents(data_generator, model, filename=None):
-    """Encode train/val/test trials of every session and pickle them (ref eval.py:6-118)."""
-    # multi-session generators serve lists of batches for training; latents are exported trial by
-    # trial (the reference's MSPSVAE.export_latents rebuilds a one-session-per-batch generator,
+def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond_enc):
+    """The trial walk the exporters share: every train / val / test trial of every session goes once through
+    ``on_device_fn(images, sess, data)`` (device-resident frames; the results stay on the device and come to the
+    host in ONE transfer at the end) or ``on_host_fn(images, sess, data)`` (-> numpy).  Under
+    ``torch.distributed`` a trial is owned by its identity and the results are gathered on rank 0.
+    -> per session a list with one array per trial (empty for trials in no split), or None on the other ranks."""
+    # multi-session generators serve lists of batches for training; trials are exported one by
+    # one (the reference's MSPSVAE.export_latents rebuilds a one-session-per-batch generator,
     # vaes.py:1198-1216)
     single = {'return_multiple': False} \
         if getattr(data_generator, 'n_sessions_per_batch', 1) > 1 else {}
     model.eval()
     rank, world = bdist.rank(), bdist.world_size()
 
-    latents = [[np.array([]) for _ in range(ds.n_trials)] for ds in data_generator.datasets]
-    cond_enc = model.hparams['model_class'] == 'cond-ae' and \
-        model.hparams.get('conditional_encoder', False)
+    results = [[np.array([]) for _ in range(ds.n_trials)] for ds in data_generator.datasets]
     # which rank encodes a trial is a function of the trial's identity (its position in the
     # sorted list of all (session, trial) pairs), not of the order in which the generator
     # happens to serve it on this rank
@@ -185,7 +190,6 @@ def export_latents(data_generator, model, filename=None):
     if serve_prev is not None and conv_u8:
         data_generator.serve_uint8 = True
     on_device = {}          # (session, trial) -> device tensor: ONE transfer to the host at the end
-    encode = _GraphedTrialEncoder(model)
     try:
         for dtype in ['train', 'val', 'test']:
             data_generator.reset_iterators(dtype)
@@ -195,24 +199,23 @@ def export_latents(data_generator, model, filename=None):
             for _ in range(n_batches):
                 data, sess = data_generator.next_batch(dtype, **single, **skip)
                 if data is None:
-                    # the generator ran dry before its own count: latents of the remaining trials would be
+                    # the generator ran dry before its own count: the remaining trials would be
                     # exported EMPTY without a word
-                    raise RuntimeError('export_latents: the generator ended after %d of %d %s batches'
-                                       % (_, n_batches, dtype))
+                    raise RuntimeError('%s: the generator ended after %d of %d %s batches'
+                                       % (who, _, n_batches, dtype))
                 if not isinstance(data, dict):       # SKIPPED: another rank's trial
                     continue
                 idx = data['batch_idx']
                 idx = idx.item() if hasattr(idx, 'item') else int(idx)
                 if owner[(sess, idx)] != rank:
                     continue
-                labels_2d = data['labels_sc'][0] if cond_enc else None
                 images = data['images'][0]
                 if not torch.is_tensor(images):      # generators serving numpy arrays (as_numpy)
                     images = torch.from_numpy(np.asarray(images))
                 if images.is_cuda:
-                    on_device[(sess, idx)] = encode(images, sess, labels_2d)
+                    on_device[(sess, idx)] = on_device_fn(images, sess, data)
                 else:
-                    latents[sess][idx] = encode_trial(model, images, sess, labels_2d)
+                    results[sess][idx] = on_host_fn(images, sess, data)
     finally:
         if serve_prev is not None:
             data_generator.serve_uint8 = serve_prev
@@ -222,39 +225,59 @@ def export_latents(data_generator, model, filename=None):
         pos = 0
         for k in keys:
             n = on_device[k].shape[0]
-            latents[k[0]][k[1]] = flat[pos:pos + n].copy()
+            results[k[0]][k[1]] = flat[pos:pos + n].copy()
             pos += n
         del on_device
 
     if world > 1:
         import torch.distributed as dist
         gathered = [None] * world if rank == 0 else None
-        dist.gather_object(latents, gathered, dst=0)
+        dist.gather_object(results, gathered, dst=0)
         if rank != 0:
-            return []
+            return None
         for other in gathered[1:]:
             for s, per_sess in enumerate(other):
                 for i, arr in enumerate(per_sess):
                     if arr.size:
-                        latents[s][i] = arr
-        missing = [key for key in wanted if latents[key[0]][key[1]].size == 0]
+                        results[s][i] = arr
+        missing = [key for key in wanted if results[key[0]][key[1]].size == 0]
         if missing:
-            raise RuntimeError('export_latents: %d trials were encoded by no rank, e.g. %s' % (
-                len(missing), missing[:3]))
+            raise RuntimeError('%s: %d trials were %s by no rank, e.g. %s' % (
+                who, len(missing), 'encoded' if who == 'export_latents' else 'scored', missing[:3]))
+    return results
 
+
+def _write_per_session(data_generator, model, filename, suffix, key, results, what):
     filenames = []
     for sess, dataset in enumerate(data_generator.datasets):
         if filename is None:
-            sess_id = '%s_%s_%s_%s_latents.pkl' % (
-                dataset.lab, dataset.expt, dataset.animal, dataset.session)
+            sess_id = '%s_%s_%s_%s_%s.pkl' % (
+                dataset.lab, dataset.expt, dataset.animal, dataset.session, suffix)
             out = os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, sess_id)
         else:
             out = filename
-        print('saving latents %i of %i:\n%s' % (sess + 1, data_generator.n_datasets, out))
+        print('saving %s %i of %i:\n%s' % (what, sess + 1, data_generator.n_datasets, out))
         with open(out, 'wb') as f:
-            pickle.dump({'latents': latents[sess], 'trials': dataset.batch_idxs}, f)
+            pickle.dump({key: results[sess], 'trials': dataset.batch_idxs}, f)
         filenames.append(out)
     return filenames
+
+
+def export_latents(data_generator, model, filename=None):
+    """Encode train/val/test trials of every session and pickle them (ref eval.py:6-118)."""
+    cond_enc = model.hparams['model_class'] == 'cond-ae' and \
+        model.hparams.get('conditional_encoder', False)
+    encode = _GraphedTrialEncoder(model)
+
+    def labels_2d_of(data):
+        return data['labels_sc'][0] if cond_enc else None
+    latents = _export_per_trial(
+        'export_latents', data_generator, model,
+        lambda images, sess, data: encode(images, sess, labels_2d_of(data)),
+        lambda images, sess, data: encode_trial(model, images, sess, labels_2d_of(data)), cond_enc)
+    if latents is None:
+        return []
+    return _write_per_session(data_generator, model, filename, 'latents', 'latents', latents, 'latents')
 
 
 # which element of ``model(x)`` holds the latents (the reconstruction is always element 0): AE / cond-AE -> (x_hat, z);
@@ -300,3 +323,115 @@ def get_reconstruction(model, inputs, dataset=None, return_latents=False, labels
             recon, latents = model.decoding(t, None, None, dataset=None), t
     recon, latents = recon.detach().cpu().numpy(), latents.detach().cpu().numpy()
     return (recon, latents) if return_latents else recon
+
+
+# ------------------------------------------------------------------------------------------ frame errors
+def _forward_kwargs(cls, sess):
+    """How ``frame_errors_device`` calls each class's ``forward`` (the conditional classes get their chunk's labels
+    on top): the posterior mean for every variational class, cond-VAE included -- a score must not depend on a draw."""
+    kwargs = {'dataset': sess}
+    if cls in ('vae', 'beta-tcvae', 'ps-vae', 'msps-vae', 'cond-vae'):
+        kwargs['use_mean'] = True
+    return kwargs
+
+
+def _frame_errors_device(model, y, sess, masks, labels, labels_2d, chunk_size, fused=True):
+    """``frame_errors_device`` inside whatever precision blocks the caller opened.  ``fused=False`` keeps the
+    decoder from scoring in its last layer (tools/bench_frame_errors.py measures both)."""
+    cls = model.hparams['model_class']
+    if cls not in _LATENTS_AT:
+        raise ValueError('Invalid model class %s' % cls)
+    if y.dim() != 4:
+        raise ValueError('frame_errors: expected frames (T, C, H, W), got %s' % (tuple(y.shape),))
+    if y.dtype not in (torch.uint8, torch.float32):
+        raise ValueError('frame_errors: frames must be uint8 or float32, got %s' % y.dtype)
+    model.eval()
+    y = y.contiguous()
+    n, d = y.shape[0], y[0].numel()
+    if masks is not None:
+        # one (C, H, W) mask per trial, or per-frame masks (models.aes.frame_masks)
+        if masks.dim() == y.dim() - 1:
+            masks = masks.unsqueeze(0)
+        if masks.dtype != torch.float32:
+            masks = masks.float()
+    # (conv encoders take the stored uint8 frames as they are, as in _encode_trial_device; the TARGET stays
+    # uint8 either way: the kernels divide by 255 as bn_u8_to_unit_float does)
+    x = y
+    if y.dtype == torch.uint8 and (labels_2d is not None or model.hparams.get('model_type', 'conv') != 'conv'):
+        x = _hip.u8_to_unit_float(y)
+    kwargs = _forward_kwargs(cls, sess)
+    out = torch.empty((n,), dtype=torch.float32, device=y.device)
+    with torch.no_grad():
+        for beg in range(0, n, chunk_size):
+            end = min(beg + chunk_size, n)
+            target = y[beg:end]
+            mask = None
+            if masks is not None:
+                mask = masks[beg:end] if masks.shape[0] != 1 else masks
+                if mask.shape[0] == 1 and end - beg != 1:
+                    mask = mask.expand_as(target)
+                mask = mask.contiguous()
+            if cls in ('cond-ae', 'cond-vae'):
+                kwargs.update(labels=labels[beg:end], labels_2d=None if labels_2d is None else labels_2d[beg:end])
+            if fused:
+                with scoring_frames(target, mask, 1.0 / d) as req:
+                    x_hat = model(x[beg:end], **kwargs)[0]
+                scores = req.scores
+            else:
+                x_hat, scores = model(x[beg:end], **kwargs)[0], None
+            if scores is None:
+                scores = _hip.frame_sq_err(x_hat.contiguous().view(target.shape), target, mask, 1.0 / d)
+            out[beg:end].copy_(scores)
+    return out
+
+
+def frame_errors_device(model, y, sess=None, masks=None, labels=None, labels_2d=None, chunk_size=200):
+    """Per-frame reconstruction error of one trial as an fp32 DEVICE tensor (T,):
+
+        mse[n] = mean over (C, H, W) of (x_hat[n] - y[n])^2 * mask
+
+    -- the reference's ``losses.mse`` (losses.py:56-59) of one frame, the full C H W in the denominator with
+    masks too.  ``y``: fp32 frames or stored uint8 frames (value / 255); ``masks``: one (C, H, W) mask for the
+    trial or one per frame.  Eval mode, ``no_grad``, the posterior mean for every variational class.  The
+    squared errors are reduced on the device (``bn_frame_sq_err``); a frame's value does not depend on
+    ``chunk_size`` or on its position in the trial.
+
+    Three lanes: by default the model's own fp32 ``forward`` gives x_hat (every class and architecture);
+    ``hparams['hip_decode_dtype'] = 'bf16'`` runs a served decoder on its bf16 stack, whose layer onto the frame
+    scores the frames in its epilogue so that x_hat is never written (``bn_convT2d_last_bf16_sqerr``);
+    ``hparams['hip_encode_dtype'] = 'bf16'`` does the same for the encoder half.  The keys are independent, and
+    this is the one entry point that honours both."""
+    with encode_precision(encode_dtype_of(model)), decode_precision(decode_dtype_of(model)):
+        return _frame_errors_device(model, y, sess, masks, labels, labels_2d, chunk_size)
+
+
+def frame_errors(model, y, sess=None, masks=None, labels=None, labels_2d=None, chunk_size=200):
+    """``frame_errors_device`` as a numpy array (T,)."""
+    return frame_errors_device(model, y, sess, masks, labels, labels_2d, chunk_size).cpu().numpy()
+
+
+def export_frame_errors(data_generator, model, filename=None):
+    """Score train/val/test trials of every session and pickle the per-frame errors next to the latents:
+    ``{'mse': [per-trial (T,) float32 arrays, empty for trials in no split], 'trials': batch_idxs}`` in
+    ``<lab>_<expt>_<animal>_<session>_frame_errors.pkl``.  The trial walk is ``export_latents``' (ownership by
+    identity under ``torch.distributed``, stored uint8 frames where the model takes them, one transfer to the host
+    at the end); every trial goes through ``frame_errors_device`` with the batch's masks and, for the conditional
+    classes, labels.  Launched eagerly: the scoring has no HIP-graph replay (``hip_graph_encode`` covers the
+    latents alone)."""
+    cls = model.hparams['model_class']
+    cond_enc = cls == 'cond-ae' and model.hparams.get('conditional_encoder', False)
+    decode_dtype_of(model), encode_dtype_of(model)          # (an invalid key is an error before any trial is read)
+    chunk = int(model.hparams.get('export_chunk_frames', 1024))
+
+    def score(images, sess, data):
+        masks = data['masks'][0] if 'masks' in data else None
+        labels = data['labels'][0] if cls in ('cond-ae', 'cond-vae') else None
+        labels_2d = data['labels_sc'][0] if cond_enc else None
+        return frame_errors_device(model, images, sess, masks, labels, labels_2d, chunk)
+
+    def score_host(images, sess, data):
+        return np.asarray(score(images, sess, data).cpu().numpy(), dtype=np.float32)
+    errors = _export_per_trial('export_frame_errors', data_generator, model, score, score_host, cond_enc)
+    if errors is None:
+        return []
+    return _write_per_session(data_generator, model, filename, 'frame_errors', 'mse', errors, 'frame errors')

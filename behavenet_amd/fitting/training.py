@@ -828,6 +828,11 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
         export_latents(data_generator, best_val_model)
     elif method == 'nll' and hparams.get('export_predictions', False):
         raise NotImplementedError('neural decoders are outside the MI355X hot path')
+    if method == 'ae' and hparams.get('export_frame_errors', False):
+        if is_main:
+            print('exporting frame errors')
+        from behavenet_amd.fitting.eval import export_frame_errors
+        export_frame_errors(data_generator, best_val_model)
     if resume and is_main:
         if state_writer is not None:
             state_writer.wait()

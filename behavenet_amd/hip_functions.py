@@ -770,11 +770,15 @@ def stack_unserved_reason_bf16_dec(plan):
     return None
 
 
-def convT_stack_bf16(plan, h, params):
+def convT_stack_bf16(plan, h, params, frame_err=None):
     """The transposed-conv stack on bf16 operands / fp32 accumulation: fp32 (N, C, H, W) input (the dense
     layer's output) -> fp32 (N, C, H, W) output of the last layer.  Inference only.  The weights are converted
     at the start of EVERY call, for the reason given in ``conv_stack_bf16``; a last layer of 1..4 channels keeps
-    its fp32 weights.  The bf16 activations between the layers never leave this function."""
+    its fp32 weights.  The bf16 activations between the layers never leave this function.
+
+    With ``frame_err`` (a :class:`FrameErrRequest`) a last layer of 1..4 channels is scored instead of stored
+    (``bn_convT2d_last_bf16_sqerr``): the per-frame errors go to ``frame_err.scores`` and None is returned, x_hat
+    is never written.  A wider last layer is a matrix-core layer: x_hat is returned, the request untouched."""
     if torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in params)):
         raise RuntimeError('convT_stack_bf16 is inference only: call it under torch.no_grad()')
     if h.shape[1:] != (plan[0].cin, plan[0].hin, plan[0].win):
@@ -798,9 +802,46 @@ def convT_stack_bf16(plan, h, params):
         w, b = params[2 * i].detach(), params[2 * i + 1].detach()
         if i in wps:
             a = _hip.convT2d_fwd_bf16(a, wps[i], b, layer.geom(n), layer.act, LRELU_SLOPE, out_f32=(i == last))
+        elif frame_err is not None:
+            frame_err.scores = _hip.convT2d_last_bf16_sqerr(
+                a, w.contiguous(), b, frame_err.target, frame_err.mask, layer.geom(n), layer.act, LRELU_SLOPE,
+                frame_err.scale)
+            a = None
         else:
             a = _hip.convT2d_last_bf16(a, w.contiguous(), b, layer.geom(n), layer.act, LRELU_SLOPE)
     return a
+
+
+# -- per-frame reconstruction errors (inference only) -------------------------------------------
+_frame_err_tls = threading.local()
+
+
+class FrameErrRequest(object):
+    """What ``fitting.eval.frame_errors_device`` asks of the decoder below the model's ``forward``: the frames
+    (fp32, or stored uint8), the optional fp32 mask of their shape and the scale of the sums.  A decoder that
+    scores in the epilogue of its last layer leaves the (N,) result in ``scores``; any other decoder ignores the
+    request and returns x_hat as always."""
+
+    def __init__(self, target, mask, scale):
+        self.target, self.mask, self.scale, self.scores = target, mask, float(scale), None
+
+
+def frame_err_request():
+    """The calling thread's open request, or None (the default: nothing but ``scoring_frames`` sets one)."""
+    return getattr(_frame_err_tls, 'req', None)
+
+
+@contextlib.contextmanager
+def scoring_frames(target, mask, scale):
+    """Within the block ONE decoder call of this thread may score its frames against ``target`` instead of
+    returning them (``FrameErrRequest``).  Only the bf16 decoder stack looks at it (``decode_precision``), under
+    that stack's own eligibility rules; thread-local; nothing in training enters it."""
+    prev = frame_err_request()
+    req = _frame_err_tls.req = FrameErrRequest(target, mask, scale)
+    try:
+        yield req
+    finally:
+        _frame_err_tls.req = prev
 
 
 _frame_scale_cache = {}

@@ -478,6 +478,37 @@ int bn_convT2d_last_bf16(const void* x, const float* w, const float* b, float* y
                          int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
                          int off_t, int off_l, int Ho, int Wo, int act, float slope, bn_stream_t stream);
 
+/* The layer onto the frame fused with the per-frame squared error: every x_hat value is computed by the
+ * device code of bn_convT2d_last_bf16 and scored in the epilogue instead of being stored,
+ *   out[n] = scale * sum_{co, h, w} (x_hat[n] - target[n])^2 * mask[n]        fp32 (N,)
+ * target: fp32 (N, Co, Ho, Wo), or with target_is_u8 stored uint8 frames (value / 255); mask: fp32 of
+ * the target's shape, nullable.  A frame's summation order depends on the geometry of one frame
+ * alone: out[n] does not change with N or with the frame's position, and there are no atomics.
+ * `ws`: bn_convT2d_last_bf16_sqerr_ws_bytes(geometry) bytes (per-frame partial sums; 0 for small
+ * frames).  Serves exactly what bn_convT2d_last_bf16_ok reports; BN_E_SHAPE (nothing written)
+ * otherwise, for another activation or an x that is not 16-byte aligned. */
+size_t bn_convT2d_last_bf16_sqerr_ws_bytes(int N, int Ci, int Hi, int Wi, int Co, int R, int S,
+                                           int stride, int off_t, int off_l, int Ho, int Wo);
+int bn_convT2d_last_bf16_sqerr(const void* x, const float* w, const float* b, const void* target,
+                               int target_is_u8, const float* mask, float* out,
+                               int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
+                               int off_t, int off_l, int Ho, int Wo, int act, float slope, float scale,
+                               void* ws, size_t ws_bytes, bn_stream_t stream);
+
+/* Per-frame squared error of a reconstruction that is already in memory:
+ *   out[n] = scale * sum_{i < D} (xhat[n, i] - target[n, i])^2 * mask[n, i]        fp32 (N,)
+ * xhat fp32 (N, D); target fp32 (N, D), or with target_is_u8 uint8 (value / 255, the division of
+ * bn_u8_to_unit_float); mask fp32 (N, D), nullable.  Any N and D.  16-byte loads where every frame
+ * of every operand starts on a 16-byte boundary, element-by-element loads otherwise -- the summation
+ * order is a function of D alone either way, so out[n] has the same bits whatever N, the frame's
+ * position and the alignment; no atomics.  `ws`: bn_frame_sq_err_ws_bytes(N, D) bytes (0 up to 4096
+ * elements a frame).  BN_E_SHAPE (nothing written) for fp32 operands off a 4-byte boundary or more
+ * than 2^31 partial sums. */
+size_t bn_frame_sq_err_ws_bytes(int N, size_t D);
+int bn_frame_sq_err(const float* xhat, const void* target, int target_is_u8, const float* mask,
+                    float* out, int N, size_t D, float scale, void* ws, size_t ws_bytes,
+                    bn_stream_t stream);
+
 /* uint8 frames -> float32/255 (replaces the host-side astype(float32)/255 of
  * data_generator.py:251-263 for device-resident uint8 trials) */
 int bn_u8_to_unit_float(const unsigned char* in, float* out, size_t n, bn_stream_t stream);
