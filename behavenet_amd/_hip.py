@@ -131,11 +131,14 @@ SIGNATURES = {
     'bn_convT2d_last_bf16_sqerr': (
         _c_int, [_c_void_p] * 4 + [_c_int] + [_c_void_p] * 2 + _CONV_GEOM +
         [_c_int, _c_float, _c_float, _c_void_p, _c_size_t, _c_void_p]),
+    'bn_convT2d_last_bf16_u8': (
+        _c_int, [_c_void_p] * 4 + _CONV_GEOM + [_c_int, _c_float, _c_void_p]),
     'bn_frame_sq_err_ws_bytes': (_c_size_t, [_c_int, _c_size_t]),
     'bn_frame_sq_err': (
         _c_int, [_c_void_p] * 2 + [_c_int] + [_c_void_p] * 2 + [_c_int, _c_size_t, _c_float, _c_void_p, _c_size_t,
                                                                  _c_void_p]),
     'bn_u8_to_unit_float': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
+    'bn_unit_float_to_u8': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
     'bn_prof_read': (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
@@ -545,6 +548,23 @@ def convT2d_last_bf16_sqerr(x, w, b, target, mask, geom, act, slope, scale=1.0, 
         _ptr(x, 'x', dtype=torch.bfloat16), _ptr(w, 'w'), _ptr(b, 'b', allow_none=True), tp, is_u8, mp,
         _ptr(out, 'out'), *geom, act, slope, float(scale), ws, nbytes, _stream()), 'bn_convT2d_last_bf16_sqerr')
     return out
+
+
+def convT2d_last_bf16_u8(x, w, b, geom, act, slope, out=None):
+    """The layer onto the frame (``convT2d_last_bf16``) written as stored grey levels: uint8 (N, Co, Ho, Wo), the
+    bytes of ``unit_float_to_u8`` of that layer's output; the fp32 x_hat is never written."""
+    N, Ci, Hi, Wi, Co, R, S, st, ct, cl, Ho, Wo = geom
+    if tuple(x.shape) != (N, Hi, Wi, Ci):
+        raise HipLibraryError('convT2d_last_bf16_u8: expected activations (N,Hi,Wi,Ci)=%s, got %s'
+                              % ((N, Hi, Wi, Ci), tuple(x.shape)))
+    if tuple(w.shape) != (Ci, Co, R, S):
+        raise HipLibraryError('convT2d_last_bf16_u8: expected weights (Ci,Co,R,S)=%s, got %s'
+                              % ((Ci, Co, R, S), tuple(w.shape)))
+    y = _bf16_out(out, (N, Co, Ho, Wo), torch.uint8, x.device, 'convT2d_last_bf16_u8')
+    _check(load().bn_convT2d_last_bf16_u8(
+        _ptr(x, 'x', dtype=torch.bfloat16), _ptr(w, 'w'), _ptr(b, 'b', allow_none=True),
+        _ptr(y, 'y', dtype=torch.uint8), *geom, act, slope, _stream()), 'bn_convT2d_last_bf16_u8')
+    return y
 
 
 def set_force_generic(on):
@@ -983,6 +1003,15 @@ def u8_to_unit_float(u8):
     _check(load().bn_u8_to_unit_float(
         _ptr(u8, 'in', dtype=torch.uint8), _ptr(out, 'out'), u8.numel(), _stream()),
         'bn_u8_to_unit_float')
+    return out
+
+
+def unit_float_to_u8(x, out=None):
+    """fp32 unit-float values -> stored uint8 grey levels of the same shape: NaN -> 0, else
+    clamp(rint(x * 255), 0, 255), numpy's ``rint(float32(x) * float32(255))`` bit for bit (csrc/recon_u8.hip)."""
+    out = _bf16_out(out, tuple(x.shape), torch.uint8, x.device, 'unit_float_to_u8')
+    _check(load().bn_unit_float_to_u8(
+        _ptr(x, 'in'), _ptr(out, 'out', dtype=torch.uint8), x.numel(), _stream()), 'bn_unit_float_to_u8')
     return out
 
 

@@ -53,6 +53,17 @@ __device__ __forceinline__ float bn_apply_act(float v, int act, float slope) {
     return v;
 }
 
+// A unit-float pixel as a stored grey level ("reconstructions"): NaN -> 0, else
+// clamp(rint(v * 255), 0, 255).  The product is an fp32 multiplication of its own and the rounding is to nearest even
+// (v_rndne_f32), which is numpy's rint(float32(v) * float32(255)) bit for bit.  Every kernel that writes uint8
+// frames calls this one function.
+__device__ __forceinline__ unsigned bn_quantise_u8(float v) {
+#pragma clang fp contract(off)
+    const float r = rintf(v * 255.f);
+    // (the comparisons are false for NaN, so NaN takes the 0)
+    return (unsigned)(r >= 0.f ? (r <= 255.f ? r : 255.f) : 0.f);
+}
+
 // derivative of the activation expressed through its saved OUTPUT y
 __device__ __forceinline__ float bn_act_grad_from_output(float y, int act, float slope) {
     if (act == BN_ACT_LRELU) return y > 0.f ? 1.f : slope;

@@ -70,6 +70,10 @@ int bn_launch_frame_sq_err(const float* xhat, const void* target, int target_is_
 // out[n] = scale * (part[n][0] + .. + part[n][P - 1]), left to right
 int bn_launch_frame_err_finish(const float* part, float* out, int N, unsigned P, float scale, hipStream_t st);
 
+// recon_u8.hip: fp32 unit-float frames -> uint8 grey levels (bn_quantise_u8 of bn_common.h), any n
+bool bn_unit_float_to_u8_ok(size_t n);
+int bn_launch_unit_float_to_u8(const float* in, unsigned char* out, size_t n, hipStream_t st);
+
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);
 int bn_launch_bn_stats(const float* x, float* mean, float* var, int N, int C, int HW, void* ws,
@@ -202,3 +206,7 @@ size_t bn_bf16_lastT_sqerr_ws_bytes(const BnBf16Geom& g);
 int bn_launch_bf16_lastT_sqerr(const void* x, const float* w, const float* bias, const void* target, int target_is_u8,
                                const float* mask, float* out, const BnBf16Geom& g, int act, float slope, float scale,
                                void* ws, hipStream_t st);
+// the layer onto the frame with bn_quantise_u8 in its epilogue: y uint8 (N, K, P, Q), the fp32 x_hat is not
+// written; serves what bn_bf16_lastT_ok serves
+int bn_launch_bf16_lastT_u8(const void* x, const float* w, const float* bias, unsigned char* y, const BnBf16Geom& g,
+                            int act, float slope, hipStream_t st);

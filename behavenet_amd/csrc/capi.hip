@@ -1899,6 +1899,16 @@ extern "C" int bn_convT2d_last_bf16(const void* x, const float* w, const float* 
     return bn_launch_bf16_lastT(x, w, b, y, g, act, slope, (hipStream_t)stream);
 }
 
+extern "C" int bn_convT2d_last_bf16_u8(const void* x, const float* w, const float* b, unsigned char* y, int N, int Ci,
+                                       int Hi, int Wi, int Co, int R, int S, int stride, int off_t, int off_l, int Ho,
+                                       int Wo, int act, float slope, bn_stream_t stream) {
+    if (!x || !w || !y) return BN_E_BADARG;
+    const BnBf16Geom g = bf16_geom(N, Ci, Hi, Wi, Co, R, S, stride, off_t, off_l, Ho, Wo);
+    if (!bf16T_geom_valid(g)) return BN_E_BADARG;
+    if (!bn_bf16_lastT_ok(g) || !bf16T_act_ok(act) || !aligned16(x)) return BN_E_SHAPE;
+    return bn_launch_bf16_lastT_u8(x, w, b, y, g, act, slope, (hipStream_t)stream);
+}
+
 extern "C" size_t bn_convT2d_last_bf16_sqerr_ws_bytes(int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
                                                       int off_t, int off_l, int Ho, int Wo) {
     const BnBf16Geom g = bf16_geom(N, Ci, Hi, Wi, Co, R, S, stride, off_t, off_l, Ho, Wo);
@@ -1936,4 +1946,14 @@ extern "C" int bn_frame_sq_err(const float* xhat, const void* target, int target
     const size_t need = bn_frame_sq_err_ws_bytes_impl(N, D);
     if (need && (!ws || ws_bytes < need)) return BN_E_WORKSPACE;
     return bn_launch_frame_sq_err(xhat, target, target_is_u8, mask, out, N, D, scale, ws, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// fp32 unit-float frames -> stored uint8 grey levels (recon_u8.hip): NaN -> 0, else clamp(rint(x * 255), 0, 255).
+extern "C" int bn_unit_float_to_u8(const float* in, unsigned char* out, size_t n, bn_stream_t stream) {
+    if (!in || !out) return BN_E_BADARG;
+    // (an fp32 operand that is not even 4-byte aligned cannot be read at all)
+    if (((uintptr_t)in & 3) || !bn_unit_float_to_u8_ok(n)) return BN_E_SHAPE;
+    if (n == 0) return 0;
+    return bn_launch_unit_float_to_u8(in, out, n, (hipStream_t)stream);
 }

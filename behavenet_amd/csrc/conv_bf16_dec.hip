@@ -394,9 +394,19 @@ __device__ __forceinline__ bool bfl_item(const bn_rsrc_t& xr, const float* s_w, 
     return true;
 }
 
-template <int CO>
+// What the layer onto the frame stores per pixel, Y: float stores x_hat = act(acc); unsigned char stores the grey
+// level bn_quantise_u8(act(acc)) and x_hat is never written.  Kernels, walks and grids are the SAME templates for
+// both, so the bytes are bn_unit_float_to_u8 of the fp32 output by construction.
+template <typename Y>
+__device__ __forceinline__ Y bfl_out(float v);
+template <>
+__device__ __forceinline__ float bfl_out<float>(float v) { return v; }
+template <>
+__device__ __forceinline__ unsigned char bfl_out<unsigned char>(float v) { return (unsigned char)bn_quantise_u8(v); }
+
+template <int CO, typename Y>
 __global__ __launch_bounds__(256) void k_bf16_lastT(const unsigned short* __restrict__ x, const float* __restrict__ w,
-                                                    const float* __restrict__ bias, float* __restrict__ y,
+                                                    const float* __restrict__ bias, Y* __restrict__ y,
                                                     BnBf16Geom g, int act, float slope, int nchunk, unsigned nitems) {
     extern __shared__ __attribute__((aligned(16))) float s_w[];          // [(r * S + s)][co][ci]
     bfl_stage_weights<CO>(w, s_w, g);
@@ -423,7 +433,7 @@ __global__ __launch_bounds__(256) void k_bf16_lastT(const unsigned short* __rest
             const size_t pq = (size_t)(ay.o0 + jy[t] * g.stride) * g.Q + ax.o0 + jx[t] * g.stride;
 #pragma unroll
             for (int co = 0; co < CO; ++co)
-                y[((size_t)n * CO + co) * PQ + pq] = bn_apply_act(acc[t][co], act, slope);
+                y[((size_t)n * CO + co) * PQ + pq] = bfl_out<Y>(bn_apply_act(acc[t][co], act, slope));
         }
     }
 }
@@ -494,10 +504,12 @@ __device__ __forceinline__ void bfl_s2_block(const bn_rsrc_t& xr, const float* s
     }
 }
 
-template <int CO>
+// (Y = unsigned char: a lane's two pixels of a row leave as ONE 2-byte store where both are inside the frame and the
+// pair sits on a 2-byte boundary, as single bytes otherwise -- odd crops, odd widths, odd bases.)
+template <int CO, typename Y>
 __global__ __launch_bounds__(256) void k_bf16_lastT_s2(const unsigned short* __restrict__ x,
                                                        const float* __restrict__ w, const float* __restrict__ bias,
-                                                       float* __restrict__ y, BnBf16Geom g, int act, float slope,
+                                                       Y* __restrict__ y, BnBf16Geom g, int act, float slope,
                                                        int qy0, int nqy, int qx0, int nqx) {
     extern __shared__ __attribute__((aligned(16))) float s_w[];          // [(r * S + s)][co][ci]
     bfl_stage_weights<CO>(w, s_w, g);
@@ -514,24 +526,48 @@ __global__ __launch_bounds__(256) void k_bf16_lastT_s2(const unsigned short* __r
         const int qy = qy0 + (int)(rest % nqy), n = (int)(rest / nqy);
         f32x2_t acc[2][2][CO];
         bfl_s2_block<CO>(xr, s_w, bv, g, nty, ntx, n, qy, qx, acc);
+        if constexpr (sizeof(Y) == 1) {
+            const int ox = 2 * qx - g.pl;          // px = 0; px = 1 is ox + 1
+            const bool in0 = ox >= 0 && ox < g.Q, in1 = ox + 1 >= 0 && ox + 1 < g.Q;
 #pragma unroll
-        for (int py = 0; py < 2; ++py) {
-            const int oy = 2 * qy + py - g.pt;
-            if (oy < 0 || oy >= g.P) continue;
+            for (int py = 0; py < 2; ++py) {
+                const int oy = 2 * qy + py - g.pt;
+                if (oy < 0 || oy >= g.P) continue;
 #pragma unroll
-            for (int px = 0; px < 2; ++px) {
-                const int ox = 2 * qx + px - g.pl;
-                if (ox < 0 || ox >= g.Q) continue;
+                for (int co = 0; co < CO; ++co) {
+                    const unsigned u0 = bfl_out<Y>(bn_apply_act(acc[py][0][co].x + acc[py][0][co].y, act, slope));
+                    const unsigned u1 = bfl_out<Y>(bn_apply_act(acc[py][1][co].x + acc[py][1][co].y, act, slope));
+                    // (pointer arithmetic only: with in0 false, p is the byte before the row and is not touched)
+                    Y* p = y + (ptrdiff_t)(((size_t)n * CO + co) * PQ + (size_t)oy * g.Q) + ox;
+                    if (in0 && in1 && (((uintptr_t)p) & 1u) == 0) {
+                        *reinterpret_cast<unsigned short*>(p) = (unsigned short)(u0 | (u1 << 8));
+                    } else {
+                        if (in0) p[0] = (Y)u0;
+                        if (in1) p[1] = (Y)u1;
+                    }
+                }
+            }
+        } else {
 #pragma unroll
-                for (int co = 0; co < CO; ++co)
-                    y[((size_t)n * CO + co) * PQ + (size_t)oy * g.Q + ox] =
-                        bn_apply_act(acc[py][px][co].x + acc[py][px][co].y, act, slope);
+            for (int py = 0; py < 2; ++py) {
+                const int oy = 2 * qy + py - g.pt;
+                if (oy < 0 || oy >= g.P) continue;
+#pragma unroll
+                for (int px = 0; px < 2; ++px) {
+                    const int ox = 2 * qx + px - g.pl;
+                    if (ox < 0 || ox >= g.Q) continue;
+#pragma unroll
+                    for (int co = 0; co < CO; ++co)
+                        y[((size_t)n * CO + co) * PQ + (size_t)oy * g.Q + ox] =
+                            bfl_out<Y>(bn_apply_act(acc[py][px][co].x + acc[py][px][co].y, act, slope));
+                }
             }
         }
     }
 }
 
-static int bf16_lastT_s2(const unsigned short* xs, const float* w, const float* bias, float* y, const BnBf16Geom& g,
+template <typename Y>
+static int bf16_lastT_s2(const unsigned short* xs, const float* w, const float* bias, Y* y, const BnBf16Geom& g,
                          int act, float slope, hipStream_t st) {
     // blocks q with an output pixel: 2 q + p - crop in [0, P) for p = 0 or 1
     const int qy0 = g.pt / 2, qy1 = (g.pt + g.P - 1) / 2, qx0 = g.pl / 2, qx1 = (g.pl + g.Q - 1) / 2;
@@ -541,7 +577,7 @@ static int bf16_lastT_s2(const unsigned short* xs, const float* w, const float* 
     const size_t lds = (size_t)g.R * g.S * g.K * g.C * sizeof(float);
     const dim3 grid((unsigned)blocks);
 #define BFL_GO2(CO)                                                                                             \
-    BN_LAUNCH_MAIN((k_bf16_lastT_s2<CO>), grid, dim3(256), lds, st, xs, w, bias, y, g, act, slope, qy0, nqy, qx0, nqx)
+    BN_LAUNCH_MAIN((k_bf16_lastT_s2<CO, Y>), grid, dim3(256), lds, st, xs, w, bias, y, g, act, slope, qy0, nqy, qx0, nqx)
     switch (g.K) {
         case 1: BFL_GO2(1); break;
         case 2: BFL_GO2(2); break;
@@ -553,10 +589,11 @@ static int bf16_lastT_s2(const unsigned short* xs, const float* w, const float* 
     return 0;
 }
 
-int bn_launch_bf16_lastT(const void* x, const float* w, const float* bias, float* y, const BnBf16Geom& g, int act,
-                         float slope, hipStream_t st) {
+template <typename Y>
+static int bf16_lastT(const void* x, const float* w, const float* bias, Y* y, const BnBf16Geom& g, int act,
+                      float slope, hipStream_t st) {
     if (!bn_bf16_lastT_ok(g)) return BN_E_SHAPE;
-    if (g.stride == 2) return bf16_lastT_s2((const unsigned short*)x, w, bias, y, g, act, slope, st);
+    if (g.stride == 2) return bf16_lastT_s2<Y>((const unsigned short*)x, w, bias, y, g, act, slope, st);
     const int cy = (g.P + g.stride - 1) / g.stride, cx = (g.Q + g.stride - 1) / g.stride;
     const int nchunk = (cy * cx + 64 * BFL_PX - 1) / (64 * BFL_PX);
     const size_t items = (size_t)g.N * g.stride * g.stride * nchunk;
@@ -566,7 +603,7 @@ int bn_launch_bf16_lastT(const void* x, const float* w, const float* bias, float
     const dim3 grid((unsigned)blocks);
     const unsigned short* xs = (const unsigned short*)x;
 #define BFL_GO(CO)                                                                                              \
-    BN_LAUNCH_MAIN((k_bf16_lastT<CO>), grid, dim3(256), lds, st, xs, w, bias, y, g, act, slope, nchunk,          \
+    BN_LAUNCH_MAIN((k_bf16_lastT<CO, Y>), grid, dim3(256), lds, st, xs, w, bias, y, g, act, slope, nchunk,       \
                    (unsigned)items)
     switch (g.K) {
         case 1: BFL_GO(1); break;
@@ -577,6 +614,17 @@ int bn_launch_bf16_lastT(const void* x, const float* w, const float* bias, float
 #undef BFL_GO
     BN_LAUNCH_CHECK();
     return 0;
+}
+
+int bn_launch_bf16_lastT(const void* x, const float* w, const float* bias, float* y, const BnBf16Geom& g, int act,
+                         float slope, hipStream_t st) {
+    return bf16_lastT<float>(x, w, bias, y, g, act, slope, st);
+}
+
+// The layer onto the frame writing stored grey levels (uint8) instead of x_hat.
+int bn_launch_bf16_lastT_u8(const void* x, const float* w, const float* bias, unsigned char* y, const BnBf16Geom& g,
+                            int act, float slope, hipStream_t st) {
+    return bf16_lastT<unsigned char>(x, w, bias, y, g, act, slope, st);
 }
 
 // ------------------------------------------------------------------------------------------ last layer, scored

@@ -9,7 +9,8 @@ same key space:
 * ``.hdf5`` / ``.h5`` -- through ``h5py`` when it is installed (it is not in the build image:
   opening such a file then raises ImportError with this explanation);
 * ``.npz`` -- a numpy zip mirror with IDENTICAL member names (``images/trial_0000`` ...), readable
-  member by member without loading the file; ``write_npz_session`` / ``hdf5_to_npz`` produce it.
+  member by member without loading the file; ``write_npz_session`` / ``hdf5_to_npz`` produce it, and
+  ``NpzSessionWriter`` appends to one trial by trial.
 """
 
 import os
@@ -18,7 +19,7 @@ import zipfile
 
 import numpy as np
 
-__all__ = ['open_trial_store', 'write_npz_session', 'hdf5_to_npz', 'TRIAL_KEY']
+__all__ = ['open_trial_store', 'write_npz_session', 'NpzSessionWriter', 'hdf5_to_npz', 'TRIAL_KEY']
 
 TRIAL_KEY = 'trial_%04i'
 
@@ -103,6 +104,8 @@ class _NpzStore(object):
         if out.dtype != dtype or tuple(out.shape) != shape or not out.flags['C_CONTIGUOUS']:
             raise ValueError('read_into: buffer %s %s does not match the stored trial %s %s' % (
                 out.dtype, out.shape, dtype, shape))
+        if out.size == 0:                   # (a zero-frame member: nothing to read, and memoryview cannot cast it)
+            return out
         view = memoryview(out).cast('B')
         done, total = 0, view.nbytes
         with self._lock:
@@ -196,6 +199,59 @@ def write_npz_session(path, signals):
                 with zf.open('%s/%s.npy' % (signal, TRIAL_KEY % i), 'w', force_zip64=True) as f:
                     np.lib.format.write_array(f, np.ascontiguousarray(arr), allow_pickle=False)
     return path
+
+
+class NpzSessionWriter(object):
+    """A trial store written ONE trial at a time, in any order: ``write(signal, trial, array)`` appends the
+    uncompressed member ``<signal>/trial_%04i.npy`` exactly as ``write_npz_session`` stores it, so every member is
+    one contiguous read for ``open_trial_store``.  The file grows under ``path + '.tmp'`` and takes its name on
+    ``close()``: an interrupted writer leaves no half store under the final name.  A (signal, trial) written twice
+    is a ``ValueError`` (a zip file would hold both members).  As a context manager it closes on a clean exit and
+    discards the temporary file on an exception."""
+
+    def __init__(self, path):
+        self.path = path
+        self._tmp = path + '.tmp'
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        self._zf = zipfile.ZipFile(self._tmp, 'w', zipfile.ZIP_STORED, allowZip64=True)
+        self._written = set()
+
+    def write(self, signal, trial, array):
+        if self._zf is None:
+            raise ValueError('%s: the writer is closed' % self.path)
+        name = '%s/%s.npy' % (signal, TRIAL_KEY % trial)
+        if name in self._written:
+            raise ValueError('%s: %s is already written' % (self.path, name))
+        self._written.add(name)
+        with self._zf.open(name, 'w', force_zip64=True) as f:
+            np.lib.format.write_array(f, np.ascontiguousarray(array), allow_pickle=False)
+
+    def close(self):
+        if self._zf is None:
+            return self.path
+        self._zf.close()
+        self._zf = None
+        os.replace(self._tmp, self.path)
+        return self.path
+
+    def abort(self):
+        """Drop what was written: nothing appears under the final name."""
+        if self._zf is None:
+            return
+        self._zf.close()
+        self._zf = None
+        if os.path.exists(self._tmp):
+            os.remove(self._tmp)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:
+            self.abort()
+        return False
 
 
 def hdf5_to_npz(hdf5_path, npz_path=None):

@@ -1,5 +1,5 @@
-"""Inference-only passes over every trial: latents -> ``*_latents.pkl`` (BASELINE config 5) and per-frame
-reconstruction errors -> ``*_frame_errors.pkl``.
+"""Inference-only passes over every trial: latents -> ``*_latents.pkl`` (BASELINE config 5), per-frame
+reconstruction errors -> ``*_frame_errors.pkl`` and uint8 reconstructions -> ``*_reconstructions.npz``.
 
 Mirror of ``export_latents`` in the reference ``behavenet/fitting/eval.py:6-118``: same pickle
 schema ``{'latents': [per-trial (T x D) arrays, empty for gap trials], 'trials': batch_idxs}``
@@ -9,6 +9,7 @@ graph), accepts device-resident ``uint8`` frames (converted by ``bn_u8_to_unit_f
 under ``torch.distributed`` shards trials round-robin over ranks and gathers on rank 0.
 """
 
+import contextlib
 import os
 import pickle
 
@@ -18,10 +19,11 @@ import torch
 from behavenet_amd import _hip
 from behavenet_amd.fitting import distributed as bdist
 from behavenet_amd.hip_functions import (DECODE_DTYPES, ENCODE_DTYPES, decode_precision, encode_precision,
-                                         scoring_frames)
+                                         quantising_frames, scoring_frames)
 
 __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconstruction', 'export_frame_errors',
-           'frame_errors', 'frame_errors_device']
+           'frame_errors', 'frame_errors_device', 'export_reconstructions', 'reconstruct_trial',
+           'reconstruct_trial_device']
 
 
 def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -154,19 +156,23 @@ class _GraphedTrialEncoder(object):
         return rec
 
 
-def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond_enc):
+def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond_enc, sink=None):
     """The trial walk the exporters share: every train / val / test trial of every session goes once through
     ``on_device_fn(images, sess, data)`` (device-resident frames; the results stay on the device and come to the
     host in ONE transfer at the end) or ``on_host_fn(images, sess, data)`` (-> numpy).  Under
     ``torch.distributed`` a trial is owned by its identity and the results are gathered on rank 0.
-    -> per session a list with one array per trial (empty for trials in no split), or None on the other ranks."""
+    -> per session a list with one array per trial (empty for trials in no split), or None on the other ranks.
+
+    With ``sink`` nothing piles up: every result, device tensor or numpy array, goes to ``sink(sess, trial, result)``
+    as soon as its trial is done and the returned lists stay empty.  Such a walk is one process's: the caller runs
+    it on ONE rank, which owns every trial and enters no collective."""
     # multi-session generators serve lists of batches for training; trials are exported one by
     # one (the reference's MSPSVAE.export_latents rebuilds a one-session-per-batch generator,
     # vaes.py:1198-1216)
     single = {'return_multiple': False} \
         if getattr(data_generator, 'n_sessions_per_batch', 1) > 1 else {}
     model.eval()
-    rank, world = bdist.rank(), bdist.world_size()
+    rank, world = (0, 1) if sink is not None else (bdist.rank(), bdist.world_size())
 
     results = [[np.array([]) for _ in range(ds.n_trials)] for ds in data_generator.datasets]
     # which rank encodes a trial is a function of the trial's identity (its position in the
@@ -212,7 +218,9 @@ def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond
                 images = data['images'][0]
                 if not torch.is_tensor(images):      # generators serving numpy arrays (as_numpy)
                     images = torch.from_numpy(np.asarray(images))
-                if images.is_cuda:
+                if sink is not None:
+                    sink(sess, idx, (on_device_fn if images.is_cuda else on_host_fn)(images, sess, data))
+                elif images.is_cuda:
                     on_device[(sess, idx)] = on_device_fn(images, sess, data)
                 else:
                     results[sess][idx] = on_host_fn(images, sess, data)
@@ -247,15 +255,18 @@ def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond
     return results
 
 
+def _session_filename(model, dataset, filename, suffix):
+    """``filename``, or ``<lab>_<expt>_<animal>_<session>_<suffix>`` in the model's version directory."""
+    if filename is not None:
+        return filename
+    sess_id = '%s_%s_%s_%s_%s' % (dataset.lab, dataset.expt, dataset.animal, dataset.session, suffix)
+    return os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, sess_id)
+
+
 def _write_per_session(data_generator, model, filename, suffix, key, results, what):
     filenames = []
     for sess, dataset in enumerate(data_generator.datasets):
-        if filename is None:
-            sess_id = '%s_%s_%s_%s_%s.pkl' % (
-                dataset.lab, dataset.expt, dataset.animal, dataset.session, suffix)
-            out = os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, sess_id)
-        else:
-            out = filename
+        out = _session_filename(model, dataset, filename, suffix + '.pkl')
         print('saving %s %i of %i:\n%s' % (what, sess + 1, data_generator.n_datasets, out))
         with open(out, 'wb') as f:
             pickle.dump({key: results[sess], 'trials': dataset.batch_idxs}, f)
@@ -288,7 +299,7 @@ _LATENTS_AT = {'ae': 1, 'cond-ae': 1, 'cond-ae-msp': 1, 'vae': 1, 'beta-tcvae': 
 
 
 def get_reconstruction(model, inputs, dataset=None, return_latents=False, labels=None, labels_2d=None,
-                       apply_inverse_transform=True, use_mean=True):
+                       apply_inverse_transform=True, use_mean=True, as_uint8=False):
     """Images from images (through the whole model) or from latents (through the decoder) as numpy arrays
     (ref fitting/eval.py:286-374; the caller of ``forward`` / ``decoding`` behind the reference's plotting code).
 
@@ -296,7 +307,11 @@ def get_reconstruction(model, inputs, dataset=None, return_latents=False, labels
     completed first: cond-AE / cond-VAE get ``labels`` appended, AEMSP / PS-VAE / MSPS-VAE latents given in the
     transformed space are mapped back (``apply_inverse_transform``).  ``use_mean`` picks the posterior mean for the
     variational classes -- except cond-VAE, which the reference calls without it (kept: it samples there).
-    Runs under ``no_grad`` in eval mode."""
+    Runs under ``no_grad`` in eval mode.
+
+    ``as_uint8=True`` returns the reconstruction as ``np.uint8`` grey levels, quantised on the device
+    (``_hip.unit_float_to_u8``'s rule; a served bf16 decoder writes them in its last layer): a quarter of the copy to
+    the host.  The latents are returned as before."""
     cls = model.hparams['model_class']
     model.eval()
     # (arrays go where the model's parameters are -- the reference sends them to hparams['device'], which a model
@@ -304,7 +319,8 @@ def get_reconstruction(model, inputs, dataset=None, return_latents=False, labels
     t = inputs if torch.is_tensor(inputs) else torch.Tensor(inputs).to(next(model.parameters()).device)
     # (the only place that asks for the bf16 decoder; the encoder half of the image branch stays fp32 whatever
     # hparams['hip_encode_dtype'] says)
-    with torch.no_grad(), decode_precision(decode_dtype_of(model)):
+    with torch.no_grad(), decode_precision(decode_dtype_of(model)), \
+            (quantising_frames() if as_uint8 else contextlib.nullcontext()) as req:
         if t.dim() != 2:
             if cls not in _LATENTS_AT:
                 raise ValueError('Invalid model class %s' % cls)
@@ -321,6 +337,8 @@ def get_reconstruction(model, inputs, dataset=None, return_latents=False, labels
             elif cls in ('cond-ae-msp', 'ps-vae', 'msps-vae') and apply_inverse_transform:
                 t = model.get_inverse_transformed_latents(t, as_numpy=False)
             recon, latents = model.decoding(t, None, None, dataset=None), t
+        if as_uint8:
+            recon = req.frames if req.frames is not None else _hip.unit_float_to_u8(recon.contiguous())
     recon, latents = recon.detach().cpu().numpy(), latents.detach().cpu().numpy()
     return (recon, latents) if return_latents else recon
 
@@ -435,3 +453,181 @@ def export_frame_errors(data_generator, model, filename=None):
     if errors is None:
         return []
     return _write_per_session(data_generator, model, filename, 'frame_errors', 'mse', errors, 'frame errors')
+
+
+# ------------------------------------------------------------------------------------------ reconstructions
+def _reconstruct_trial_device(model, y, sess, labels, labels_2d, chunk_size, fused=True):
+    """``reconstruct_trial_device`` inside whatever precision blocks the caller opened.  ``fused=False`` keeps the
+    decoder from quantising in its last layer (tools/bench_reconstructions.py measures both)."""
+    cls = model.hparams['model_class']
+    if cls not in _LATENTS_AT:
+        raise ValueError('Invalid model class %s' % cls)
+    if y.dim() != 4:
+        raise ValueError('reconstruct_trial: expected frames (T, C, H, W), got %s' % (tuple(y.shape),))
+    if y.dtype not in (torch.uint8, torch.float32):
+        raise ValueError('reconstruct_trial: frames must be uint8 or float32, got %s' % y.dtype)
+    model.eval()
+    x = y.contiguous()
+    n = x.shape[0]
+    # (conv encoders take the stored uint8 frames as they are, as in _encode_trial_device)
+    if x.dtype == torch.uint8 and (labels_2d is not None or model.hparams.get('model_type', 'conv') != 'conv'):
+        x = _hip.u8_to_unit_float(x)
+    kwargs = _forward_kwargs(cls, sess)
+    out = None
+    with torch.no_grad():
+        for beg in range(0, n, chunk_size):
+            end = min(beg + chunk_size, n)
+            if cls in ('cond-ae', 'cond-vae'):
+                kwargs.update(labels=labels[beg:end], labels_2d=None if labels_2d is None else labels_2d[beg:end])
+            with (quantising_frames() if fused else contextlib.nullcontext()) as req:
+                x_hat = model(x[beg:end], **kwargs)[0]
+            frames = req.frames if fused else None
+            if frames is None:
+                frames = _hip.unit_float_to_u8(x_hat.contiguous())
+            if beg == 0 and end == n:
+                return frames          # (one pass: the decoder's own tensor, no copy)
+            if out is None:
+                out = torch.empty((n,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=frames.device)
+            out[beg:end].copy_(frames)
+    if out is None:          # (a trial without frames)
+        out = torch.empty((0,) + tuple(y.shape[1:]), dtype=torch.uint8, device=y.device)
+    return out
+
+
+def reconstruct_trial_device(model, y, sess=None, labels=None, labels_2d=None, chunk_size=200):
+    """The reconstruction of one trial as stored grey levels, a uint8 DEVICE tensor (T, C, H, W):
+
+        u8 = NaN -> 0, else clamp(rint(x_hat * 255), 0, 255)
+
+    -- fp32 product, round half to even (``bn_unit_float_to_u8``), the inverse of the ``value / 255`` by which stored
+    frames are read.  ``y``: fp32 frames or stored uint8 frames.  Eval mode, ``no_grad``, the posterior mean for every
+    variational class, cond-VAE included.  A frame's bytes do not depend on ``chunk_size`` or on its position in the
+    trial.
+
+    By default the model's own fp32 ``forward`` gives x_hat (every class and architecture) and
+    ``bn_unit_float_to_u8`` quantises it; ``hparams['hip_decode_dtype'] = 'bf16'`` runs a served decoder on its bf16
+    stack, whose layer onto the frame writes the grey levels itself so that the fp32 x_hat is never written
+    (``bn_convT2d_last_bf16_u8``); ``hparams['hip_encode_dtype'] = 'bf16'`` does the same for the encoder half.  The
+    keys are independent."""
+    with encode_precision(encode_dtype_of(model)), decode_precision(decode_dtype_of(model)):
+        return _reconstruct_trial_device(model, y, sess, labels, labels_2d, chunk_size)
+
+
+def reconstruct_trial(model, y, sess=None, labels=None, labels_2d=None, chunk_size=200):
+    """``reconstruct_trial_device`` as a numpy array (T, C, H, W) of uint8."""
+    return reconstruct_trial_device(model, y, sess, labels, labels_2d, chunk_size).cpu().numpy()
+
+
+class _PinnedTrialSink(object):
+    """Where ``export_reconstructions`` sends a trial's device result: into one of TWO pinned host buffers, copied
+    on a side stream so that trial k's copy runs under trial k + 1's kernels.  An event guards each buffer: before
+    a buffer is used again its copy is waited for and the filled buffer handed to ``write(sess, trial, array)``
+    (trial k - 1 is written while trial k is copied).  Host memory stays bounded by two trials, device memory by
+    the results whose copies are in flight.  Host results go to ``write`` as they are."""
+
+    def __init__(self, write):
+        self._write = write
+        self._stream = None
+        self._slots = [{'buf': None, 'event': None, 'pending': None} for _ in range(2)]
+        self._turn = 0
+
+    def _drain(self, slot):
+        if slot['pending'] is not None:
+            sess, trial, view = slot['pending']
+            slot['event'].synchronize()
+            slot['pending'] = None
+            self._write(sess, trial, view.numpy())
+
+    def __call__(self, sess, trial, result):
+        if not torch.is_tensor(result):
+            self._write(sess, trial, np.asarray(result))
+            return
+        if not result.is_cuda:
+            self._write(sess, trial, result.numpy())
+            return
+        result = result.contiguous()
+        slot = self._slots[self._turn]
+        self._turn ^= 1
+        self._drain(slot)
+        nbytes = result.numel() * result.element_size()
+        if slot['buf'] is None or slot['buf'].numel() < nbytes:
+            slot['buf'] = torch.empty(max(nbytes, 1), dtype=torch.uint8).pin_memory()
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(device=result.device)
+        if slot['event'] is None:
+            slot['event'] = torch.cuda.Event()
+        view = slot['buf'][:nbytes].view(result.dtype).view(result.shape)
+        self._stream.wait_stream(torch.cuda.current_stream(result.device))
+        with torch.cuda.stream(self._stream):
+            view.copy_(result, non_blocking=True)
+            slot['event'].record(self._stream)
+        result.record_stream(self._stream)          # (the result's memory is not reused before the copy has read it)
+        slot['pending'] = (sess, trial, view)
+
+    def flush(self):
+        """Hand over what is still in flight, oldest first."""
+        for slot in (self._slots[self._turn], self._slots[self._turn ^ 1]):
+            self._drain(slot)
+
+
+def export_reconstructions(data_generator, model, filename=None):
+    """Reconstruct train/val/test trials of every session and write them next to the latents as a trial store,
+    ``<lab>_<expt>_<animal>_<session>_reconstructions.npz``: ``images/trial_%04i`` holds the uint8 (T, C, H, W)
+    reconstruction of that trial (``reconstruct_trial_device``: quantised on the device, a quarter of the fp32 copy)
+    and a (0, C, H, W) member stands for each trial in no split, so ``open_trial_store(path).read('images', t)``
+    lines up with the session's own store and a data generator serves the file as ``images``.
+
+    The trial walk is ``export_latents``', with the batch's labels for the conditional classes, except that
+    nothing piles up on the device: each trial leaves through two pinned buffers on a side stream while the next
+    one is computed (``_PinnedTrialSink``) and is appended to its store at once (``NpzSessionWriter``; the file
+    takes its name when it is complete).  Launched eagerly.  Under ``torch.distributed`` rank 0 alone walks and
+    writes every trial -- frames are too large to gather as objects -- and the other ranks return [] at once.
+    ``filename`` names the one file of a single-session generator (``ValueError`` with several sessions).
+    -> the list of file names."""
+    from behavenet_amd.data.trial_store import NpzSessionWriter
+    cls = model.hparams['model_class']
+    cond_enc = cls == 'cond-ae' and model.hparams.get('conditional_encoder', False)
+    decode_dtype_of(model), encode_dtype_of(model)          # (an invalid key is an error before any trial is read)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return []
+    chunk = int(model.hparams.get('export_chunk_frames', 1024))
+
+    def reconstruct(images, sess, data):
+        labels = data['labels'][0] if cls in ('cond-ae', 'cond-vae') else None
+        labels_2d = data['labels_sc'][0] if cond_enc else None
+        return reconstruct_trial_device(model, images, sess, labels, labels_2d, chunk)
+
+    def reconstruct_host(images, sess, data):
+        return reconstruct(images, sess, data).cpu().numpy()
+
+    if filename is not None and data_generator.n_datasets > 1:
+        raise ValueError('export_reconstructions: one file per session; an explicit filename serves one session, '
+                         'the generator has %i' % data_generator.n_datasets)
+    filenames = [_session_filename(model, dataset, filename, 'reconstructions.npz')
+                 for dataset in data_generator.datasets]
+    writers, frame_shape = {}, {}
+
+    def write(sess, trial, array):
+        if sess not in writers:
+            print('saving reconstructions %i of %i:\n%s' % (sess + 1, data_generator.n_datasets, filenames[sess]))
+            writers[sess] = NpzSessionWriter(filenames[sess])
+        writers[sess].write('images', trial, array)
+        frame_shape[sess] = tuple(array.shape[1:])
+
+    sink = _PinnedTrialSink(write)
+    try:
+        _export_per_trial('export_reconstructions', data_generator, model, reconstruct, reconstruct_host, cond_enc,
+                          sink=sink)
+        sink.flush()
+        for sess, dataset in enumerate(data_generator.datasets):
+            if sess not in writers:
+                continue          # (a session without a train / val / test trial: no frame shape, no store)
+            split = set(int(t) for dt in ('train', 'val', 'test') for t in dataset.batch_idxs[dt])
+            for trial in range(dataset.n_trials):
+                if trial not in split:
+                    writers[sess].write('images', trial, np.empty((0,) + frame_shape[sess], dtype=np.uint8))
+    except BaseException:
+        for w in writers.values():
+            w.abort()
+        raise
+    return [writers[sess].close() for sess in sorted(writers)]

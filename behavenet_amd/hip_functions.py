@@ -770,7 +770,7 @@ def stack_unserved_reason_bf16_dec(plan):
     return None
 
 
-def convT_stack_bf16(plan, h, params, frame_err=None):
+def convT_stack_bf16(plan, h, params, frame_err=None, frame_u8=None):
     """The transposed-conv stack on bf16 operands / fp32 accumulation: fp32 (N, C, H, W) input (the dense
     layer's output) -> fp32 (N, C, H, W) output of the last layer.  Inference only.  The weights are converted
     at the start of EVERY call, for the reason given in ``conv_stack_bf16``; a last layer of 1..4 channels keeps
@@ -778,9 +778,16 @@ def convT_stack_bf16(plan, h, params, frame_err=None):
 
     With ``frame_err`` (a :class:`FrameErrRequest`) a last layer of 1..4 channels is scored instead of stored
     (``bn_convT2d_last_bf16_sqerr``): the per-frame errors go to ``frame_err.scores`` and None is returned, x_hat
-    is never written.  A wider last layer is a matrix-core layer: x_hat is returned, the request untouched."""
+    is never written.  A wider last layer is a matrix-core layer: x_hat is returned, the request untouched.
+
+    With ``frame_u8`` (a :class:`FrameU8Request`) a last layer of 1..4 channels writes stored grey levels instead
+    (``bn_convT2d_last_bf16_u8``): the uint8 frames go to ``frame_u8.frames`` and None is returned, under the same
+    rules.  Both requests at once is an error, raised before any launch."""
     if torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in params)):
         raise RuntimeError('convT_stack_bf16 is inference only: call it under torch.no_grad()')
+    if frame_err is not None and frame_u8 is not None:
+        raise RuntimeError('convT_stack_bf16: a scoring request and a quantising request at once; a decoder call '
+                           'serves one of them')
     if h.shape[1:] != (plan[0].cin, plan[0].hin, plan[0].win):
         raise ValueError('convT stack expects input (N,%d,%d,%d), got %s' % (
             plan[0].cin, plan[0].hin, plan[0].win, tuple(h.shape)))
@@ -806,6 +813,9 @@ def convT_stack_bf16(plan, h, params, frame_err=None):
             frame_err.scores = _hip.convT2d_last_bf16_sqerr(
                 a, w.contiguous(), b, frame_err.target, frame_err.mask, layer.geom(n), layer.act, LRELU_SLOPE,
                 frame_err.scale)
+            a = None
+        elif frame_u8 is not None:
+            frame_u8.frames = _hip.convT2d_last_bf16_u8(a, w.contiguous(), b, layer.geom(n), layer.act, LRELU_SLOPE)
             a = None
         else:
             a = _hip.convT2d_last_bf16(a, w.contiguous(), b, layer.geom(n), layer.act, LRELU_SLOPE)
@@ -836,12 +846,49 @@ def scoring_frames(target, mask, scale):
     """Within the block ONE decoder call of this thread may score its frames against ``target`` instead of
     returning them (``FrameErrRequest``).  Only the bf16 decoder stack looks at it (``decode_precision``), under
     that stack's own eligibility rules; thread-local; nothing in training enters it."""
+    if frame_u8_request() is not None:
+        raise RuntimeError('scoring_frames: a quantising request is open; a decoder call serves one of the two')
     prev = frame_err_request()
     req = _frame_err_tls.req = FrameErrRequest(target, mask, scale)
     try:
         yield req
     finally:
         _frame_err_tls.req = prev
+
+
+# -- reconstructions as stored grey levels (inference only) -------------------------------------
+_frame_u8_tls = threading.local()
+
+
+class FrameU8Request(object):
+    """What ``fitting.eval.reconstruct_trial_device`` asks of the decoder below the model's ``forward``: x_hat as
+    stored uint8 grey levels (``_hip.unit_float_to_u8``'s rule).  A decoder that quantises in the epilogue of its
+    last layer leaves the uint8 (N, C, H, W) tensor in ``frames``; any other decoder ignores the request and
+    returns fp32 x_hat as always."""
+
+    def __init__(self):
+        self.frames = None
+
+
+def frame_u8_request():
+    """The calling thread's open request, or None (the default: nothing but ``quantising_frames`` sets one)."""
+    return getattr(_frame_u8_tls, 'req', None)
+
+
+@contextlib.contextmanager
+def quantising_frames():
+    """Within the block ONE decoder call of this thread may leave its frames as uint8 grey levels instead of
+    returning them (``FrameU8Request``).  Only the bf16 decoder stack looks at it (``decode_precision``), under
+    that stack's own eligibility rules; thread-local; nothing in training enters it.  Opening it while a scoring
+    request is open (or the other way round) is a RuntimeError, before anything is launched."""
+    if frame_err_request() is not None:
+        raise RuntimeError('quantising_frames: a scoring request is open; a decoder call serves one of the two')
+    prev = frame_u8_request()
+    req = _frame_u8_tls.req = FrameU8Request()
+    try:
+        yield req
+    finally:
+        _frame_u8_tls.req = prev
 
 
 _frame_scale_cache = {}

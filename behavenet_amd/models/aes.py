@@ -21,8 +21,8 @@ from behavenet_amd.models.base import BaseModule, BaseModel
 from behavenet_amd.hip_functions import (
     ChunkScalars, ConvLayerPlan, FusedPixelLoss, Readback, activation, backward_chunks, bn_chunks,
     capturing, finish_loss, conv_stack_bf16, encode_dtype, stack_unserved_reason_bf16, warn_bf16_unserved,
-    convT_stack_bf16, decode_dtype, decode_precision, frame_err_request, stack_unserved_reason_bf16_dec,
-    warn_bf16_unserved_dec,
+    convT_stack_bf16, decode_dtype, decode_precision, frame_err_request, frame_u8_request,
+    stack_unserved_reason_bf16_dec, warn_bf16_unserved_dec,
     chunked_sq_err, conv_stack, conv_stack_bn, conv_stack_sq_err, first_layer_forward,
     join_side_streams, linear, begin_chunks, chunk_stream, max_pool, max_pool_act, max_unpool, conv_pool_act,
     pixel_loss_scales, reserve_device_pools)
@@ -487,8 +487,10 @@ class ConvAEDecoder(BaseModule):
             return FusedPixelLoss(x_hat, chunked_sq_err(
                 x_hat, target, pixel_loss.get('mask'), bounds, scales), kind, bounds)
         if decode_dtype() == 'bf16' and self._bf16_eligible(h):
-            # (an open request of fitting.eval.frame_errors_device: the last layer scores the frames, -> None)
-            return convT_stack_bf16(self._plan, h, params, frame_err=frame_err_request())
+            # (an open request of fitting.eval.frame_errors_device: the last layer scores the frames, -> None;
+            # one of fitting.eval.reconstruct_trial_device: it writes them as uint8 grey levels, -> None)
+            return convT_stack_bf16(self._plan, h, params, frame_err=frame_err_request(),
+                                    frame_u8=frame_u8_request())
         if any(self._unpool_before):
             # max-pooling architectures: MaxUnpool2d with the encoder's indices (last pooled first)
             # in front of its transposed convolution, layer by layer (ref aes.py:460-476)

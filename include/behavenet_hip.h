@@ -495,6 +495,16 @@ int bn_convT2d_last_bf16_sqerr(const void* x, const float* w, const float* b, co
                                int off_t, int off_l, int Ho, int Wo, int act, float slope, float scale,
                                void* ws, size_t ws_bytes, bn_stream_t stream);
 
+/* The layer onto the frame writing stored grey levels: every x_hat value is computed by the device
+ * code of bn_convT2d_last_bf16 and leaves through the rounding rule of bn_unit_float_to_u8 in the
+ * epilogue, y uint8 (N, Co, Ho, Wo); the fp32 x_hat is never written.  The bytes are those of
+ * bn_unit_float_to_u8 applied to bn_convT2d_last_bf16's output.  y needs no alignment.  Serves exactly
+ * what bn_convT2d_last_bf16_ok reports; BN_E_SHAPE (nothing written) otherwise, for another
+ * activation or an x that is not 16-byte aligned. */
+int bn_convT2d_last_bf16_u8(const void* x, const float* w, const float* b, unsigned char* y,
+                            int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
+                            int off_t, int off_l, int Ho, int Wo, int act, float slope, bn_stream_t stream);
+
 /* Per-frame squared error of a reconstruction that is already in memory:
  *   out[n] = scale * sum_{i < D} (xhat[n, i] - target[n, i])^2 * mask[n, i]        fp32 (N,)
  * xhat fp32 (N, D); target fp32 (N, D), or with target_is_u8 uint8 (value / 255, the division of
@@ -512,6 +522,14 @@ int bn_frame_sq_err(const float* xhat, const void* target, int target_is_u8, con
 /* uint8 frames -> float32/255 (replaces the host-side astype(float32)/255 of
  * data_generator.py:251-263 for device-resident uint8 trials) */
 int bn_u8_to_unit_float(const unsigned char* in, float* out, size_t n, bn_stream_t stream);
+
+/* unit-float frames -> stored uint8 grey levels, the inverse of bn_u8_to_unit_float on k / 255:
+ *   out[i] = NaN -> 0, else clamp(rint(in[i] * 255), 0, 255)
+ * The product is one fp32 multiplication and rint rounds half to even, i.e. numpy's
+ * rint(float32(x) * float32(255)) bit for bit; values below 0 and above 1 saturate.  Any n.  16-byte
+ * loads and stores where `in` and `out` both sit on a 16-byte boundary, element by element otherwise,
+ * with the same arithmetic.  BN_E_SHAPE (nothing written) for an `in` off a 4-byte boundary. */
+int bn_unit_float_to_u8(const float* in, unsigned char* out, size_t n, bn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * In-library kernel timing used by bench.py's roofline line: when enabled, every call of the
