@@ -41,15 +41,14 @@ SIGNATURES = {
     'bn_conv_ws_bytes': (_c_size_t, [_c_int] + _CONV_GEOM),
     'bn_conv_taps_bytes': (_c_size_t, [_c_int] + _CONV_GEOM),
     'bn_conv_taps_pad': (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
-    'bn_conv_taps_hint': (_c_int, [_c_void_p, _c_void_p]),
-    'bn_conv2d_fwd': (_c_int, [_c_void_p] * 4 + _CONV_GEOM + _ACT_WS),
+    'bn_conv2d_fwd': (_c_int, [_c_void_p] * 5 + _CONV_GEOM + _ACT_WS),
     'bn_conv2d_fwd_u8_ws_bytes': (_c_size_t, _CONV_GEOM + [_c_int]),
     'bn_conv2d_fwd_u8': (_c_int, [_c_void_p] * 4 + _CONV_GEOM + _ACT_WS),
-    'bn_conv2d_bwd_data': (_c_int, [_c_void_p] * 4 + _CONV_GEOM + _ACT_WS),
+    'bn_conv2d_bwd_data': (_c_int, [_c_void_p] * 5 + _CONV_GEOM + _ACT_WS),
     'bn_conv2d_bwd_weight': (
         _c_int, [_c_void_p] * 4 + _CONV_GEOM + [_c_int, _c_void_p, _c_size_t, _c_void_p]),
-    'bn_convT2d_fwd': (_c_int, [_c_void_p] * 4 + _CONV_GEOM + _ACT_WS),
-    'bn_convT2d_bwd_data': (_c_int, [_c_void_p] * 4 + _CONV_GEOM + _ACT_WS),
+    'bn_convT2d_fwd': (_c_int, [_c_void_p] * 5 + _CONV_GEOM + _ACT_WS),
+    'bn_convT2d_bwd_data': (_c_int, [_c_void_p] * 5 + _CONV_GEOM + _ACT_WS),
     'bn_convT2d_bwd_weight': (
         _c_int, [_c_void_p] * 4 + _CONV_GEOM + [_c_int, _c_void_p, _c_size_t, _c_void_p]),
     'bn_batchnorm_ws_bytes': (_c_size_t, [_c_int, _c_int]),
@@ -280,19 +279,13 @@ def conv_taps_pad(jobs, device):
     return out
 
 
-def _taps_hint(w, w5):
-    if w5 is not None:
-        load().bn_conv_taps_hint(w.data_ptr(), w5.data_ptr())
-
-
 def conv2d_fwd(x, w, b, geom, act, slope, w5=None):
     N, C, H, W, K, R, S, st, pt, pl, P, Q = geom
     y = torch.empty((N, K, P, Q), dtype=torch.float32, device=x.device)
     ws, nb = _workspace(OP_CONV_FWD, geom, x.device)
-    _taps_hint(w, w5)
     _check(load().bn_conv2d_fwd(
-        _ptr(x, 'x'), _ptr(w, 'w'), _ptr(b, 'b', allow_none=True), _ptr(y, 'y'), *geom,
-        act, slope, ws, nb, _stream()), 'bn_conv2d_fwd')
+        _ptr(x, 'x'), _ptr(w, 'w'), _ptr(w5, 'w5', allow_none=True), _ptr(b, 'b', allow_none=True), _ptr(y, 'y'),
+        *geom, act, slope, ws, nb, _stream()), 'bn_conv2d_fwd')
     return y
 
 
@@ -315,10 +308,9 @@ def conv2d_bwd_data(dy, w, geom, dact_src, dact, slope, w5=None):
     N, C, H, W = geom[:4]
     dx = torch.empty((N, C, H, W), dtype=torch.float32, device=dy.device)
     ws, nb = _workspace(OP_CONV_BWD_D, geom, dy.device)
-    _taps_hint(w, w5)
     _check(load().bn_conv2d_bwd_data(
-        _ptr(dy, 'dy'), _ptr(w, 'w'), _ptr(dx, 'dx'), _ptr(dact_src, 'dact_src', allow_none=True),
-        *geom, dact, slope, ws, nb, _stream()), 'bn_conv2d_bwd_data')
+        _ptr(dy, 'dy'), _ptr(w, 'w'), _ptr(w5, 'w5', allow_none=True), _ptr(dx, 'dx'),
+        _ptr(dact_src, 'dact_src', allow_none=True), *geom, dact, slope, ws, nb, _stream()), 'bn_conv2d_bwd_data')
     return dx
 
 
@@ -333,10 +325,9 @@ def convT2d_fwd(x, w, b, geom, act, slope, w5=None):
     N, Ci, Hi, Wi, Co, R, S, st, ct, cl, Ho, Wo = geom
     y = torch.empty((N, Co, Ho, Wo), dtype=torch.float32, device=x.device)
     ws, nb = _workspace(OP_CONVT_FWD, geom, x.device)
-    _taps_hint(w, w5)
     _check(load().bn_convT2d_fwd(
-        _ptr(x, 'x'), _ptr(w, 'w'), _ptr(b, 'b', allow_none=True), _ptr(y, 'y'), *geom,
-        act, slope, ws, nb, _stream()), 'bn_convT2d_fwd')
+        _ptr(x, 'x'), _ptr(w, 'w'), _ptr(w5, 'w5', allow_none=True), _ptr(b, 'b', allow_none=True), _ptr(y, 'y'),
+        *geom, act, slope, ws, nb, _stream()), 'bn_convT2d_fwd')
     return y
 
 
@@ -344,10 +335,9 @@ def convT2d_bwd_data(dy, w, geom, dact_src, dact, slope, w5=None):
     N, Ci, Hi, Wi = geom[:4]
     dx = torch.empty((N, Ci, Hi, Wi), dtype=torch.float32, device=dy.device)
     ws, nb = _workspace(OP_CONVT_BWD_D, geom, dy.device)
-    _taps_hint(w, w5)
     _check(load().bn_convT2d_bwd_data(
-        _ptr(dy, 'dy'), _ptr(w, 'w'), _ptr(dx, 'dx'), _ptr(dact_src, 'dact_src', allow_none=True),
-        *geom, dact, slope, ws, nb, _stream()), 'bn_convT2d_bwd_data')
+        _ptr(dy, 'dy'), _ptr(w, 'w'), _ptr(w5, 'w5', allow_none=True), _ptr(dx, 'dx'),
+        _ptr(dact_src, 'dact_src', allow_none=True), *geom, dact, slope, ws, nb, _stream()), 'bn_convT2d_bwd_data')
     return dx
 
 

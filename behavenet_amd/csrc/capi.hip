@@ -444,17 +444,6 @@ static bool taps_plan(int role, const BnGeom& g, BnGeom* g5) {
     return served_fast(role, *g5);
 }
 static inline size_t taps_bytes(const BnGeom& g) { return align256((size_t)g.Cs * g.Cb * 25 * sizeof(float)); }
-// One-shot hint (round 6, bn_conv_taps_hint): the caller already holds the 5x5 copy of `w` (bn_conv_taps_pad, one
-// launch for all the layers of a stack).  The next forward / data-gradient entry of THIS thread takes it if the
-// weight pointer matches and drops it otherwise -- a hint never outlives one call.
-static thread_local const float* g_taps_hint_w = nullptr;
-static thread_local const float* g_taps_hint_w5 = nullptr;
-struct TapsHintDrop { ~TapsHintDrop() { g_taps_hint_w = g_taps_hint_w5 = nullptr; } };   // every conv entry ends with no hint
-static const float* taps_hint_take(const float* w) {
-    const float* w5 = (w && g_taps_hint_w == w) ? g_taps_hint_w5 : nullptr;
-    g_taps_hint_w = g_taps_hint_w5 = nullptr;
-    return w5;
-}
 
 // ---- kernels larger than 5x5 with stride 2 (7x7, 9x9): conv_pad.hip, "Kernels LARGER than 5x5"
 struct BigK {
@@ -583,20 +572,20 @@ static bool flip_plan(const BnGeom& g, BnGeom* gf, BnFastPlan* inner) {
 }
 static inline size_t flip_bytes(const BnGeom& g) { return align256((size_t)g.Cs * g.Cb * g.R * g.S * sizeof(float)); }
 
-static int run_down(int family, const float* big, const float* w, const float* bias, float* out,
+// w5: the caller's 5x5 copy of `w` (bn_conv_taps_pad) or nullptr; every internal call passes nullptr
+static int run_down(int family, const float* big, const float* w, const float* w5, const float* bias, float* out,
                     const float* dact_src, const BnGeom& g, int act, int dact, float slope,
                     void* ws, size_t ws_bytes, hipStream_t st) {
     const bool generic = force_generic() || !aligned16_all(big, w, out, dact_src);
-    const float* w5 = taps_hint_take(w);
     BnGeom g5;
     if (!generic && w5 && aligned16_all(w5, w5, w5) && taps_plan(0, g, &g5))        // the caller's padded copy
-        return run_down(family, big, w5, bias, out, dact_src, g5, act, dact, slope, ws, ws_bytes, st);
+        return run_down(family, big, w5, nullptr, bias, out, dact_src, g5, act, dact, slope, ws, ws_bytes, st);
     if (!generic && taps_plan(0, g, &g5)) {
         const size_t wb = taps_bytes(g);
         if (!ws || ws_bytes < wb + role_ws_need(0, g5)) return BN_E_WORKSPACE;
         const int rc = bn_launch_pad_taps(w, (float*)ws, (size_t)g.Cs * g.Cb, g.R, g.S, st, taps_dr(g), taps_ds(g));
         if (rc) return rc;
-        return run_down(family, big, (const float*)ws, bias, out, dact_src, g5, act, dact, slope,
+        return run_down(family, big, (const float*)ws, nullptr, bias, out, dact_src, g5, act, dact, slope,
                         (char*)ws + wb, ws_bytes - wb, st);
     }
     if (!generic && bn_s1in1_ok(g)) {
@@ -619,7 +608,7 @@ static int run_down(int family, const float* big, const float* w, const float* b
         if (rc) return rc;
         rc = bn_launch_bigk_phase_pack(w, w1, g.Cs, g.Cb, g.R, g.S, bk.kr, bk.ofr, bk.kc, bk.ofc, 1, 0, st);
         if (rc) return rc;
-        return run_down(family, X, w1, bias, out, dact_src, g5, act, dact, slope, (char*)ws + xb + wb,
+        return run_down(family, X, w1, nullptr, bias, out, dact_src, g5, act, dact, slope, (char*)ws + xb + wb,
                         ws_bytes - xb - wb, st);
     }
     BigK1 b1;
@@ -627,8 +616,8 @@ static int run_down(int family, const float* big, const float* w, const float* b
         const size_t xb = bigk1_map_bytes(g, b1), wb = bigk_w_bytes(g), iw = bigk1_inner_ws(0, g, g5, b1);
         if (!ws || ws_bytes < xb + wb + iw) return BN_E_WORKSPACE;
         float* xcat = (float*)ws;
-        float* w5 = (float*)((char*)ws + xb);
-        int rc = bn_launch_bigk_pack(w, w5, g.Cs, g.Cb, g.R, g.S, b1.L0r, b1.L0c, st);
+        float* w1 = (float*)((char*)ws + xb);
+        int rc = bn_launch_bigk_pack(w, w1, g.Cs, g.Cb, g.R, g.S, b1.L0r, b1.L0c, st);
         if (rc) return rc;
         const size_t fb = (size_t)g.Cb * g.Hb * g.Wb, fs = (size_t)g.Cs * g.Hs * g.Ws;
         for (int n0 = 0; n0 < g.N; n0 += b1.nb) {
@@ -637,7 +626,7 @@ static int run_down(int family, const float* big, const float* w, const float* b
             rc = bn_launch_shift_cat(big + n0 * fb, xcat, gb.N, g.Cb, g.Hb, g.Wb, b1.Ho, b1.Wo, b1.dr[0], b1.dr[1],
                                      b1.dc[0], b1.dc[1], st);
             if (rc) return rc;
-            rc = run_down(family, xcat, w5, bias, out + n0 * fs, dact_src ? dact_src + n0 * fs : nullptr, gb, act,
+            rc = run_down(family, xcat, w1, nullptr, bias, out + n0 * fs, dact_src ? dact_src + n0 * fs : nullptr, gb, act,
                           dact, slope, (char*)ws + xb + wb, ws_bytes - xb - wb, st);
             if (rc) return rc;
         }
@@ -665,7 +654,7 @@ static int run_down(int family, const float* big, const float* w, const float* b
             return 0;
         }
         for (int c0 = 0; c0 < g.Cs; c0 += 32) {
-            int rc = run_down(family, big, w + (size_t)c0 * g.Cb * 25, bias ? bias + c0 : nullptr, (float*)ws,
+            int rc = run_down(family, big, w + (size_t)c0 * g.Cb * 25, nullptr, bias ? bias + c0 : nullptr, (float*)ws,
                               nullptr, g5, act, BN_ACT_NONE, slope, (char*)ws + cb, ws_bytes - cb, st);
             if (rc) return rc;
             rc = bn_launch_chan_copy((const float*)ws, out, g.N, 32, 0, g.Cs, c0, 32, PQ, dact_src, dact, slope, st);
@@ -758,20 +747,19 @@ static int run_down(int family, const float* big, const float* w, const float* b
     return bn_launch_down_generic(big, w, bias, out, dact_src, g, act, dact, slope, st);
 }
 
-static int run_up(int family, const float* small, const float* w, const float* bias, float* out,
+static int run_up(int family, const float* small, const float* w, const float* w5, const float* bias, float* out,
                   const float* dact_src, const BnGeom& g, int act, int dact, float slope,
                   void* ws, size_t ws_bytes, hipStream_t st) {
     const bool generic = force_generic() || !aligned16_all(small, w, out, dact_src);
-    const float* w5 = taps_hint_take(w);
     BnGeom g5;
     if (!generic && w5 && aligned16_all(w5, w5, w5) && taps_plan(1, g, &g5))        // the caller's padded copy
-        return run_up(family, small, w5, bias, out, dact_src, g5, act, dact, slope, ws, ws_bytes, st);
+        return run_up(family, small, w5, nullptr, bias, out, dact_src, g5, act, dact, slope, ws, ws_bytes, st);
     if (!generic && taps_plan(1, g, &g5)) {
         const size_t wb = taps_bytes(g);
         if (!ws || ws_bytes < wb + role_ws_need(1, g5)) return BN_E_WORKSPACE;
         const int rc = bn_launch_pad_taps(w, (float*)ws, (size_t)g.Cs * g.Cb, g.R, g.S, st, taps_dr(g), taps_ds(g));
         if (rc) return rc;
-        return run_up(family, small, (const float*)ws, bias, out, dact_src, g5, act, dact, slope,
+        return run_up(family, small, (const float*)ws, nullptr, bias, out, dact_src, g5, act, dact, slope,
                       (char*)ws + wb, ws_bytes - wb, st);
     }
     BigK bk;
@@ -782,7 +770,7 @@ static int run_up(int family, const float* small, const float* w, const float* b
         float* w1 = (float*)((char*)ws + yb);
         int rc = bn_launch_bigk_phase_pack(w, w1, g.Cs, g.Cb, g.R, g.S, bk.kr, bk.ofr, bk.kc, bk.ofc, -1, 1, st);
         if (rc) return rc;
-        rc = run_down(family, small, w1, nullptr, y, nullptr, g5, BN_ACT_NONE, BN_ACT_NONE, slope,
+        rc = run_down(family, small, w1, nullptr, nullptr, y, nullptr, g5, BN_ACT_NONE, BN_ACT_NONE, slope,
                       (char*)ws + yb + wb, ws_bytes - yb - wb, st);
         if (rc) return rc;
         return bn_launch_depth_to_space(y, out, bias, dact_src, g.N, g.Cb, bk.Hy, bk.Wy, act, dact, slope, st);
@@ -883,7 +871,7 @@ static int run_up(int family, const float* small, const float* w, const float* b
             if (!ws || ws_bytes < fb + role_ws_need(0, gf)) return BN_E_WORKSPACE;
             const int rc = bn_launch_flip_taps(w, (float*)ws, g.Cs, g.Cb, g.R * g.S, st);
             if (rc) return rc;
-            return run_down(family, small, (const float*)ws, bias, out, dact_src, gf, act, dact, slope,
+            return run_down(family, small, (const float*)ws, nullptr, bias, out, dact_src, gf, act, dact, slope,
                             (char*)ws + fb, ws_bytes - fb, st);
         }
     }
@@ -1226,23 +1214,14 @@ extern "C" int bn_conv_taps_pad(int n, const float* const* w, float* const* w5, 
     return 0;
 }
 
-// One-shot: the next forward / data-gradient call of this thread on weights `w` reads their 5x5 copy from `w5`
-// (written by bn_conv_taps_pad for the same layer) instead of padding them again; any other call drops the hint.
-extern "C" int bn_conv_taps_hint(const float* w, const float* w5) {
-    g_taps_hint_w = w5 ? w : nullptr;
-    g_taps_hint_w5 = w ? w5 : nullptr;
-    return 0;
-}
-
-extern "C" int bn_conv2d_fwd(const float* x, const float* w, const float* b, float* y, int N,
+extern "C" int bn_conv2d_fwd(const float* x, const float* w, const float* w5, const float* b, float* y, int N,
                              int C, int H, int W, int K, int R, int S, int stride, int pad_t,
                              int pad_l, int P, int Q, int act, float slope, void* ws,
                              size_t ws_bytes, bn_stream_t stream) {
-    TapsHintDrop hint_drop;
     if (!x || !w || !y) return BN_E_BADARG;
     const BnGeom g = conv_geom(N, C, H, W, K, R, S, stride, pad_t, pad_l, P, Q);
     if (!bn_geom_ok(g)) return BN_E_BADARG;
-    return run_down(BN_PROF_CONV_FWD, x, w, b, y, nullptr, g, act, BN_ACT_NONE, slope, ws,
+    return run_down(BN_PROF_CONV_FWD, x, w, w5, b, y, nullptr, g, act, BN_ACT_NONE, slope, ws,
                     ws_bytes, (hipStream_t)stream);
 }
 
@@ -1253,7 +1232,6 @@ extern "C" int bn_conv2d_fwd(const float* x, const float* w, const float* b, flo
 extern "C" int bn_conv2d_pool2_act_fwd(const float* x, const float* w, const float* b, float* y, int* idx, int N,
                                        int C, int H, int W, int K, int R, int S, int stride, int pad_t, int pad_l,
                                        int P, int Q, int act, float slope, bn_stream_t stream) {
-    TapsHintDrop hint_drop;
     if (!x || !w || !y || !idx) return BN_E_BADARG;
     const BnGeom g = conv_geom(N, C, H, W, K, R, S, stride, pad_t, pad_l, P, Q);
     if (!bn_geom_ok(g)) return BN_E_BADARG;
@@ -1292,7 +1270,6 @@ extern "C" int bn_conv2d_pool2_bwd_weight(const float* x, const float* dy, const
                                           float* db, int N, int C, int H, int W, int K, int R, int S, int stride,
                                           int pad_t, int pad_l, int P, int Q, int act, float slope, int accumulate,
                                           void* ws, size_t ws_bytes, bn_stream_t stream) {
-    TapsHintDrop hint_drop;
     if (!x || !dy || !y || !idx || !dw) return BN_E_BADARG;
     const BnGeom g = conv_geom(N, C, H, W, K, R, S, stride, pad_t, pad_l, P, Q);
     if (!bn_geom_ok(g)) return BN_E_BADARG;
@@ -1323,7 +1300,6 @@ extern "C" int bn_conv2d_fwd_u8(const unsigned char* x, const float* w, const fl
                                 int N, int C, int H, int W, int K, int R, int S, int stride,
                                 int pad_t, int pad_l, int P, int Q, int act, float slope, void* ws,
                                 size_t ws_bytes, bn_stream_t stream) {
-    TapsHintDrop hint_drop;
     if (!x || !w || !y) return BN_E_BADARG;
     const BnGeom g = conv_geom(N, C, H, W, K, R, S, stride, pad_t, pad_l, P, Q);
     if (!bn_geom_ok(g)) return BN_E_BADARG;
@@ -1340,19 +1316,18 @@ extern "C" int bn_conv2d_fwd_u8(const unsigned char* x, const float* w, const fl
     float* xf = (float*)((char*)ws + conv_ws);
     int rc = bn_launch_u8_to_unit_float(x, xf, n_in, st);
     if (rc) return rc;
-    return run_down(BN_PROF_CONV_FWD, xf, w, b, y, nullptr, g, act, BN_ACT_NONE, slope, ws, conv_ws,
+    return run_down(BN_PROF_CONV_FWD, xf, w, nullptr, b, y, nullptr, g, act, BN_ACT_NONE, slope, ws, conv_ws,
                     st);
 }
 
-extern "C" int bn_conv2d_bwd_data(const float* dy, const float* w, float* dx,
+extern "C" int bn_conv2d_bwd_data(const float* dy, const float* w, const float* w5, float* dx,
                                   const float* dact_src, int N, int C, int H, int W, int K, int R,
                                   int S, int stride, int pad_t, int pad_l, int P, int Q, int dact,
                                   float slope, void* ws, size_t ws_bytes, bn_stream_t stream) {
-    TapsHintDrop hint_drop;
     if (!dy || !w || !dx) return BN_E_BADARG;
     const BnGeom g = conv_geom(N, C, H, W, K, R, S, stride, pad_t, pad_l, P, Q);
     if (!bn_geom_ok(g)) return BN_E_BADARG;
-    return run_up(BN_PROF_CONV_BWD_D, dy, w, nullptr, dx, dact_src, g, BN_ACT_NONE, dact, slope,
+    return run_up(BN_PROF_CONV_BWD_D, dy, w, w5, nullptr, dx, dact_src, g, BN_ACT_NONE, dact, slope,
                   ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -1360,7 +1335,6 @@ extern "C" int bn_conv2d_bwd_weight(const float* x, const float* dy, float* dw, 
                                     int C, int H, int W, int K, int R, int S, int stride,
                                     int pad_t, int pad_l, int P, int Q, int accumulate, void* ws,
                                     size_t ws_bytes, bn_stream_t stream) {
-    TapsHintDrop hint_drop;
     if (!x || !dy || !dw) return BN_E_BADARG;
     const BnGeom g = conv_geom(N, C, H, W, K, R, S, stride, pad_t, pad_l, P, Q);
     if (!bn_geom_ok(g)) return BN_E_BADARG;
@@ -1374,28 +1348,26 @@ extern "C" int bn_conv2d_bwd_weight(const float* x, const float* dy, float* dw, 
     return rc;
 }
 
-extern "C" int bn_convT2d_fwd(const float* x, const float* w, const float* b, float* y, int N,
+extern "C" int bn_convT2d_fwd(const float* x, const float* w, const float* w5, const float* b, float* y, int N,
                               int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
                               int crop_t, int crop_l, int Ho, int Wo, int act, float slope,
                               void* ws, size_t ws_bytes, bn_stream_t stream) {
-    TapsHintDrop hint_drop;
     if (!x || !w || !y) return BN_E_BADARG;
     const BnGeom g = convT_geom(N, Ci, Hi, Wi, Co, R, S, stride, crop_t, crop_l, Ho, Wo);
     if (!bn_geom_ok(g)) return BN_E_BADARG;
-    return run_up(BN_PROF_CONVT_FWD, x, w, b, y, nullptr, g, act, BN_ACT_NONE, slope, ws,
+    return run_up(BN_PROF_CONVT_FWD, x, w, w5, b, y, nullptr, g, act, BN_ACT_NONE, slope, ws,
                   ws_bytes, (hipStream_t)stream);
 }
 
-extern "C" int bn_convT2d_bwd_data(const float* dy, const float* w, float* dx,
+extern "C" int bn_convT2d_bwd_data(const float* dy, const float* w, const float* w5, float* dx,
                                    const float* dact_src, int N, int Ci, int Hi, int Wi, int Co,
                                    int R, int S, int stride, int crop_t, int crop_l, int Ho,
                                    int Wo, int dact, float slope, void* ws, size_t ws_bytes,
                                    bn_stream_t stream) {
-    TapsHintDrop hint_drop;
     if (!dy || !w || !dx) return BN_E_BADARG;
     const BnGeom g = convT_geom(N, Ci, Hi, Wi, Co, R, S, stride, crop_t, crop_l, Ho, Wo);
     if (!bn_geom_ok(g)) return BN_E_BADARG;
-    return run_down(BN_PROF_CONVT_BWD_D, dy, w, nullptr, dx, dact_src, g, BN_ACT_NONE, dact, slope,
+    return run_down(BN_PROF_CONVT_BWD_D, dy, w, w5, nullptr, dx, dact_src, g, BN_ACT_NONE, dact, slope,
                     ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -1403,7 +1375,6 @@ extern "C" int bn_convT2d_bwd_weight(const float* x, const float* dy, float* dw,
                                      int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
                                      int crop_t, int crop_l, int Ho, int Wo, int accumulate,
                                      void* ws, size_t ws_bytes, bn_stream_t stream) {
-    TapsHintDrop hint_drop;
     if (!x || !dy || !dw) return BN_E_BADARG;
     const BnGeom g = convT_geom(N, Ci, Hi, Wi, Co, R, S, stride, crop_t, crop_l, Ho, Wo);
     if (!bn_geom_ok(g)) return BN_E_BADARG;
@@ -1682,7 +1653,6 @@ extern "C" int bn_convT2d_fwd_sqerr(const float* x, const float* w, const float*
                                     int Co, int R, int S, int stride, int crop_t, int crop_l,
                                     int Ho, int Wo, int act, float slope, void* ws,
                                     size_t ws_bytes, bn_stream_t stream) {
-    TapsHintDrop hint_drop;
     if (!x || !w || !target || !dpre || !part) return BN_E_BADARG;
     const BnGeom g = convT_geom(N, Ci, Hi, Wi, Co, R, S, stride, crop_t, crop_l, Ho, Wo);
     if (!bn_geom_ok(g)) return BN_E_BADARG;
@@ -1697,7 +1667,7 @@ extern "C" int bn_convT2d_fwd_sqerr(const float* x, const float* w, const float*
     const size_t n_out = (size_t)N * Co * Ho * Wo;
     const size_t conv_ws = need - (xhat ? 0 : n_out * sizeof(float));
     float* xh = xhat ? xhat : (float*)((char*)ws + conv_ws);
-    int rc = run_up(BN_PROF_CONVT_FWD, x, w, b, xh, nullptr, g, act, BN_ACT_NONE, slope, ws,
+    int rc = run_up(BN_PROF_CONVT_FWD, x, w, nullptr, b, xh, nullptr, g, act, BN_ACT_NONE, slope, ws,
                     conv_ws, st);
     if (rc) return rc;
     rc = bn_launch_sqerr_frame_sums(xh, target, mask, part, N, (size_t)Co * Ho * Wo, st);

@@ -138,7 +138,7 @@ int bn_launch_pad_taps(const float* w, float* w5, size_t pairs, int R, int S, hi
     return 0;
 }
 // the same for several layers in ONE launch (round 6): a fused conv stack pads the taps of all its small-kernel layers
-// when its forward pass starts and hands the copies to the forward and data-gradient entry points (bn_conv_taps_hint);
+// when its forward pass starts and hands the copies to the forward and data-gradient entry points (their w5 argument);
 // k_pad_taps ran once per layer and role, 19 launches of 5-6 us in a step of ae_arch_2.json
 __global__ __launch_bounds__(PD_THREADS) void k_pad_taps_jobs(BnPadTapsJobs p) {
     int b = blockIdx.x;

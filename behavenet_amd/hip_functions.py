@@ -46,14 +46,6 @@ class accumulate_into_param_grads(object):
         return False
 
 
-# Single-pass schedule only (ONE backward per step): number of bottom layers of the LAST stack in
-# the backward order (the encoder) whose weight gradients are issued on the main stream, after
-# its data-gradient chain, instead of on the side stream.  The side stream lags the main one, so
-# without this the last ~0.6 ms of a step run one weight-gradient kernel at a time.
-_tail_on_main = 0
-_TAIL_LAYERS = int(os.environ.get('BN_WGRAD_TAIL', '2'))
-_SINGLE_PASS_SIDE = os.environ.get('BN_SINGLE_PASS_SIDE', '0') == '1'
-
 # Data-parallel runs: fitting/distributed.BucketedGradReducer asks to be told when the kernels
 # that complete a parameter's gradient have been issued, so that it can start that bucket's
 # all-reduce under the rest of the backward pass.  Reported only in the single-pass schedule (one
@@ -117,14 +109,13 @@ def backward_chunks(chunk_losses, streams=None, single_pass=False):
     stream idle and the tail of chunk c's weight gradients overlaps the head of chunk c+1's data
     gradients.
     """
-    global _tail_on_main, _single_pass, _use_side_stream
+    global _single_pass, _use_side_stream
     _single_pass = bool(single_pass and len(chunk_losses) == 1)
-    _tail_on_main = _TAIL_LAYERS if _single_pass else 0
     # single-pass schedule: every kernel sees the whole batch and fills the chip on its own; a
     # second stream of weight-gradient kernels then only competes for LDS and wave slots (5.45 ->
-    # 5.43 ms for the AE, 6.39 -> 6.19 ms for the PS-VAE).  BN_SINGLE_PASS_SIDE=1 keeps it.
+    # 5.43 ms for the AE, 6.39 -> 6.19 ms for the PS-VAE), so it runs without the side stream.
     saved_side = _use_side_stream
-    if _single_pass and not _SINGLE_PASS_SIDE:
+    if _single_pass:
         _use_side_stream = False
     try:
         with accumulate_into_param_grads():
@@ -142,7 +133,6 @@ def backward_chunks(chunk_losses, streams=None, single_pass=False):
                 else:
                     loss.backward(seed)
     finally:
-        _tail_on_main = 0
         _single_pass = False
         _use_side_stream = saved_side
 
@@ -456,7 +446,6 @@ def _fwd(layer, x, w, b, w5=None):
     return _hip.convT2d_fwd(x, w, b, g, layer.act, LRELU_SLOPE, w5=w5)
 
 
-_STACK_TAPS = os.environ.get('BN_STACK_TAPS', '1') != '0'      # 0: every entry point pads for itself (A/B switch)
 _FWD_OP = {'conv': _hip.OP_CONV_FWD, 'convT': _hip.OP_CONVT_FWD}
 _BWD_OP = {'conv': _hip.OP_CONV_BWD_D, 'convT': _hip.OP_CONVT_BWD_D}
 
@@ -467,8 +456,6 @@ def _stack_taps(plan, n, params, first=0):
     the data gradient of every such layer, 19 launches in a step of ae_arch_2.json; a stack makes the copies of ALL
     its layers in one launch when its forward pass starts and keeps them for its backward pass (same weights: the
     node's saved tensors).  -> [w5 | None] per layer, None for a stack without such layers."""
-    if not _STACK_TAPS:
-        return None
     jobs, idx = [], []
     for i in range(first, len(plan)):
         layer = plan[i]
@@ -496,6 +483,12 @@ def first_layer_forward(plan, x, params):
 _sign_tap = None
 
 
+def _note_signs(plan, i, h):
+    """File the signs of ``h``, the output of layer ``i``, under ``plan`` if that layer ends in a LeakyReLU."""
+    if _sign_tap is not None and plan[i].act == _hip.ACT_LRELU:
+        _sign_tap.setdefault(id(plan), [[] for _ in plan])[i].append((h.detach() > 0).cpu())
+
+
 class ConvStackFn(torch.autograd.Function):
     """y = layer_L(...layer_1(x)); params = (w_1, b_1, ..., w_L, b_L).
 
@@ -521,11 +514,8 @@ class ConvStackFn(torch.autograd.Function):
                 h = _fwd(layer, h, params[2 * i].detach(), params[2 * i + 1].detach(),
                          w5=taps[i] if taps else None)
             acts.append(h)
-        if _sign_tap is not None:
-            rec = _sign_tap.setdefault(id(plan), [[] for _ in plan])
-            for i, layer in enumerate(plan):
-                if layer.act == _hip.ACT_LRELU:
-                    rec[i].append((acts[i + 1] > 0).cpu())
+        for i in range(len(plan)):
+            _note_signs(plan, i, acts[i + 1])
         ctx.plan = plan
         ctx.taps = taps
         ctx.need_dx = x.requires_grad
@@ -547,9 +537,6 @@ class ConvStackFn(torch.autograd.Function):
         return (None, dx, None) + tuple(grads)
 
 
-_DGRAD_FIRST = os.environ.get('BN_DGRAD_FIRST', '0') == '1'
-
-
 def _stack_backward(ctx, dpre, first_param):
     """Backward pass of a fused conv stack from ``dpre`` = dL/d(pre-activation of the top layer):
     per layer the weight (+bias) gradient, then the data gradient with the activation derivative
@@ -562,7 +549,6 @@ def _stack_backward(ctx, dpre, first_param):
     n = dpre.shape[0]
     grads = [None] * (2 * n_layers)
     taps = getattr(ctx, 'taps', None)       # the forward pass's 5x5 copies of small-kernel taps (_stack_taps)
-    tail = []     # weight gradients deferred to the main stream (see _tail_on_main)
     for i in range(n_layers - 1, -1, -1):
         layer = plan[i]
         g = layer.geom(n)
@@ -575,17 +561,6 @@ def _stack_backward(ctx, dpre, first_param):
                 if ctx.needs_input_grad[first_param + 2 * i] else None
         need_w = ctx.needs_input_grad[first_param + 2 * i]
         need_b = ctx.needs_input_grad[first_param + 1 + 2 * i]
-        # BN_DGRAD_FIRST=1: data gradient FIRST when the layer below is a single-channel edge layer,
-        # so that this layer's matrix-bound weight gradient runs between the 134 MB of (non-temporal)
-        # data-gradient writes and the HBM-bound weight gradient that reads them back.  Measured
-        # (round 4, one box): no difference (35.2 against 35.1 us for enc.conv0's weight gradient,
-        # step 4.330 against 4.337 ms); that kernel takes 35 us on some boxes and 41 on others in
-        # either order.  Off by default.
-        dpre_below = None
-        if i > 0 and min(plan[i - 1].cin, plan[i - 1].cout) <= 4 and _DGRAD_FIRST:
-            dact_src, dact = acts[i], plan[i - 1].act
-            bwd_data = _hip.conv2d_bwd_data if layer.kind == 'conv' else _hip.convT2d_bwd_data
-            dpre_below = bwd_data(dpre, w, g, dact_src, dact, LRELU_SLOPE, w5=taps[i] if taps else None)
         if need_w:
             gw = _grad_buffer(ctx.param_refs[2 * i])
             gb = _grad_buffer(ctx.param_refs[2 * i + 1]) if need_b else None
@@ -598,9 +573,7 @@ def _stack_backward(ctx, dpre, first_param):
                     else None
             wgrad = _hip.conv2d_bwd_weight if layer.kind == 'conv' else _hip.convT2d_bwd_weight
             side = _side_stream(w.device) if (direct and _use_side_stream) else None
-            if side is not None and not ctx.need_dx and i < _tail_on_main:
-                tail.append(((wgrad, x_in, dpre, dw, db, g), ctx.param_refs[2 * i:2 * i + 2]))
-            elif side is not None:
+            if side is not None:
                 # weight gradients go to a second HIP stream: they only depend on dpre and the
                 # saved input, while the main stream continues down the data-gradient chain;
                 # the tail of one kernel is filled by workgroups of the other.  Gradients
@@ -620,9 +593,7 @@ def _stack_backward(ctx, dpre, first_param):
                     _report_ready(ctx.param_refs[2 * i:2 * i + 2])
             if not direct:
                 grads[2 * i], grads[2 * i + 1] = dw, db
-        if dpre_below is not None:
-            dpre = dpre_below
-        elif i > 0 or ctx.need_dx:
+        if i > 0 or ctx.need_dx:
             # fuse the derivative of the layer below into this kernel's epilogue
             dact_src = acts[i] if i > 0 else None
             dact = plan[i - 1].act if i > 0 else _hip.ACT_NONE
@@ -631,9 +602,6 @@ def _stack_backward(ctx, dpre, first_param):
                 dpre = _hip.conv2d_bwd_data(dpre, w, g, dact_src, dact, LRELU_SLOPE, w5=w5)
             else:
                 dpre = _hip.convT2d_bwd_data(dpre, w, g, dact_src, dact, LRELU_SLOPE, w5=w5)
-    for (wgrad, x_in, dy, dw, db, g), refs in tail:
-        wgrad(x_in, dy, dw, db, g, True)
-        _report_ready(refs)
     return (dpre if ctx.need_dx else None), grads
 
 
@@ -941,11 +909,8 @@ class ConvStackSqErrFn(torch.autograd.Function):
         xhat, dpre, part = _hip.convT2d_fwd_sqerr(
             h, params[-2].detach(), params[-1].detach(), target, mask, top.geom(n), top.act,
             LRELU_SLOPE, bool(want_xhat))
-        if _sign_tap is not None:
-            rec = _sign_tap.setdefault(id(plan), [[] for _ in plan])
-            for i, layer in enumerate(plan[:-1]):
-                if layer.act == _hip.ACT_LRELU:
-                    rec[i].append((acts[i + 1] > 0).cpu())
+        for i in range(len(plan) - 1):
+            _note_signs(plan, i, acts[i + 1])
         out = torch.empty((len(bounds),), dtype=torch.float32, device=x.device)
         for c, ((beg, end), sc) in enumerate(zip(bounds, scales)):
             _hip.reduce_sum(part[beg:end], float(sc), out=out[c:c + 1])
@@ -1241,8 +1206,7 @@ def conv_stack_bn(plan, x, params, bn_modules):
         h = ConvStackFn.apply(run_plan, h, None, *run_params)
         bn = bn_modules[i]
         h = BatchNormActFn.apply(h, bn.weight, bn.bias, bn, layer.act)
-        if _sign_tap is not None and layer.act == _hip.ACT_LRELU:
-            _sign_tap.setdefault(id(plan), [[] for _ in plan])[i].append((h.detach() > 0).cpu())
+        _note_signs(plan, i, h)
         run_plan, run_params = [], []
     if run_plan:
         h = ConvStackFn.apply(run_plan, h, None, *run_params)
@@ -1530,7 +1494,7 @@ class ConvPoolActFn(torch.autograd.Function):
         layer = ctx.plan[0]
         g = layer.geom(dy.shape[0])
         need_w, need_b = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
-        if (_CONV_POOL_WGRAD and not ctx.need_dx and need_w and x.dtype == torch.float32 and
+        if (not ctx.need_dx and need_w and x.dtype == torch.float32 and
                 _hip.conv2d_pool_bwd_weight_ws_bytes(g)):
             # the first layer: no data gradient, and its weight gradient needs the winners only -- straight from the
             # pooled gradient (the dense one, 3/4 zeros, is never built: bn_conv2d_pool2_bwd_weight)
@@ -1552,14 +1516,10 @@ class ConvPoolActFn(torch.autograd.Function):
         return (None, dx, None) + tuple(grads)
 
 
-_CONV_POOL = os.environ.get('BN_CONV_POOL', '1') != '0'      # 0: convolve, then pool (A/B switch)
-_CONV_POOL_WGRAD = os.environ.get('BN_CONV_POOL_WGRAD', '1') != '0'      # 0: dense gradient, then the layer's weight gradient
-
-
 def conv_pool_act(layer, x, params, k, stride, pad, out_hw, act):
     """``max_pool_act(conv_stack([layer], x, params), ...)`` in one kernel where bn_conv2d_pool2_act_fwd serves the layer
     (bn_conv2d_pool2_act_ok; pooling 2x2 / stride 2 / unpadded on an even map) -> (y, idx), else None."""
-    if not (_CONV_POOL and x.is_cuda and layer.kind == 'conv' and layer.act == _hip.ACT_NONE and int(k) == 2 and
+    if not (x.is_cuda and layer.kind == 'conv' and layer.act == _hip.ACT_NONE and int(k) == 2 and
             int(stride) == 2 and int(pad[0]) == 0 and int(pad[1]) == 0 and layer.hout == 2 * int(out_hw[0]) and
             layer.wout == 2 * int(out_hw[1]) and layer.wout % 4 == 0 and x.dtype == torch.float32 and
             x.data_ptr() % 16 == 0 and params[0].data_ptr() % 16 == 0 and

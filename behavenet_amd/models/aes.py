@@ -25,7 +25,7 @@ from behavenet_amd.hip_functions import (
     stack_unserved_reason_bf16_dec, warn_bf16_unserved_dec,
     chunked_sq_err, conv_stack, conv_stack_bn, conv_stack_sq_err, first_layer_forward,
     join_side_streams, linear, begin_chunks, chunk_stream, max_pool, max_pool_act, max_unpool, conv_pool_act,
-    pixel_loss_scales, reserve_device_pools)
+    pixel_loss_scales, reserve_device_pools, _note_signs)
 
 __all__ = [
     'ConvAEEncoder', 'ConvAEDecoder', 'LinearAEEncoder', 'LinearAEDecoder', 'AE', 'ConditionalAE',
@@ -73,15 +73,6 @@ def _bn_modules(container, layer_names):
         num = ''.join(ch for ch in name.split('_')[0] if ch.isdigit())
         out.append(getattr(container, 'batchnorm%s' % num, None))
     return out
-
-
-
-def _tap_signs(plan, j, layer, h):
-    """Tests only (tests/branches.py): the layer-by-layer paths of max-pooling architectures run every layer as
-    its own one-layer stack, so the LeakyReLU signs are filed under the module's plan here."""
-    from behavenet_amd import hip_functions as hf
-    if hf._sign_tap is not None and layer.act == _hip.ACT_LRELU:
-        hf._sign_tap.setdefault(id(plan), [[] for _ in plan])[j].append((h.detach() > 0).cpu())
 
 
 class ConvAEEncoder(BaseModule):
@@ -258,7 +249,7 @@ class ConvAEEncoder(BaseModule):
                 sizes.append(torch.Size((h.size(0), layer.cout, layer.hout, layer.wout)))
                 h, idx = fused
                 pool_idx.append(idx)
-                _tap_signs(self._plan, j, layer, h)
+                _note_signs(self._plan, j, h)
                 continue
             if bns[j] is not None:
                 h = conv_stack_bn(one, h, params[2 * j:2 * j + 2], [bns[j]])
@@ -269,7 +260,9 @@ class ConvAEEncoder(BaseModule):
                 sizes.append(h.size())
                 h, idx = max_pool_act(h, k, stride, pad, out_hw, _hip.ACT_LRELU)
                 pool_idx.append(idx)
-            _tap_signs(self._plan, j, layer, h)
+            # (tests/branches.py: every layer ran as its own one-layer stack, so its LeakyReLU signs are filed
+            # under the module's plan here)
+            _note_signs(self._plan, j, h)
         self._pool_state = (pool_idx, sizes)
         return h.reshape(h.size(0), -1)
 
@@ -506,7 +499,7 @@ class ConvAEDecoder(BaseModule):
                     h = conv_stack_bn([layer], h, params[2 * j:2 * j + 2], [bns[j]])
                 else:
                     h = conv_stack([layer], h, params[2 * j:2 * j + 2])
-                _tap_signs(self._plan, j, layer, h)
+                _note_signs(self._plan, j, h)
         elif hp['ae_batch_norm']:
             h = conv_stack_bn(self._plan, h, params, _bn_modules(self.decoder, self._layer_names))
         else:

@@ -76,28 +76,31 @@ size_t bn_set_bigk1_block_bytes(size_t bytes);
 size_t bn_conv_ws_bytes(int op, int N, int C, int H, int W, int K, int R, int S, int stride,
                         int off_t, int off_l, int P, int Q);
 /* Kernels smaller than 5x5 (the reference's architecture search draws 3x3; configs/ae_jsons/ae_arch_2.json has 4x4:
- * /root/reference/behavenet/models/ae_model_architecture_generator.py:90-100) run on the 5x5 kernel families with
+ * models/ae_model_architecture_generator.py:90-100 of the reference) run on the 5x5 kernel families with
  * their taps embedded in 5x5 ones.  Every forward / data-gradient entry point makes that copy itself; a caller that
  * runs a whole stack of layers (and both roles of each) can make the copies of all layers in ONE launch instead:
  *   bn_conv_taps_bytes  bytes of the 5x5 copy if `op` (BN_OP_CONV_FWD / _BWD_D, BN_OP_CONVT_FWD / _BWD_D) pads this
  *                       geometry's taps, 0 if it does not (the copy is the same for the two ops of a layer)
  *   bn_conv_taps_pad    w5[j] <- 5x5 copy of w[j], j < n, one launch; geoms = n x 13 ints (op + the twelve geometry
  *                       arguments); BN_E_SHAPE if an op does not pad
- *   bn_conv_taps_hint   one-shot: the NEXT conv entry point called by this thread reads the 5x5 copy of `w` from `w5`
- *                       if it is called on weights `w` (and pads for itself otherwise); every conv entry point
- *                       clears the hint on return.  w5 = NULL clears it. */
+ * The four forward / data-gradient entry points then take that copy as `w5`, directly after `w`.  w5 = NULL: the
+ * call pads for itself.  A copy is read only where the call is not on the shape-agnostic path (bn_set_force_generic,
+ * operands off 16 bytes), `w5` is 16-byte aligned and the op pads this geometry's taps (bn_conv_taps_bytes != 0);
+ * anywhere else -- any 5x5 layer, say -- it is ignored, which is not an error.  Nothing is kept between calls.
+ * The caller's one obligation: `w5` was made by bn_conv_taps_pad from the CURRENT contents of `w`, for this geometry
+ * and this role pair, and is made again after every update of `w` -- in-place updates that no version counter sees
+ * (a flat-arena Adam step) included.  The library cannot check this and does not try. */
 size_t bn_conv_taps_bytes(int op, int N, int C, int H, int W, int K, int R, int S, int stride,
                           int off_t, int off_l, int P, int Q);
 int bn_conv_taps_pad(int n, const float* const* w, float* const* w5, const int* geoms, bn_stream_t stream);
-int bn_conv_taps_hint(const float* w, const float* w5);
 
 /* ------------------------------------------------------------------------------------------
  * Convolution (replaces ZeroPad2d + nn.Conv2d + LeakyReLU, aes.py:81-86,113-114,145-155).
  *   y[n,k,p,q] = act( b[k] + sum_{c,r,s} x[n,c,p*stride+r-pad_t,q*stride+s-pad_l] * w[k,c,r,s] )
  * reads outside [0,H)x[0,W) are zero, so TF-"same" asymmetric padding needs no padded copy.
- * x:(N,C,H,W) w:(K,C,R,S) b:(K) or NULL  y:(N,K,P,Q)
+ * x:(N,C,H,W) w:(K,C,R,S) w5: NULL or the 5x5 copy of w (above)  b:(K) or NULL  y:(N,K,P,Q)
  * ------------------------------------------------------------------------------------------ */
-int bn_conv2d_fwd(const float* x, const float* w, const float* b, float* y,
+int bn_conv2d_fwd(const float* x, const float* w, const float* w5, const float* b, float* y,
                   int N, int C, int H, int W, int K, int R, int S, int stride,
                   int pad_t, int pad_l, int P, int Q,
                   int act, float slope, void* ws, size_t ws_bytes, bn_stream_t stream);
@@ -107,7 +110,7 @@ int bn_conv2d_fwd(const float* x, const float* w, const float* b, float* y,
  * `dact_src` (nullable) is the saved post-activation input of this layer (= output of the layer
  * below); when given, the derivative of the lower layer's activation `dact` is applied in the
  * epilogue so dx is the lower layer's pre-activation gradient (autograd of aes.py:203-211). */
-int bn_conv2d_bwd_data(const float* dy, const float* w, float* dx, const float* dact_src,
+int bn_conv2d_bwd_data(const float* dy, const float* w, const float* w5, float* dx, const float* dact_src,
                        int N, int C, int H, int W, int K, int R, int S, int stride,
                        int pad_t, int pad_l, int P, int Q,
                        int dact, float slope, void* ws, size_t ws_bytes, bn_stream_t stream);
@@ -125,15 +128,15 @@ int bn_conv2d_bwd_weight(const float* x, const float* dy, float* dw, float* db,
  * into the output index range; the un-cropped tensor is never materialised:
  *   y[n,co,h,w] = act( b[co] + sum_{ci,r,s} x[n,ci,p,q] * w[ci,co,r,s] ),
  *   p*stride + r == h + crop_t,  q*stride + s == w + crop_l,  0<=h<Ho, 0<=w<Wo.
- * x:(N,Ci,Hi,Wi) w:(Ci,Co,R,S) b:(Co) or NULL  y:(N,Co,Ho,Wo)
+ * x:(N,Ci,Hi,Wi) w:(Ci,Co,R,S) w5: NULL or the 5x5 copy of w  b:(Co) or NULL  y:(N,Co,Ho,Wo)
  * ------------------------------------------------------------------------------------------ */
-int bn_convT2d_fwd(const float* x, const float* w, const float* b, float* y,
+int bn_convT2d_fwd(const float* x, const float* w, const float* w5, const float* b, float* y,
                    int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
                    int crop_t, int crop_l, int Ho, int Wo,
                    int act, float slope, void* ws, size_t ws_bytes, bn_stream_t stream);
 
 /* dx[n,ci,p,q] = act'(dact_src[n,ci,p,q]) * sum_{co,r,s} dy[n,co,p*stride+r-crop_t,...] * w[ci,co,r,s] */
-int bn_convT2d_bwd_data(const float* dy, const float* w, float* dx, const float* dact_src,
+int bn_convT2d_bwd_data(const float* dy, const float* w, const float* w5, float* dx, const float* dact_src,
                         int N, int Ci, int Hi, int Wi, int Co, int R, int S, int stride,
                         int crop_t, int crop_l, int Ho, int Wo,
                         int dact, float slope, void* ws, size_t ws_bytes, bn_stream_t stream);

@@ -31,6 +31,11 @@ def test_every_declared_symbol_is_exported_and_bound():
         assert hasattr(lib, n), 'header declares %s but the .so does not export it' % n
     # the ctypes table covers the header one to one
     assert sorted(_hip.SIGNATURES.keys()) == names
+    # ... and the .so exports nothing of the ABI's prefix that the header does not declare (a retired entry point is
+    # gone from all three): candidates are the NUL-terminated bn_* strings of the file, dlsym says which are exports
+    with open(_hip.lib_path(), 'rb') as f:
+        found = set(m.decode() for m in re.findall(rb'\x00(bn_[A-Za-z0-9_]+)(?=\x00)', f.read()))
+    assert sorted(n for n in found if hasattr(lib, n)) == names
 
 
 def test_info_calls():
@@ -39,7 +44,7 @@ def test_info_calls():
     assert lib.bn_build_arch() == b'gfx950'
     assert b'BN_E_SHAPE' in lib.bn_error_string(-2)
     # argument errors are reported, not thrown
-    assert lib.bn_conv2d_fwd(None, None, None, None, *([1] * 12), 0, 0.0, None, 0, None) == -1
+    assert lib.bn_conv2d_fwd(None, None, None, None, None, *([1] * 12), 0, 0.0, None, 0, None) == -1
     assert lib.bn_conv_ws_bytes(99, *([1] * 12)) == 0
     assert lib.bn_prof_select(99, 0, 0) == -1
 

@@ -27,26 +27,32 @@ def _cases(seed, count):
 @pytest.mark.skipif(torch.cuda.is_available(), reason='launches real kernels on dummy pointers when a GPU is present')
 def test_every_role_of_a_geometry_sweep_reaches_a_launch():
     lib = _hip.load()
-    buf = (ctypes.c_char * 256)()
-    p = ctypes.addressof(buf)
+    buf = (ctypes.c_char * 272)()
+    p = (ctypes.addressof(buf) + 15) & ~15          # 16-byte aligned: a padded copy is read from aligned pointers only
     big = ctypes.c_size_t(1 << 42)
     refused = []
     for name, N, C, H, W, K, R, st, (pt, pb), (pl, pr) in _cases(7, 600):
         P, Q = (H + pt + pb - R) // st + 1, (W + pl + pr - R) // st + 1
         conv = (N, C, H, W, K, R, R, st, pt, pl, P, Q)
+        # the transposed layer with the same maps: small (K, P, Q) -> big (C, H, W)
+        convT = (N, K, P, Q, C, R, R, st, pt, pl, H, W)
         rcs = {
-            'conv fwd': lib.bn_conv2d_fwd(p, p, p, p, *conv, 1, 0.05, p, big, None),
-            'conv bwd_data': lib.bn_conv2d_bwd_data(p, p, p, None, *conv, 0, 0.05, p, big, None),
-            'conv bwd_data*lrelu': lib.bn_conv2d_bwd_data(p, p, p, p, *conv, 1, 0.05, p, big, None),
             'conv bwd_weight': lib.bn_conv2d_bwd_weight(p, p, p, p, *conv, 0, p, big, None),
-            # the transposed layer with the same maps: small (K, P, Q) -> big (C, H, W)
-            'convT fwd': lib.bn_convT2d_fwd(p, p, p, p, N, K, P, Q, C, R, R, st, pt, pl, H, W, 1, 0.05, p, big,
-                                            None),
-            'convT bwd_data': lib.bn_convT2d_bwd_data(p, p, p, p, N, K, P, Q, C, R, R, st, pt, pl, H, W, 1,
-                                                      0.05, p, big, None),
-            'convT bwd_weight': lib.bn_convT2d_bwd_weight(p, p, p, p, N, K, P, Q, C, R, R, st, pt, pl, H, W, 0,
-                                                          p, big, None),
+            'convT bwd_weight': lib.bn_convT2d_bwd_weight(p, p, p, p, *convT, 0, p, big, None),
         }
+        # the four roles that take a 5x5 copy of the taps: without one, and with one whether the layer pads or not
+        # (a copy for a layer that does not pad is ignored) -- the latter with exactly the scratch the role's query
+        # asks for, which is the query of the call that pads for itself
+        for tag, w5, ws_of in (('', None, lambda op, g: big),
+                               (' w5', p, lambda op, g: ctypes.c_size_t(lib.bn_conv_ws_bytes(op, *g)))):
+            rcs['conv fwd' + tag] = lib.bn_conv2d_fwd(p, p, w5, p, p, *conv, 1, 0.05, p, ws_of(1, conv), None)
+            rcs['conv bwd_data' + tag] = lib.bn_conv2d_bwd_data(p, p, w5, p, None, *conv, 0, 0.05, p,
+                                                                ws_of(2, conv), None)
+            rcs['conv bwd_data*lrelu' + tag] = lib.bn_conv2d_bwd_data(p, p, w5, p, p, *conv, 1, 0.05, p,
+                                                                      ws_of(2, conv), None)
+            rcs['convT fwd' + tag] = lib.bn_convT2d_fwd(p, p, w5, p, p, *convT, 1, 0.05, p, ws_of(4, convT), None)
+            rcs['convT bwd_data' + tag] = lib.bn_convT2d_bwd_data(p, p, w5, p, p, *convT, 1, 0.05, p,
+                                                                  ws_of(5, convT), None)
         for role, rc in rcs.items():
             if rc < 0:
                 refused.append((name, role, rc))
@@ -67,7 +73,7 @@ def test_scratch_sizes_of_the_sweep_are_finite():
 
 
 def test_padded_taps_queries_and_argument_checks():
-    """bn_conv_taps_bytes / _pad / _hint (round 6) on the host: a 5x5 layer pads nothing, the 3x3 / 4x4 stride-2 layers of
+    """bn_conv_taps_bytes / _pad (round 6) on the host: a 5x5 layer pads nothing, the 3x3 / 4x4 stride-2 layers of
     the architecture search / ae_arch_2.json ask for a [pairs][5][5] copy in both of their roles, the weight-gradient ops
     and unknown ops for none; the batched copy checks its arguments before it launches anything."""
     lib = _hip.load()
@@ -89,4 +95,3 @@ def test_padded_taps_queries_and_argument_checks():
     geoms = (ctypes.c_int * 13)(_hip.OP_CONV_FWD, *five)
     assert lib.bn_conv_taps_pad(1, ptrs, ptrs, geoms, None) < 0             # a layer that does not pad: refused
     assert lib.bn_conv_taps_pad(1, None, ptrs, geoms, None) < 0
-    assert lib.bn_conv_taps_hint(None, None) == 0

@@ -1193,12 +1193,25 @@ def test_random_geometries_all_roles_transposed(case):
     test_convT2d_bwd(case)
 
 
+def _nan_copies(numel):
+    """-> (aligned, misaligned): two all-NaN stand-ins for a 5x5 copy of ``numel`` floats, the second 4 bytes off."""
+    buf = torch.full((numel + 1,), float('nan'), device=DEV)
+    assert buf.data_ptr() % 16 == 0 and buf[1:].data_ptr() % 16 == 4
+    return buf[:numel], buf[1:]
+
+
+def _smallest_5x5_stride2(cases):
+    """The 5x5 stride-2 case with the fewest input elements: a layer that pads nothing."""
+    return min((c for c in cases if c[6] == 5 and c[7] == 2), key=lambda c: c[1] * c[2] * c[3] * c[4])
+
+
 @pytest.mark.parametrize('case_name', ['k4_64ch_32x32', 'k3s2_same_32x32', 'k3_16x16', 'k3s2_pt0_pl1', 'k4x3_24x20',
                                        'k3s2_same_8x8_4x4', 'k2s2_same_16x16'])
 def test_padded_taps_made_once_serve_both_roles(case_name):
     """Round 6: a conv stack makes the 5x5 copies of its small-kernel layers' taps in one launch (bn_conv_taps_pad) and
-    hands them to the forward and data-gradient entry points (bn_conv_taps_hint, one-shot) -- same bits as the
-    copies the entry points make themselves; a hint for other weights is dropped, never used later."""
+    hands them to the forward and data-gradient entry points as their w5 argument -- same bits as the copies the entry
+    points make themselves.  The argument is all there is: nothing outlives a call, a layer that does not pad ignores
+    a copy, and so does a call whose copy is not 16-byte aligned."""
     case = [c for c in CONV_CASES if c[0] == case_name][0]
     x, w, b, geom, _ = _conv_setup(case)
     xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
@@ -1210,24 +1223,36 @@ def test_padded_taps_made_once_serve_both_roles(case_name):
     t5 = w5[:K * C * 25]
     assert torch.equal(t5, w5b[:K * C * 25])
     assert torch.equal(t5[t5 != 0].sort().values, wd.flatten().sort().values)       # every tap once, zeros elsewhere
-    y0 = _hip.conv2d_fwd(xd, wd, bd, geom, _hip.ACT_LRELU, SLOPE)
-    y1 = _hip.conv2d_fwd(xd, wd, bd, geom, _hip.ACT_LRELU, SLOPE, w5=w5)
-    assert torch.equal(y0, y1)
-    dx0 = _hip.conv2d_bwd_data(dy, wd, geom, None, _hip.ACT_NONE, SLOPE)
-    dx1 = _hip.conv2d_bwd_data(dy, wd, geom, None, _hip.ACT_NONE, SLOPE, w5=w5)
-    assert torch.equal(dx0, dx1)
+
+    def fwd(**kw):
+        return _hip.conv2d_fwd(xd, wd, bd, geom, _hip.ACT_LRELU, SLOPE, **kw)
+
+    def bwd(**kw):
+        return _hip.conv2d_bwd_data(dy, wd, geom, None, _hip.ACT_NONE, SLOPE, **kw)
+    y0, dx0 = fwd(), bwd()
+    assert torch.equal(y0, fwd(w5=w5))
+    assert torch.equal(dx0, bwd(w5=w5))
+    poison, off4 = _nan_copies(w5.numel())
     # the copy IS what the kernels read ...
-    poison = torch.full_like(w5, float('nan'))
-    assert bool(torch.isnan(_hip.conv2d_fwd(xd, wd, bd, geom, _hip.ACT_LRELU, SLOPE, w5=poison)).all())
-    # ... only for the weights it was made for, and only in the very next call
-    other = wd.clone()
-    _hip.load().bn_conv_taps_hint(other.data_ptr(), poison.data_ptr())
-    assert torch.equal(_hip.conv2d_fwd(xd, wd, bd, geom, _hip.ACT_LRELU, SLOPE), y0)
-    assert torch.equal(_hip.conv2d_fwd(xd, other, bd, geom, _hip.ACT_LRELU, SLOPE), y0)
-    _hip.load().bn_conv_taps_hint(wd.data_ptr(), poison.data_ptr())
-    dwt = torch.zeros_like(wd)
-    _hip.conv2d_bwd_weight(xd, dy, dwt, None, geom, False)          # (an entry point that takes no hint drops it)
-    assert torch.equal(_hip.conv2d_fwd(xd, wd, bd, geom, _hip.ACT_LRELU, SLOPE), y0)
+    assert bool(torch.isnan(fwd(w5=poison)).all())
+    # ... in the call that is given it and in no later one
+    assert torch.equal(fwd(), y0)
+    assert bool(torch.isnan(bwd(w5=poison)).any())
+    assert torch.equal(bwd(), dx0)
+    # a copy that is not 16-byte aligned is not read: the call pads for itself
+    assert torch.equal(fwd(w5=off4), y0)
+    assert torch.equal(bwd(w5=off4), dx0)
+    # a layer that does not pad ignores a copy
+    x5, w5x5, b5, geom5, _ = _conv_setup(_smallest_5x5_stride2(CONV_CASES))
+    x5, w5x5, b5 = x5.to(DEV), w5x5.to(DEV), b5.to(DEV)
+    dy5 = torch.rand((geom5[0], geom5[4], geom5[10], geom5[11]), generator=torch.Generator().manual_seed(3))
+    dy5 = (dy5 - 0.5).to(DEV)
+    nan5, _ = _nan_copies(w5x5.numel())
+    assert _hip.conv_taps_bytes(_hip.OP_CONV_FWD, geom5) == 0
+    assert torch.equal(_hip.conv2d_fwd(x5, w5x5, b5, geom5, _hip.ACT_LRELU, SLOPE, w5=nan5),
+                       _hip.conv2d_fwd(x5, w5x5, b5, geom5, _hip.ACT_LRELU, SLOPE))
+    assert torch.equal(_hip.conv2d_bwd_data(dy5, w5x5, geom5, None, _hip.ACT_NONE, SLOPE, w5=nan5),
+                       _hip.conv2d_bwd_data(dy5, w5x5, geom5, None, _hip.ACT_NONE, SLOPE))
 
 
 @pytest.mark.parametrize('case_name', ['k4_64ch_16x16', 'k3_8x8', 'k3s2_same_16x16', 'k3s2_same_10x12'])
@@ -1239,13 +1264,34 @@ def test_padded_taps_made_once_serve_both_roles_transposed(case_name):
     dy = (torch.rand((N, Co, Ho, Wo), generator=torch.Generator().manual_seed(3)) - 0.5).to(DEV)
     assert _hip.conv_taps_bytes(_hip.OP_CONVT_FWD, geom) >= Ci * Co * 25 * 4
     (w5,) = _hip.conv_taps_pad([(_hip.OP_CONVT_FWD, geom, wd)], DEV)
-    y0 = _hip.convT2d_fwd(xd, wd, bd, geom, _hip.ACT_LRELU, SLOPE)
-    assert torch.equal(y0, _hip.convT2d_fwd(xd, wd, bd, geom, _hip.ACT_LRELU, SLOPE, w5=w5))
-    dx0 = _hip.convT2d_bwd_data(dy, wd, geom, None, _hip.ACT_NONE, SLOPE)
-    assert torch.equal(dx0, _hip.convT2d_bwd_data(dy, wd, geom, None, _hip.ACT_NONE, SLOPE, w5=w5))
-    poison = torch.full_like(w5, float('nan'))
-    assert bool(torch.isnan(_hip.convT2d_bwd_data(dy, wd, geom, None, _hip.ACT_NONE, SLOPE, w5=poison)).all())
-    assert torch.equal(_hip.convT2d_bwd_data(dy, wd, geom, None, _hip.ACT_NONE, SLOPE), dx0)
+
+    def fwd(**kw):
+        return _hip.convT2d_fwd(xd, wd, bd, geom, _hip.ACT_LRELU, SLOPE, **kw)
+
+    def bwd(**kw):
+        return _hip.convT2d_bwd_data(dy, wd, geom, None, _hip.ACT_NONE, SLOPE, **kw)
+    y0, dx0 = fwd(), bwd()
+    assert torch.equal(y0, fwd(w5=w5))
+    assert torch.equal(dx0, bwd(w5=w5))
+    poison, off4 = _nan_copies(w5.numel())
+    # read in the call that is given it, in no later one, and not at all where it is not 16-byte aligned
+    assert bool(torch.isnan(bwd(w5=poison)).all())
+    assert torch.equal(bwd(), dx0)
+    assert bool(torch.isnan(fwd(w5=poison)).any())
+    assert torch.equal(fwd(), y0)
+    assert torch.equal(fwd(w5=off4), y0)
+    assert torch.equal(bwd(w5=off4), dx0)
+    # a layer that does not pad ignores a copy
+    x5, w5x5, b5, geom5, _ = _convT_setup(_smallest_5x5_stride2(CONVT_CASES))
+    x5, w5x5, b5 = x5.to(DEV), w5x5.to(DEV), b5.to(DEV)
+    dy5 = torch.rand((geom5[0], geom5[4], geom5[10], geom5[11]), generator=torch.Generator().manual_seed(3))
+    dy5 = (dy5 - 0.5).to(DEV)
+    nan5, _ = _nan_copies(w5x5.numel())
+    assert _hip.conv_taps_bytes(_hip.OP_CONVT_FWD, geom5) == 0
+    assert torch.equal(_hip.convT2d_fwd(x5, w5x5, b5, geom5, _hip.ACT_LRELU, SLOPE, w5=nan5),
+                       _hip.convT2d_fwd(x5, w5x5, b5, geom5, _hip.ACT_LRELU, SLOPE))
+    assert torch.equal(_hip.convT2d_bwd_data(dy5, w5x5, geom5, None, _hip.ACT_NONE, SLOPE, w5=nan5),
+                       _hip.convT2d_bwd_data(dy5, w5x5, geom5, None, _hip.ACT_NONE, SLOPE))
 
 
 @pytest.mark.parametrize('case_name', ['s1_k5_64x64', 's1_k3_32x32', 's1_k4_8x8', 's1_k5_24x16', 's1_k5_pad13',

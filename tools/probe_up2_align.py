@@ -27,8 +27,8 @@ src = (torch.rand(nx, generator=g) - 0.3).cuda()
 def run(xo, yo, iters=30):
     x = xbuf[xo:xo + nx]; x.copy_(src)
     y = ybuf[yo:yo + ny]
-    args = (ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(b.data_ptr()),
-            ctypes.c_void_p(y.data_ptr()), N, ci, hi, wi, co, 5, 5, st, off, off, ho, wo, 1, ctypes.c_float(0.05),
+    args = (ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(None),      # w5: none
+            ctypes.c_void_p(b.data_ptr()), ctypes.c_void_p(y.data_ptr()), N, ci, hi, wi, co, 5, 5, st, off, off, ho, wo, 1, ctypes.c_float(0.05),
             ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()), ctypes.c_void_p(stream))
     for _ in range(5):
         rc = fn(*args); assert rc == 0, rc

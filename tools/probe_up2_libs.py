@@ -22,8 +22,8 @@ for path in sys.argv[1:]:
             y = torch.empty((N, co, ho, wo), device='cuda')
             wsb = lib.bn_conv_ws_bytes(4, N, ci, hi, wi, co, 5, 5, st, off, off, ho, wo)
             ws = torch.empty(max(int(wsb), 256), dtype=torch.uint8, device='cuda')
-            args = (ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(b.data_ptr()),
-                    ctypes.c_void_p(y.data_ptr()), N, ci, hi, wi, co, 5, 5, st, off, off, ho, wo, 1, ctypes.c_float(0.05),
+            args = (ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(None),      # w5: none
+                    ctypes.c_void_p(b.data_ptr()), ctypes.c_void_p(y.data_ptr()), N, ci, hi, wi, co, 5, 5, st, off, off, ho, wo, 1, ctypes.c_float(0.05),
                     ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(ws.numel()),
                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
             for _ in range(10):
