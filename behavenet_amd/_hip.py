@@ -136,6 +136,10 @@ SIGNATURES = {
     'bn_frame_sq_err': (
         _c_int, [_c_void_p] * 2 + [_c_int] + [_c_void_p] * 2 + [_c_int, _c_size_t, _c_float, _c_void_p, _c_size_t,
                                                                  _c_void_p]),
+    'bn_pixel_stats_ws_bytes': (_c_size_t, [_c_int, _c_size_t]),
+    'bn_pixel_stats_accum': (
+        _c_int, [_c_void_p] * 2 + [_c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_size_t, _c_void_p, _c_size_t,
+                                   _c_void_p]),
     'bn_u8_to_unit_float': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     'bn_unit_float_to_u8': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
@@ -515,6 +519,43 @@ def frame_sq_err(xhat, target, mask=None, scale=1.0, out=None):
     _check(lib.bn_frame_sq_err(_ptr(xhat, 'xhat'), tp, is_u8, mp, _ptr(out, 'out'), n, d, float(scale), ws, nbytes,
                                _stream()), 'bn_frame_sq_err')
     return out
+
+
+def pixel_stats_accum(xhat, target, mask, acc):
+    """acc (4, ...) float64 += per-pixel sums over the N frames of target (N, ...): plane 0 the squared error
+    (xhat - target)^2 * mask (left alone when ``xhat`` is None), plane 1 the mask weight, planes 2 and 3 the
+    mask-weighted first and second moment of the target.  xhat fp32 of target's shape or None; target fp32 or uint8
+    (value / 255); mask fp32 of target's shape, of ONE frame's shape (one mask for all frames) or None.  Sums in
+    float64 in a fixed order (csrc/pixel_stats.hip).  -> acc."""
+    if target.dim() < 2:
+        raise HipLibraryError('pixel_stats_accum: expected a target (N, ...), got %s' % (tuple(target.shape),))
+    if target.dtype not in (torch.float32, torch.uint8) or not target.is_contiguous():
+        raise HipLibraryError('pixel_stats_accum: the target must be a contiguous float32 or uint8 tensor')
+    if xhat is not None and tuple(xhat.shape) != tuple(target.shape):
+        raise HipLibraryError('pixel_stats_accum: xhat %s and target %s must share a shape (N, ...)'
+                              % (tuple(xhat.shape), tuple(target.shape)))
+    n, frame = int(target.shape[0]), tuple(target.shape[1:])
+    d = target[0].numel() if n else 0
+    mask_frames = 0
+    if mask is not None:
+        if tuple(mask.shape) == tuple(target.shape):
+            mask_frames = n
+        elif tuple(mask.shape) in (frame, (1,) + frame):
+            mask_frames = 1
+        else:
+            raise HipLibraryError('pixel_stats_accum: the mask must have the target\'s shape %s or one frame\'s, got %s'
+                                  % (tuple(target.shape), tuple(mask.shape)))
+    if tuple(acc.shape) != (4,) + frame:
+        raise HipLibraryError('pixel_stats_accum: acc must have the shape %s, got %s'
+                              % ((4,) + frame, tuple(acc.shape)))
+    lib = load()
+    nbytes = lib.bn_pixel_stats_ws_bytes(n, d)
+    ws = _arena(target.device, nbytes) if nbytes else None
+    _check(lib.bn_pixel_stats_accum(
+        _ptr(xhat, 'xhat', allow_none=True), _ptr(target, 'target', dtype=target.dtype),
+        int(target.dtype == torch.uint8), _ptr(mask, 'mask', allow_none=True), mask_frames,
+        _ptr(acc, 'acc', dtype=torch.float64), n, d, ws, nbytes, _stream()), 'bn_pixel_stats_accum')
+    return acc
 
 
 def convT2d_last_bf16_sqerr(x, w, b, target, mask, geom, act, slope, scale=1.0, out=None):

@@ -74,6 +74,13 @@ int bn_launch_frame_err_finish(const float* part, float* out, int N, unsigned P,
 bool bn_unit_float_to_u8_ok(size_t n);
 int bn_launch_unit_float_to_u8(const float* in, unsigned char* out, size_t n, hipStream_t st);
 
+// pixel_stats.hip: per-pixel float64 sums over the frames (squared error, mask weight, first and second moment of
+// the target) added onto acc (4, D); a pixel's summation order a function of (N, D) alone
+bool bn_pixel_stats_ok(int N, size_t D);
+size_t bn_pixel_stats_ws_bytes_impl(int N, size_t D);
+int bn_launch_pixel_stats(const float* xhat, const void* target, int target_is_u8, const float* mask, int mask_frames,
+                          double* acc, int N, size_t D, void* ws, hipStream_t st);
+
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);
 int bn_launch_bn_stats(const float* x, float* mean, float* var, int N, int C, int HW, void* ws,

@@ -1919,6 +1919,25 @@ extern "C" int bn_frame_sq_err(const float* xhat, const void* target, int target
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Per-pixel sums over the frames (pixel_stats.hip), added onto acc (4, D) float64.  Every refusal is BN_E_SHAPE.
+extern "C" size_t bn_pixel_stats_ws_bytes(int N, size_t D) { return bn_pixel_stats_ws_bytes_impl(N, D); }
+
+extern "C" int bn_pixel_stats_accum(const float* xhat, const void* target, int target_is_u8, const float* mask,
+                                    int mask_frames, double* acc, int N, size_t D, void* ws, size_t ws_bytes,
+                                    bn_stream_t stream) {
+    if (!target || !acc) return BN_E_BADARG;
+    if (N <= 0 || D == 0 || !bn_pixel_stats_ok(N, D)) return BN_E_SHAPE;
+    if (mask && mask_frames != 1 && mask_frames != N) return BN_E_SHAPE;
+    // (fp32 operands that are not even 4-byte aligned cannot be read at all)
+    if (((uintptr_t)xhat & 3) || ((uintptr_t)mask & 3) || (!target_is_u8 && ((uintptr_t)target & 3)))
+        return BN_E_SHAPE;
+    const size_t need = bn_pixel_stats_ws_bytes_impl(N, D);
+    if (need && (!ws || ws_bytes < need)) return BN_E_SHAPE;
+    if (!aligned16(acc) || (need && !aligned16(ws))) return BN_E_SHAPE;
+    return bn_launch_pixel_stats(xhat, target, target_is_u8, mask, mask_frames, acc, N, D, ws, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // fp32 unit-float frames -> stored uint8 grey levels (recon_u8.hip): NaN -> 0, else clamp(rint(x * 255), 0, 255).
 extern "C" int bn_unit_float_to_u8(const float* in, unsigned char* out, size_t n, bn_stream_t stream) {
     if (!in || !out) return BN_E_BADARG;

@@ -1,5 +1,6 @@
 """Inference-only passes over every trial: latents -> ``*_latents.pkl`` (BASELINE config 5), per-frame
-reconstruction errors -> ``*_frame_errors.pkl`` and uint8 reconstructions -> ``*_reconstructions.npz``.
+reconstruction errors -> ``*_frame_errors.pkl``, uint8 reconstructions -> ``*_reconstructions.npz`` and per-pixel
+error / moment maps -> ``*_pixel_stats.pkl``.
 
 Mirror of ``export_latents`` in the reference ``behavenet/fitting/eval.py:6-118``: same pickle
 schema ``{'latents': [per-trial (T x D) arrays, empty for gap trials], 'trials': batch_idxs}``
@@ -23,7 +24,8 @@ from behavenet_amd.hip_functions import (DECODE_DTYPES, ENCODE_DTYPES, decode_pr
 
 __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconstruction', 'export_frame_errors',
            'frame_errors', 'frame_errors_device', 'export_reconstructions', 'reconstruct_trial',
-           'reconstruct_trial_device']
+           'reconstruct_trial_device', 'export_pixel_stats', 'pixel_stats', 'pixel_stats_device',
+           'summarise_pixel_stats']
 
 
 def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -156,7 +158,7 @@ class _GraphedTrialEncoder(object):
         return rec
 
 
-def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond_enc, sink=None):
+def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond_enc, sink=None, sink_sharded=False):
     """The trial walk the exporters share: every train / val / test trial of every session goes once through
     ``on_device_fn(images, sess, data)`` (device-resident frames; the results stay on the device and come to the
     host in ONE transfer at the end) or ``on_host_fn(images, sess, data)`` (-> numpy).  Under
@@ -165,14 +167,15 @@ def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond
 
     With ``sink`` nothing piles up: every result, device tensor or numpy array, goes to ``sink(sess, trial, result)``
     as soon as its trial is done and the returned lists stay empty.  Such a walk is one process's: the caller runs
-    it on ONE rank, which owns every trial and enters no collective."""
+    it on ONE rank, which owns every trial and enters no collective -- unless ``sink_sharded``: then every rank
+    walks the trials it owns into its own sink, and what the sinks hold is the caller's to gather."""
     # multi-session generators serve lists of batches for training; trials are exported one by
     # one (the reference's MSPSVAE.export_latents rebuilds a one-session-per-batch generator,
     # vaes.py:1198-1216)
     single = {'return_multiple': False} \
         if getattr(data_generator, 'n_sessions_per_batch', 1) > 1 else {}
     model.eval()
-    rank, world = (0, 1) if sink is not None else (bdist.rank(), bdist.world_size())
+    rank, world = (0, 1) if (sink is not None and not sink_sharded) else (bdist.rank(), bdist.world_size())
 
     results = [[np.array([]) for _ in range(ds.n_trials)] for ds in data_generator.datasets]
     # which rank encodes a trial is a function of the trial's identity (its position in the
@@ -237,7 +240,7 @@ def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond
             pos += n
         del on_device
 
-    if world > 1:
+    if world > 1 and sink is None:
         import torch.distributed as dist
         gathered = [None] * world if rank == 0 else None
         dist.gather_object(results, gathered, dst=0)
@@ -631,3 +634,183 @@ def export_reconstructions(data_generator, model, filename=None):
             w.abort()
         raise
     return [writers[sess].close() for sess in sorted(writers)]
+
+
+# ------------------------------------------------------------------------------------------ pixel stats
+_PIXEL_SPLITS = ('train', 'val', 'test')
+
+
+def _pixel_stats_device(model, y, sess, masks, labels, labels_2d, chunk_size, out):
+    """``pixel_stats_device`` inside whatever precision blocks the caller opened."""
+    cls = model.hparams['model_class']
+    if cls not in _LATENTS_AT:
+        raise ValueError('Invalid model class %s' % cls)
+    if y.dim() != 4:
+        raise ValueError('pixel_stats: expected frames (T, C, H, W), got %s' % (tuple(y.shape),))
+    if y.dtype not in (torch.uint8, torch.float32):
+        raise ValueError('pixel_stats: frames must be uint8 or float32, got %s' % y.dtype)
+    model.eval()
+    y = y.contiguous()
+    n = y.shape[0]
+    if out is None:
+        out = torch.zeros((4,) + tuple(y.shape[1:]), dtype=torch.float64, device=y.device)
+    elif tuple(out.shape) != (4,) + tuple(y.shape[1:]) or out.dtype != torch.float64:
+        raise ValueError('pixel_stats: out must be a float64 tensor of shape %s, got %s %s'
+                         % ((4,) + tuple(y.shape[1:]), out.dtype, tuple(out.shape)))
+    if masks is not None:
+        # one (C, H, W) mask per trial -- handed to the kernel as it is, not expanded -- or per-frame masks
+        if masks.dim() == y.dim() and masks.shape[0] == 1 and n != 1:
+            masks = masks[0]
+        if masks.dtype != torch.float32:
+            masks = masks.float()
+        masks = masks.contiguous()
+    # (conv encoders take the stored uint8 frames as they are, as in _encode_trial_device; the TARGET stays
+    # uint8 either way: the kernel divides by 255 as bn_u8_to_unit_float does)
+    x = y
+    if y.dtype == torch.uint8 and (labels_2d is not None or model.hparams.get('model_type', 'conv') != 'conv'):
+        x = _hip.u8_to_unit_float(y)
+    kwargs = _forward_kwargs(cls, sess)
+    with torch.no_grad():
+        for beg in range(0, n, chunk_size):
+            end = min(beg + chunk_size, n)
+            target = y[beg:end]
+            mask = masks
+            if masks is not None and masks.dim() == y.dim():
+                mask = masks[beg:end]
+            if cls in ('cond-ae', 'cond-vae'):
+                kwargs.update(labels=labels[beg:end], labels_2d=None if labels_2d is None else labels_2d[beg:end])
+            x_hat = model(x[beg:end], **kwargs)[0]
+            _hip.pixel_stats_accum(x_hat.contiguous().view(target.shape), target, mask, out)
+    return out
+
+
+def pixel_stats_device(model, y, sess=None, masks=None, labels=None, labels_2d=None, chunk_size=200, out=None):
+    """Per-pixel sums over the frames of one trial as a float64 DEVICE tensor (4, C, H, W):
+
+        [0] sse = sum_n (x_hat[n] - y[n])^2 * mask        [1] w  = sum_n mask
+        [2] s1  = sum_n mask * y[n]                       [3] s2 = sum_n mask * y[n]^2
+
+    -- what ``summarise_pixel_stats`` turns into per-pixel MSE and R^2 maps.  With ``out`` the sums are ADDED onto
+    that tensor, which is returned: a session's trials accumulate on the device.  ``frame_errors_device``'s contract
+    otherwise: ``y`` fp32 frames or stored uint8 frames (value / 255); ``masks`` one (C, H, W) mask for the trial or
+    one per frame; eval mode, ``no_grad``, the posterior mean for every variational class.  The squared-error terms
+    are ``bn_frame_sq_err``'s in fp32; every sum is float64 in a fixed order (``bn_pixel_stats_accum``), which
+    ``chunk_size`` changes and nothing else.
+
+    ``hparams['hip_encode_dtype']`` and ``hparams['hip_decode_dtype']`` are honoured independently, each under its own
+    eligibility rules; the decoder writes its fp32 x_hat on every lane and the kernel reads it (no scoring or
+    quantising request is opened)."""
+    with encode_precision(encode_dtype_of(model)), decode_precision(decode_dtype_of(model)):
+        return _pixel_stats_device(model, y, sess, masks, labels, labels_2d, chunk_size, out)
+
+
+def pixel_stats(model, y, sess=None, masks=None, labels=None, labels_2d=None, chunk_size=200, out=None):
+    """``pixel_stats_device`` as a numpy array (4, C, H, W) of float64."""
+    return pixel_stats_device(model, y, sess, masks, labels, labels_2d, chunk_size, out).cpu().numpy()
+
+
+def summarise_pixel_stats(acc, n_frames):
+    """Maps and scalars from the (4, C, H, W) sums of ``n_frames`` frames, numpy float64 on the host:
+
+        mse_map  = sse / n_frames                       mean_map = s1 / w
+        var_map  = max(s2 / w - mean_map^2, 0)          r2_map   = 1 - sse / (s2 - s1^2 / w)
+        mse      = sum(sse) / (n_frames * C H W)        r2       = 1 - sum(sse) / sum(s2 - s1^2 / w)
+
+    ``mse`` is the mean of ``frame_errors`` over the same frames (the reference's denominator, masks included);
+    ``r2`` without masks is sklearn's ``r2_score(..., multioutput='variance_weighted')`` with pixels as outputs, the
+    definition of ``models.vaes._r2_variance_weighted``.  A pixel whose (mask-weighted) variance is zero -- its
+    denominator no larger than the rounding of the float64 sums it is the difference of -- has NaN in ``r2_map`` and
+    adds nothing to the scalar's denominator; a pixel of zero weight has NaN in ``mean_map`` and ``var_map`` too."""
+    acc = np.asarray(acc, dtype=np.float64)
+    if acc.ndim < 2 or acc.shape[0] != 4:
+        raise ValueError('summarise_pixel_stats: expected sums (4, C, H, W), got %s' % (acc.shape,))
+    n_frames = int(n_frames)
+    if n_frames <= 0:
+        raise ValueError('summarise_pixel_stats: n_frames must be positive, got %d' % n_frames)
+    sse, w, s1, s2 = acc
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mean = s1 / w
+        var = np.maximum(s2 / w - mean * mean, 0.0)
+        var[np.isnan(mean)] = np.nan
+        denom = s2 - s1 * s1 / w
+        # s2 and s1^2 / w each carry up to ~n_frames roundings of 2^-53: a difference below that is no variance
+        denom[~(denom > 4.0 * (n_frames + 4) * 2.0 ** -53 * s2)] = 0.0
+        r2_map = np.where(denom > 0, 1.0 - sse / denom, np.nan)
+        total = float(denom.sum())
+        r2 = 1.0 - float(sse.sum()) / total if total > 0 else float('nan')
+    return {'mse_map': sse / n_frames, 'mean_map': mean, 'var_map': var, 'r2_map': r2_map,
+            'mse': float(sse.sum()) / (n_frames * sse.size), 'r2': r2}
+
+
+def export_pixel_stats(data_generator, model, filename=None):
+    """Accumulate the per-pixel sums of ``pixel_stats_device`` over the train / val / test trials of every session
+    and pickle them next to the latents, ``<lab>_<expt>_<animal>_<session>_pixel_stats.pkl``:
+
+        {'stats': {split: (4, C, H, W) float64}, 'n_frames': {split: int},
+         'summary': {split: {'mse': float, 'r2': float}, or None for a split without frames}, 'trials': batch_idxs}
+
+    (``summarise_pixel_stats(stats[split], n_frames[split])`` gives the maps).  The trial walk is ``export_latents``'
+    (ownership by identity under ``torch.distributed``, stored uint8 frames where the model takes them), with the
+    batch's masks and, for the conditional classes, labels; a trial's split is the one ``dataset.batch_idxs`` lists it
+    in.  Every trial is added onto its (session, split) accumulator ON THE DEVICE; the accumulators alone come to
+    the host.  Under ``torch.distributed`` they are gathered on rank 0 and added in rank order, and the other ranks
+    return [].  Launched eagerly.  -> the list of file names."""
+    cls = model.hparams['model_class']
+    cond_enc = cls == 'cond-ae' and model.hparams.get('conditional_encoder', False)
+    decode_dtype_of(model), encode_dtype_of(model)          # (an invalid key is an error before any trial is read)
+    chunk = int(model.hparams.get('export_chunk_frames', 1024))
+    split_of = {(s_, int(t)): dt for s_, ds in enumerate(data_generator.datasets)
+                for dt in _PIXEL_SPLITS for t in ds.batch_idxs[dt]}
+    accs, n_frames, done = {}, {}, []
+
+    def accumulate(images, sess, data):
+        idx = data['batch_idx']
+        key = (sess, split_of[(sess, idx.item() if hasattr(idx, 'item') else int(idx))])
+        masks = data['masks'][0] if 'masks' in data else None
+        labels = data['labels'][0] if cls in ('cond-ae', 'cond-vae') else None
+        labels_2d = data['labels_sc'][0] if cond_enc else None
+        accs[key] = pixel_stats_device(model, images, sess, masks, labels, labels_2d, chunk, out=accs.get(key))
+        n_frames[key] = n_frames.get(key, 0) + int(images.shape[0])
+        return None
+
+    _export_per_trial('export_pixel_stats', data_generator, model, accumulate, accumulate, cond_enc,
+                      sink=lambda sess, trial, result: done.append((sess, trial)), sink_sharded=True)
+    mine = ({k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)) for k, v in accs.items()},
+            n_frames, done)
+    if bdist.world_size() > 1:
+        import torch.distributed as dist
+        gathered = [None] * bdist.world_size() if bdist.rank() == 0 else None
+        dist.gather_object(mine, gathered, dst=0)
+        if bdist.rank() != 0:
+            return []
+        accs, n_frames, done = {}, {}, []
+        for r_accs, r_frames, r_done in gathered:          # (rank order: the sum's order is the ranks')
+            for k, v in r_accs.items():
+                accs[k] = accs[k] + v if k in accs else v
+                n_frames[k] = n_frames.get(k, 0) + r_frames[k]
+            done.extend(r_done)
+        missing = sorted(set(split_of) - set(done))
+        if missing:
+            raise RuntimeError('export_pixel_stats: %d trials were accumulated by no rank, e.g. %s'
+                               % (len(missing), missing[:3]))
+    else:
+        accs = mine[0]
+
+    filenames = []
+    for sess, dataset in enumerate(data_generator.datasets):
+        out = _session_filename(model, dataset, filename, 'pixel_stats.pkl')
+        print('saving pixel stats %i of %i:\n%s' % (sess + 1, data_generator.n_datasets, out))
+        shapes = [accs[(sess, dt)].shape for dt in _PIXEL_SPLITS if (sess, dt) in accs]
+        empty = np.zeros(shapes[0] if shapes else (4, 0, 0, 0), dtype=np.float64)
+        stats = {dt: accs.get((sess, dt), empty.copy()) for dt in _PIXEL_SPLITS}
+        frames = {dt: int(n_frames.get((sess, dt), 0)) for dt in _PIXEL_SPLITS}
+        summary = {}
+        for dt in _PIXEL_SPLITS:
+            summary[dt] = None
+            if frames[dt]:
+                full = summarise_pixel_stats(stats[dt], frames[dt])
+                summary[dt] = {'mse': full['mse'], 'r2': full['r2']}
+        with open(out, 'wb') as f:
+            pickle.dump({'stats': stats, 'n_frames': frames, 'summary': summary, 'trials': dataset.batch_idxs}, f)
+        filenames.append(out)
+    return filenames

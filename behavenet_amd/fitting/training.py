@@ -838,6 +838,11 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
             print('exporting reconstructions')
         from behavenet_amd.fitting.eval import export_reconstructions
         export_reconstructions(data_generator, best_val_model)
+    if method == 'ae' and hparams.get('export_pixel_stats', False):
+        if is_main:
+            print('exporting pixel stats')
+        from behavenet_amd.fitting.eval import export_pixel_stats
+        export_pixel_stats(data_generator, best_val_model)
     if resume and is_main:
         if state_writer is not None:
             state_writer.wait()

@@ -522,6 +522,30 @@ int bn_frame_sq_err(const float* xhat, const void* target, int target_is_u8, con
                     float* out, int N, size_t D, float scale, void* ws, size_t ws_bytes,
                     bn_stream_t stream);
 
+/* Per-pixel sums over the frames of a reconstruction that is already in memory, ADDED ONTO acc, float64
+ * (4, D), plane by plane (t = target, m = mask or 1):
+ *   0  sse[i] += sum_n ((xhat[n,i] - t[n,i]) * (xhat[n,i] - t[n,i])) * m[n,i]   the fp32 term of
+ *                bn_frame_sq_err, widened to double; the plane is not touched when xhat is NULL
+ *   1  w[i]   += sum_n (double)m[n,i]
+ *   2  s1[i]  += sum_n (double)m[n,i] * (double)t[n,i]
+ *   3  s2[i]  += sum_n (double)m[n,i] * ((double)t[n,i] * (double)t[n,i])
+ * xhat fp32 (N, D), nullable; target fp32 (N, D), or with target_is_u8 uint8 (value / 255, the
+ * division of bn_u8_to_unit_float); mask fp32, nullable: (N, D) with mask_frames == N, or one (D,)
+ * mask for all frames with mask_frames == 1 (mask_frames is not read without a mask).
+ * Order: every sum is float64, without atomics.  A workgroup walks a block of consecutive frames in
+ * ascending order; the blocks' partial sums are added from left to right, and that sum onto acc.  The
+ * cut into frame blocks is a function of (N, D) alone, so equal calls give equal bits; 16-byte loads
+ * where every operand sits on a 16-byte boundary (4 bytes for a uint8 target) and D is a multiple of
+ * 4, element-by-element loads otherwise, with the same bits either way.
+ * `ws`: bn_pixel_stats_ws_bytes(N, D) bytes (0 while one frame block serves the call).
+ * Refusals, all BN_E_SHAPE with nothing written: N <= 0, D == 0, a mask with mask_frames not in
+ * {1, N}, a workspace smaller than the query says, an acc or ws off a 16-byte boundary, fp32 operands
+ * off a 4-byte boundary.  (A NULL target or acc is BN_E_BADARG.) */
+size_t bn_pixel_stats_ws_bytes(int N, size_t D);
+int bn_pixel_stats_accum(const float* xhat, const void* target, int target_is_u8, const float* mask,
+                         int mask_frames, double* acc, int N, size_t D, void* ws, size_t ws_bytes,
+                         bn_stream_t stream);
+
 /* uint8 frames -> float32/255 (replaces the host-side astype(float32)/255 of
  * data_generator.py:251-263 for device-resident uint8 trials) */
 int bn_u8_to_unit_float(const unsigned char* in, float* out, size_t n, bn_stream_t stream);
