@@ -142,6 +142,7 @@ SIGNATURES = {
                                    _c_void_p]),
     'bn_u8_to_unit_float': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     'bn_unit_float_to_u8': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
+    'bn_cond_encoder_input': (_c_int, [_c_void_p, _c_int, _c_void_p] + [_c_int] * 6 + [_c_void_p, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
     'bn_prof_read': (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
@@ -1043,6 +1044,40 @@ def unit_float_to_u8(x, out=None):
     out = _bf16_out(out, tuple(x.shape), torch.uint8, x.device, 'unit_float_to_u8')
     _check(load().bn_unit_float_to_u8(
         _ptr(x, 'in'), _ptr(out, 'out', dtype=torch.uint8), x.numel(), _stream()), 'bn_unit_float_to_u8')
+    return out
+
+
+def cond_encoder_input(x, coords, n_maps=None):
+    """Frames (N, C, H, W), uint8 or fp32, and label coordinates (N, >= 2 L) -> the fp32 (N, C + L, H, W) input of a
+    conditional encoder: the frames (uint8: value / 255, ``u8_to_unit_float``'s division) followed by one one-hot map
+    per label, x from column l and y from column L + l through ``MakeOneHot2D``'s rule (NaN counts as 0, clip, round
+    half to even) -- ``torch.cat((frames, MakeOneHot2D(H, W)(coords)), 1)`` bit for bit, built in one pass on the
+    current stream from coordinates the DEVICE reads (csrc/cond_input.hip; capturable).  ``n_maps`` defaults to
+    ``coords.shape[1] // 2``; further columns are ignored.  Shapes, dtypes and devices are checked before any call
+    (``ValueError``)."""
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise ValueError('cond_encoder_input: expected frames (N, C, H, W), got %s'
+                         % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
+    if x.dtype not in (torch.uint8, torch.float32):
+        raise ValueError('cond_encoder_input: frames must be uint8 or float32, got %s' % x.dtype)
+    if not torch.is_tensor(coords) or coords.dim() != 2:
+        raise ValueError('cond_encoder_input: expected coordinates (N, 2 * n_maps), got %s'
+                         % (tuple(coords.shape) if torch.is_tensor(coords) else type(coords).__name__,))
+    if coords.shape[0] != x.shape[0]:
+        raise ValueError('cond_encoder_input: %d frames but %d rows of coordinates' % (x.shape[0], coords.shape[0]))
+    n_maps = coords.shape[1] // 2 if n_maps is None else int(n_maps)
+    if n_maps < 0 or 2 * n_maps > coords.shape[1]:
+        raise ValueError('cond_encoder_input: %d maps need %d columns of coordinates, got %d'
+                         % (n_maps, 2 * n_maps, coords.shape[1]))
+    if coords.device != x.device:
+        raise ValueError('cond_encoder_input: frames on %s, coordinates on %s' % (x.device, coords.device))
+    x = x.contiguous()
+    coords = coords.to(torch.float32).contiguous()
+    N, C, H, W = x.shape
+    out = torch.empty((N, C + n_maps, H, W), dtype=torch.float32, device=x.device)
+    _check(load().bn_cond_encoder_input(
+        _ptr(x, 'frames', dtype=x.dtype), int(x.dtype == torch.uint8), _ptr(coords, 'coords'), int(coords.shape[1]),
+        N, C, H, W, n_maps, _ptr(out, 'out'), _stream()), 'bn_cond_encoder_input')
     return out
 
 

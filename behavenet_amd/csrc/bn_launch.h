@@ -81,6 +81,12 @@ size_t bn_pixel_stats_ws_bytes_impl(int N, size_t D);
 int bn_launch_pixel_stats(const float* xhat, const void* target, int target_is_u8, const float* mask, int mask_frames,
                           double* acc, int N, size_t D, void* ws, hipStream_t st);
 
+// cond_input.hip: frames (uint8 or fp32) + label coordinates -> the (N, C + L, H, W) fp32 input of a conditional
+// encoder, the one-hot maps built in the pass that writes them
+bool bn_cond_input_ok(int N, int C, int H, int W, int L);
+int bn_launch_cond_input(const void* frames, int frames_is_u8, const float* coords, int ld, int N, int C, int H, int W,
+                         int L, float* out, hipStream_t st);
+
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);
 int bn_launch_bn_stats(const float* x, float* mean, float* var, int N, int C, int HW, void* ws,

@@ -1938,6 +1938,22 @@ extern "C" int bn_pixel_stats_accum(const float* xhat, const void* target, int t
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// The input of a conditional encoder (cond_input.hip): frames next to the one-hot maps of their label coordinates.
+extern "C" int bn_cond_encoder_input(const void* frames, int frames_is_u8, const float* coords, int ld, int n, int c,
+                                     int h, int w, int n_maps, float* out, bn_stream_t stream) {
+    if (n < 0 || c <= 0 || h <= 0 || w <= 0 || n_maps < 0 || (long)ld < 2L * n_maps ||
+        !bn_cond_input_ok(n, c, h, w, n_maps))
+        return BN_E_SHAPE;
+    if (n == 0) return 0;
+    // (without maps no coordinate is read)
+    if (!frames || !out || (n_maps > 0 && !coords)) return BN_E_BADARG;
+    // (fp32 operands that are not even 4-byte aligned cannot be read at all)
+    if (((uintptr_t)out & 3) || ((uintptr_t)coords & 3) || (!frames_is_u8 && ((uintptr_t)frames & 3)))
+        return BN_E_SHAPE;
+    return bn_launch_cond_input(frames, frames_is_u8, coords, ld, n, c, h, w, n_maps, out, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // fp32 unit-float frames -> stored uint8 grey levels (recon_u8.hip): NaN -> 0, else clamp(rint(x * 255), 0, 255).
 extern "C" int bn_unit_float_to_u8(const float* in, unsigned char* out, size_t n, bn_stream_t stream) {
     if (!in || !out) return BN_E_BADARG;

@@ -566,6 +566,8 @@ class ConcatSessionsGenerator(SyntheticSessionsGenerator):
                     # is not wrapped in a list before ``sample[signal][0]``): the mask of the
                     # trial's FIRST frame, (C, H, W); the losses broadcast it over the frames
                     a = a[0]
+                # (no transform: served as stored -- labels_sc under hip_label_maps = 'device' stays the (T, 2 L)
+                # coordinates, 8 KB a trial where MakeOneHot2D's dense maps take 67 MB; data/utils.py)
                 if tr:
                     a = tr(a)
                 return torch.from_numpy(np.ascontiguousarray(a)).float().to(device)

@@ -8,10 +8,24 @@ which signals a class reads from each session's ``data.hdf5`` (or its ``data.npz
 
 import os
 
-__all__ = ['get_data_generator_inputs', 'build_data_generator']
+__all__ = ['get_data_generator_inputs', 'build_data_generator', 'label_maps_of', 'LABEL_MAPS']
 
 _IMAGES_ONLY = ('ae', 'vae', 'beta-tcvae')
 _IMAGES_AND_LABELS = ('cond-ae', 'cond-ae-msp', 'cond-vae', 'ps-vae', 'msps-vae', 'labels-images')
+
+LABEL_MAPS = ('host', 'device')
+
+
+def label_maps_of(hparams):
+    """'host' (default) or 'device': ``hparams['hip_label_maps']``, else the environment's BN_LABEL_MAPS.  Where the
+    one-hot label maps of a conditional encoder are built: by ``MakeOneHot2D`` on the host, one dense (T, L, H, W)
+    array per trial (the reference's path), or on the device from the stored ``labels_sc`` coordinates, in the pass
+    that writes the encoder's input (``models.aes.encoder_input``) -- the same tensor either way."""
+    where = hparams.get('hip_label_maps', os.environ.get('BN_LABEL_MAPS', 'host'))
+    if where not in LABEL_MAPS:
+        raise ValueError("hparams['hip_label_maps'] (or BN_LABEL_MAPS) must be one of %s, got %r"
+                         % (LABEL_MAPS, where))
+    return where
 
 
 def get_data_generator_inputs(hparams, sess_ids, check_splits=True):
@@ -19,7 +33,8 @@ def get_data_generator_inputs(hparams, sess_ids, check_splits=True):
 
     images [+ masks if ``use_output_mask``] for ae / vae / beta-tcvae; images + labels
     [+ masks] [+ labels_masks if ``use_label_mask`` and the class is cond-ae-msp or ps-vae]
-    [+ labels_sc through ``MakeOneHot2D`` if ``conditional_encoder``] for the label-aware
+    [+ labels_sc through ``MakeOneHot2D`` -- or as stored with ``hip_label_maps = 'device'``, see
+    :func:`label_maps_of` -- if ``conditional_encoder``] for the label-aware
     classes.  Every signal of a session lives in ``data_dir/lab/expt/animal/session/data.hdf5``.
     """
     model_class = hparams['model_class']
@@ -27,6 +42,7 @@ def get_data_generator_inputs(hparams, sess_ids, check_splits=True):
         raise NotImplementedError(
             'model class "%s" is outside the MI355X autoencoder path (SURVEY.md section 2)' %
             model_class)
+    label_maps = label_maps_of(hparams)          # (an invalid key is an error whatever the class)
     signals_list, transforms_list, paths_list = [], [], []
     for sess_id in sess_ids:
         data_file = os.path.join(hparams['data_dir'], sess_id['lab'], sess_id['expt'],
@@ -45,7 +61,9 @@ def get_data_generator_inputs(hparams, sess_ids, check_splits=True):
             if hparams.get('conditional_encoder', False):
                 from behavenet_amd.data.transforms import MakeOneHot2D
                 signals.append('labels_sc')
-                transforms.append(MakeOneHot2D(hparams['y_pixels'], hparams['x_pixels']))
+                # ('device': the stored (T, 2 L) coordinates are served as they are and the maps built on the device)
+                transforms.append(None if label_maps == 'device' else
+                                  MakeOneHot2D(hparams['y_pixels'], hparams['x_pixels']))
         signals_list.append(signals)
         transforms_list.append(transforms)
         paths_list.append([data_file] * len(signals))

@@ -19,8 +19,10 @@ import torch
 
 from behavenet_amd import _hip
 from behavenet_amd.fitting import distributed as bdist
+from behavenet_amd.data.utils import label_maps_of
 from behavenet_amd.hip_functions import (DECODE_DTYPES, ENCODE_DTYPES, decode_precision, encode_precision,
                                          quantising_frames, scoring_frames)
+from behavenet_amd.models.aes import encoder_input
 
 __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconstruction', 'export_frame_errors',
            'frame_errors', 'frame_errors_device', 'export_reconstructions', 'reconstruct_trial',
@@ -56,6 +58,14 @@ def decode_dtype_of(model):
     return dtype
 
 
+def _wants_float_frames(model, labels_2d):
+    """Stored uint8 frames have to be converted before the model sees them: for the linear models, and where dense
+    label maps (N, L, H, W) are concatenated onto them.  Label coordinates (N, 2 L) leave them uint8
+    (``models.aes.encoder_input`` divides by 255 in the pass that builds the maps)."""
+    dense = labels_2d is not None and not (torch.is_tensor(labels_2d) and labels_2d.dim() == 2)
+    return dense or model.hparams.get('model_type', 'conv') != 'conv'
+
+
 def encode_trial_device(model, y, sess=None, labels_2d=None, chunk_size=200):
     """The same latents as a DEVICE tensor: nothing waits for the host (``export_latents`` keeps
     the trials' latents on the device and fetches them once at the end)."""
@@ -65,19 +75,17 @@ def encode_trial_device(model, y, sess=None, labels_2d=None, chunk_size=200):
 
 def _encode_trial_device(model, y, sess, labels_2d, chunk_size):
     mc = model.hparams['model_class']
-    if y.dtype == torch.uint8 and (labels_2d is not None or
-                                   model.hparams.get('model_type', 'conv') != 'conv'):
+    if y.dtype == torch.uint8 and _wants_float_frames(model, labels_2d):
         # (conv encoders take the stored uint8 frames as they are: value / 255 is fused into the
-        # first layer, csrc k_down_c1s<.., U8>; extra input channels need the float tensor)
+        # first layer, csrc k_down_c1s<.., U8>; dense label maps are concatenated onto the float tensor, label
+        # COORDINATES go with the uint8 frames into the one pass that builds the encoder's input)
         y = _hip.u8_to_unit_float(y.contiguous())
     n = y.shape[0]
     parts = []
     with torch.no_grad():
         for beg in range(0, n, chunk_size):
             end = min(beg + chunk_size, n)
-            y_in = y[beg:end]
-            if labels_2d is not None:
-                y_in = torch.cat((y_in, labels_2d[beg:end]), dim=1)
+            y_in = encoder_input(y[beg:end], None if labels_2d is None else labels_2d[beg:end])
             out = model.encoding(y_in, dataset=sess)
             if mc == 'ps-vae':
                 cur = torch.cat([out[0], out[1]], dim=1)
@@ -194,7 +202,10 @@ def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond
         can_skip = False
     skip = {'skip': (lambda s_, t_: owner.get((s_, int(t_)), rank) != rank)} \
         if (can_skip and world > 1) else {}
-    conv_u8 = model.hparams.get('model_type', 'conv') == 'conv' and not cond_enc
+    # (a conditional encoder takes them too once its label maps are built on the device: hip_label_maps = 'device';
+    # a generator that serves dense maps all the same is still served, models.aes.encoder_input converts for them)
+    conv_u8 = model.hparams.get('model_type', 'conv') == 'conv' and \
+        (not cond_enc or label_maps_of(model.hparams) == 'device')
     serve_prev = getattr(data_generator, 'serve_uint8', None)
     if serve_prev is not None and conv_u8:
         data_generator.serve_uint8 = True
@@ -378,7 +389,7 @@ def _frame_errors_device(model, y, sess, masks, labels, labels_2d, chunk_size, f
     # (conv encoders take the stored uint8 frames as they are, as in _encode_trial_device; the TARGET stays
     # uint8 either way: the kernels divide by 255 as bn_u8_to_unit_float does)
     x = y
-    if y.dtype == torch.uint8 and (labels_2d is not None or model.hparams.get('model_type', 'conv') != 'conv'):
+    if y.dtype == torch.uint8 and _wants_float_frames(model, labels_2d):
         x = _hip.u8_to_unit_float(y)
     kwargs = _forward_kwargs(cls, sess)
     out = torch.empty((n,), dtype=torch.float32, device=y.device)
@@ -473,7 +484,7 @@ def _reconstruct_trial_device(model, y, sess, labels, labels_2d, chunk_size, fus
     x = y.contiguous()
     n = x.shape[0]
     # (conv encoders take the stored uint8 frames as they are, as in _encode_trial_device)
-    if x.dtype == torch.uint8 and (labels_2d is not None or model.hparams.get('model_type', 'conv') != 'conv'):
+    if x.dtype == torch.uint8 and _wants_float_frames(model, labels_2d):
         x = _hip.u8_to_unit_float(x)
     kwargs = _forward_kwargs(cls, sess)
     out = None
@@ -667,7 +678,7 @@ def _pixel_stats_device(model, y, sess, masks, labels, labels_2d, chunk_size, ou
     # (conv encoders take the stored uint8 frames as they are, as in _encode_trial_device; the TARGET stays
     # uint8 either way: the kernel divides by 255 as bn_u8_to_unit_float does)
     x = y
-    if y.dtype == torch.uint8 and (labels_2d is not None or model.hparams.get('model_type', 'conv') != 'conv'):
+    if y.dtype == torch.uint8 and _wants_float_frames(model, labels_2d):
         x = _hip.u8_to_unit_float(y)
     kwargs = _forward_kwargs(cls, sess)
     with torch.no_grad():

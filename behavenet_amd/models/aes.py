@@ -30,7 +30,7 @@ from behavenet_amd.hip_functions import (
 __all__ = [
     'ConvAEEncoder', 'ConvAEDecoder', 'LinearAEEncoder', 'LinearAEDecoder', 'AE', 'ConditionalAE',
     'AEMSP',
-    'load_pretrained_ae']
+    'load_pretrained_ae', 'encoder_input']
 
 
 def _mark_footprint(module):
@@ -50,6 +50,25 @@ def _no_sharded_chunk_loop(model):
         raise NotImplementedError(
             'frame-sharded data parallelism of %s with ae_batch_norm=1 is not implemented '
             '(use dp_shard="trial", or the plain AE)' % type(model).__name__)
+
+
+def encoder_input(x, labels_2d):
+    """What the encoder sees: the frames ``x`` (N, C, H, W) with the labels' maps as extra input channels (ref
+    aes.py:818-826).  ``labels_2d`` is None (-> ``x`` as it is), the dense one-hot maps (N, L, H, W) the
+    ``MakeOneHot2D`` transform serves (-> ``torch.cat``; uint8 frames are converted first), or the stored ``labels_sc``
+    coordinates (N, 2 L) themselves: then the maps are built on the device in the pass that writes the input
+    (``_hip.cond_encoder_input``; uint8 frames are divided by 255 in the same pass) -- the same tensor, bit for bit.
+    No gradient flows into either argument."""
+    if labels_2d is None:
+        return x
+    if not torch.is_tensor(labels_2d) or labels_2d.dim() not in (2, 4):
+        raise ValueError('labels_2d: expected one-hot maps (N, L, H, W) or coordinates (N, 2 L), got %s'
+                         % (tuple(labels_2d.shape) if torch.is_tensor(labels_2d) else type(labels_2d).__name__,))
+    if labels_2d.dim() == 4:
+        if x.dtype == torch.uint8:
+            x = _hip.u8_to_unit_float(x.contiguous())
+        return torch.cat((x, labels_2d), dim=1)
+    return _hip.cond_encoder_input(x, labels_2d)
 
 
 def frame_masks(data, x):
@@ -860,7 +879,7 @@ class ConditionalAE(AE):
 
     def forward(self, x, dataset=None, labels=None, labels_2d=None, **kwargs):
         if self.hparams.get('conditional_encoder', False):
-            x = torch.cat((x, labels_2d), dim=1)
+            x = encoder_input(x, labels_2d)
         z, pool_idx, outsize = self.encoding(x, dataset=dataset)
         z_aug = torch.cat((z, labels), dim=1)
         y = self.decoding(z_aug, pool_idx, outsize, dataset=dataset,

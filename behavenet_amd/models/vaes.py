@@ -23,7 +23,7 @@ from behavenet_amd import hip_functions as hf
 from behavenet_amd.fitting import distributed as bdist
 from behavenet_amd.hip_functions import linear
 from behavenet_amd.models.aes import (
-    AE, ConvAEDecoder, ConvAEEncoder, _no_sharded_chunk_loop, frame_masks)
+    AE, ConvAEDecoder, ConvAEEncoder, _no_sharded_chunk_loop, encoder_input, frame_masks)
 from behavenet_amd.models.base import DiagLinear
 
 __all__ = [
@@ -337,7 +337,7 @@ class ConditionalVAE(VAE):
 
     def forward(self, x, dataset=None, labels=None, labels_2d=None, use_mean=False, **kwargs):
         if self.hparams['conditional_encoder']:
-            x = torch.cat((x, labels_2d), dim=1)
+            x = encoder_input(x, labels_2d)
         mu, logvar, pool_idx, outsize = self.encoding(x, dataset=dataset)
         z = _sample(mu, logvar, use_mean, kwargs.get('sample_bounds'), kwargs.get('sample_shards'))
         z_aug = torch.cat((z, labels), dim=1)

@@ -550,6 +550,24 @@ int bn_pixel_stats_accum(const float* xhat, const void* target, int target_is_u8
  * data_generator.py:251-263 for device-resident uint8 trials) */
 int bn_u8_to_unit_float(const unsigned char* in, float* out, size_t n, bn_stream_t stream);
 
+/* The input of a conditional encoder in one pass (replaces the host-side MakeOneHot2D of
+ * data/transforms.py:186-245 and the torch.cat of aes.py:818-826): out fp32 (n, c + n_maps, h, w),
+ *   out[i, k]         = frames[i, k]            k < c: fp32 frames (n, c, h, w) copied; with frames_is_u8
+ *                                               uint8 frames, value / 255 (the division of bn_u8_to_unit_float)
+ *   out[i, c + l]     = zeros but for one 1.0f at (y, x)                              l < n_maps
+ * where x = pixel(coords[i * ld + l], w) and y = pixel(coords[i * ld + n_maps + l], h), and pixel(v, size)
+ * is the transform's rule: NaN counts as 0, clip to [0, size - 1], round half to even.  coords fp32 (n, ld),
+ * ld >= 2 * n_maps; columns from 2 * n_maps on are not read.  The coordinates are read on the device: no
+ * host read, no synchronisation, capturable in a graph.  Every output byte is written once, by plain
+ * stores; no atomics.  16-byte stores with 16-byte (uint8 frames: 4-byte) loads where h * w is a multiple
+ * of 4 and `out` sits on a 16-byte and `frames` on a 16-byte (uint8: 4-byte) boundary, element by element
+ * otherwise, with the same values.
+ * n_maps == 0 is the plain conversion (coords is not read and may be NULL); n == 0 returns 0 and launches
+ * nothing.  BN_E_SHAPE (nothing written): n < 0, c, h or w <= 0, n_maps < 0, ld < 2 * n_maps, an output of
+ * more than 2^40 elements, fp32 operands off a 4-byte boundary.  BN_E_BADARG: a NULL pointer (n > 0). */
+int bn_cond_encoder_input(const void* frames, int frames_is_u8, const float* coords, int ld,
+                          int n, int c, int h, int w, int n_maps, float* out, bn_stream_t stream);
+
 /* unit-float frames -> stored uint8 grey levels, the inverse of bn_u8_to_unit_float on k / 255:
  *   out[i] = NaN -> 0, else clamp(rint(in[i] * 255), 0, 255)
  * The product is one fp32 multiplication and rint rounds half to even, i.e. numpy's
