@@ -9,6 +9,7 @@ contiguous fp32 device tensor, the call raises.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 _LIB_NAME = 'libbehavenet_hip.so'
@@ -143,6 +144,7 @@ SIGNATURES = {
     'bn_u8_to_unit_float': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     'bn_unit_float_to_u8': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     'bn_cond_encoder_input': (_c_int, [_c_void_p, _c_int, _c_void_p] + [_c_int] * 6 + [_c_void_p, _c_void_p]),
+    'bn_frame_mosaic_u8': (_c_int, [_c_void_p] + [_c_int] * 10 + [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
     'bn_prof_read': (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
@@ -1078,6 +1080,66 @@ def cond_encoder_input(x, coords, n_maps=None):
     _check(load().bn_cond_encoder_input(
         _ptr(x, 'frames', dtype=x.dtype), int(x.dtype == torch.uint8), _ptr(coords, 'coords'), int(coords.shape[1]),
         N, C, H, W, n_maps, _ptr(out, 'out'), _stream()), 'bn_cond_encoder_input')
+    return out
+
+
+def check_mosaic_args(shape, ch=0, crop=None):
+    """The crop window ``(y_min, x_min, Hc, Wc)`` of a mosaic of frames of ``shape`` (P, C, H, W) -- ``crop`` or the
+    whole frame -- after the checks that need no device: ``ValueError`` for a channel outside [0, C), a negative
+    origin (a numpy slice would wrap there) or an empty window."""
+    if len(shape) != 4:
+        raise ValueError('frame_mosaic_u8: expected frames (P, C, H, W), got %s' % (tuple(shape),))
+    P, C, H, W = (int(v) for v in shape)
+    if not 0 <= int(ch) < C:
+        raise ValueError('frame_mosaic_u8: channel %d of frames with %d channels' % (ch, C))
+    y_min, x_min, Hc, Wc = (0, 0, H, W) if crop is None else (int(v) for v in crop)
+    if y_min < 0 or x_min < 0:
+        raise ValueError('frame_mosaic_u8: the crop window starts at (%d, %d); a negative origin is not served '
+                         '(the reference\'s numpy slice wraps there)' % (y_min, x_min))
+    if Hc <= 0 or Wc <= 0:
+        raise ValueError('frame_mosaic_u8: the crop window is %d x %d pixels' % (Hc, Wc))
+    return y_min, x_min, Hc, Wc
+
+
+def check_mosaic_src(src, n_frames):
+    """``src`` as a contiguous int32 numpy array (T, R, Cc) of frame indices below ``n_frames``, -1 (any negative
+    value) for a blank panel; ``ValueError`` otherwise.  Checked on the host, before the upload."""
+    src = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
+    if src.ndim == 2:
+        src = src[None]
+    if src.ndim != 3:
+        raise ValueError('frame_mosaic_u8: expected src (T, R, Cc) or (R, Cc), got %s' % (src.shape,))
+    if src.size and int(src.max()) >= n_frames:
+        raise ValueError('frame_mosaic_u8: src names frame %d of %d' % (int(src.max()), n_frames))
+    return np.maximum(src, -1).astype(np.int32)
+
+
+def frame_mosaic_u8(frames, src, ch=0, crop=None):
+    """Frames (P, C, H, W), fp32 unit floats or uint8 grey levels, -> the uint8 DEVICE mosaic (T, R * Hc, Cc * Wc)
+    whose panel (t, r, c) shows channel ``ch`` of frame ``src[t, r, c]`` inside the window ``crop = (y_min, x_min, Hc,
+    Wc)`` (default: the whole frame), zero where the window passes the bottom or right edge and where ``src`` is
+    negative.  fp32 frames are quantised by ``unit_float_to_u8``'s rule.  ``src``: a host array (T, R, Cc) or (R, Cc),
+    checked against P here and uploaded, or an int32 device tensor (T, R, Cc) the caller has checked
+    (``check_mosaic_src``).  One pass on the current stream (csrc/frame_mosaic.hip)."""
+    if not torch.is_tensor(frames) or frames.dim() != 4:
+        raise ValueError('frame_mosaic_u8: expected frames (P, C, H, W), got %s'
+                         % (tuple(frames.shape) if torch.is_tensor(frames) else type(frames).__name__,))
+    if frames.dtype not in (torch.uint8, torch.float32):
+        raise ValueError('frame_mosaic_u8: frames must be uint8 or float32, got %s' % frames.dtype)
+    y_min, x_min, Hc, Wc = check_mosaic_args(frames.shape, ch, crop)
+    if not torch.is_tensor(src):
+        src = torch.from_numpy(check_mosaic_src(src, frames.shape[0])).to(frames.device)
+    if src.dim() != 3 or src.dtype != torch.int32:
+        raise ValueError('frame_mosaic_u8: a device src must be int32 (T, R, Cc), got %s %s'
+                         % (src.dtype, tuple(src.shape)))
+    frames, src = frames.contiguous(), src.contiguous()
+    P, C, H, W = frames.shape
+    T, R, Cc = src.shape
+    out = torch.empty((T, R * Hc, Cc * Wc), dtype=torch.uint8, device=frames.device)
+    _check(load().bn_frame_mosaic_u8(
+        _ptr(frames, 'frames', dtype=frames.dtype), int(frames.dtype == torch.uint8), P, C, H, W, int(ch), y_min,
+        x_min, Hc, Wc, _ptr(src, 'src', dtype=torch.int32), T, R, Cc, _ptr(out, 'out', dtype=torch.uint8), _stream()),
+        'bn_frame_mosaic_u8')
     return out
 
 

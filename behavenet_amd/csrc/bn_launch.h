@@ -87,6 +87,12 @@ bool bn_cond_input_ok(int N, int C, int H, int W, int L);
 int bn_launch_cond_input(const void* frames, int frames_is_u8, const float* coords, int ld, int N, int C, int H, int W,
                          int L, float* out, hipStream_t st);
 
+// frame_mosaic.hip: one channel of frames (fp32 unit floats or uint8 grey levels), cropped, quantised and tiled into
+// a (T, R Hc, Cc Wc) uint8 mosaic by a device table of source frames (-1: a blank panel)
+bool bn_frame_mosaic_ok(int P, int C, int H, int W, int ch, int y_min, int x_min, int Hc, int Wc, int T, int R, int Cc);
+int bn_launch_frame_mosaic(const void* frames, int frames_u8, int P, int C, int H, int W, int ch, int y_min, int x_min,
+                           int Hc, int Wc, const int* src, int T, int R, int Cc, unsigned char* out, hipStream_t st);
+
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);
 int bn_launch_bn_stats(const float* x, float* mean, float* var, int N, int C, int HW, void* ws,

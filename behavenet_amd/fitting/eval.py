@@ -1,6 +1,7 @@
 """Inference-only passes over every trial: latents -> ``*_latents.pkl`` (BASELINE config 5), per-frame
 reconstruction errors -> ``*_frame_errors.pkl``, uint8 reconstructions -> ``*_reconstructions.npz`` and per-pixel
-error / moment maps -> ``*_pixel_stats.pkl``.
+error / moment maps -> ``*_pixel_stats.pkl``; and latent traversals as uint8 mosaics and movies, decoded in one batch
+and tiled on the device.
 
 Mirror of ``export_latents`` in the reference ``behavenet/fitting/eval.py:6-118``: same pickle
 schema ``{'latents': [per-trial (T x D) arrays, empty for gap trials], 'trials': batch_idxs}``
@@ -27,7 +28,8 @@ from behavenet_amd.models.aes import encoder_input
 __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconstruction', 'export_frame_errors',
            'frame_errors', 'frame_errors_device', 'export_reconstructions', 'reconstruct_trial',
            'reconstruct_trial_device', 'export_pixel_stats', 'pixel_stats', 'pixel_stats_device',
-           'summarise_pixel_stats']
+           'summarise_pixel_stats', 'traversal_points', 'traverse_latents', 'traverse_latents_device',
+           'traversal_movie', 'traversal_movie_device']
 
 
 def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -825,3 +827,201 @@ def export_pixel_stats(data_generator, model, filename=None):
             pickle.dump({'stats': stats, 'n_frames': frames, 'summary': summary, 'trials': dataset.batch_idxs}, f)
         filenames.append(out)
     return filenames
+
+
+# ------------------------------------------------------------------------------------------ latent traversals
+def traversal_points(base, mins, maxes, input_idxs, n_frames, mode='1d'):
+    """The points of a latent (or label) traversal as one float32 table ``(P, D)`` -> ``(table, (rows, cols))``:
+    the values of the reference's ``interpolate_1d`` / ``interpolate_2d`` (plotting/cond_ae_utils.py), every row a
+    copy of ``base`` -- (D,) or (1, D) -- with the swept dimensions overwritten by
+    ``vals[k] = np.linspace(mins[input_idxs[k]], maxes[input_idxs[k]], n_frames)`` and cast to float32 as
+    ``torch.from_numpy(...).float()`` casts.  Panel (i0, i1) is row ``i0 * cols + i1``.
+
+    ``mode='1d'``: ``rows = len(input_idxs)``, ``cols = n_frames``; panel (i0, i1) changes dimension ``input_idxs[i0]``
+    to ``vals[i0][i1]``.  ``mode='2d'``: exactly two indices, ``rows = cols = n_frames``; panel (i0, i1) sets
+    ``input_idxs[0]`` to ``vals[0][i0]`` and ``input_idxs[1]`` to ``vals[1][i1]``.  Host numpy: the table is a few KB
+    and is uploaded once."""
+    base = np.asarray(base)
+    if base.ndim == 2 and base.shape[0] == 1:
+        base = base[0]
+    if base.ndim != 1:
+        raise ValueError('traversal_points: expected one base point (D,) or (1, D), got %s' % (base.shape,))
+    input_idxs = [int(d) for d in input_idxs]
+    n_frames = int(n_frames)
+    if n_frames < 1:
+        raise ValueError('traversal_points: n_frames must be at least 1, got %d' % n_frames)
+    if mode not in ('1d', '2d'):
+        raise ValueError("traversal_points: mode must be '1d' or '2d', got %r" % (mode,))
+    if mode == '2d' and len(input_idxs) != 2:
+        raise ValueError('traversal_points: a 2-d traversal sweeps exactly two dimensions, got %d' % len(input_idxs))
+    for d in input_idxs:
+        if not 0 <= d < base.shape[0]:
+            raise ValueError('traversal_points: dimension %d of a base point with %d' % (d, base.shape[0]))
+    vals = [np.linspace(mins[d], maxes[d], n_frames) for d in input_idxs]
+    rows, cols = (len(input_idxs), n_frames) if mode == '1d' else (n_frames, n_frames)
+    # (the assignment casts the float64 values to the base's dtype, as the reference's does)
+    table = np.repeat(base[None, :], rows * cols, axis=0).reshape(rows, cols, base.shape[0])
+    if mode == '1d':
+        for i0, d in enumerate(input_idxs):
+            table[i0, :, d] = vals[i0]
+    else:
+        table[:, :, input_idxs[0]] = vals[0][:, None]
+        table[:, :, input_idxs[1]] = vals[1][None, :]
+    return np.ascontiguousarray(table.reshape(rows * cols, base.shape[0]).astype(np.float32)), (rows, cols)
+
+
+def _crop_window(crop_kwargs):
+    """``(y_min, x_min, Hc, Wc)`` of the reference's ``crop_kwargs`` (keys x_0, x_ext, y_0, y_ext: the window
+    [y_0 - y_ext, y_0 + y_ext) x [x_0 - x_ext, x_0 + x_ext) of ``get_crop``), or the whole frame for None."""
+    if not crop_kwargs:
+        return None
+    y_0, y_ext, x_0, x_ext = (int(crop_kwargs[k]) for k in ('y_0', 'y_ext', 'x_0', 'x_ext'))
+    return y_0 - y_ext, x_0 - x_ext, 2 * y_ext, 2 * x_ext
+
+
+def _point_labels(model, labels, n):
+    """(n, L) fp32 device labels for the conditional classes from one row (1, L) / (L,) or one per point; else None."""
+    if model.hparams['model_class'] not in ('cond-ae', 'cond-vae'):
+        return None
+    if labels is None:
+        raise ValueError('a %s decodes latents together with labels: labels_0 is needed'
+                         % model.hparams['model_class'])
+    dev = next(model.parameters()).device
+    labels = labels if torch.is_tensor(labels) else torch.from_numpy(np.asarray(labels))
+    labels = labels.to(dev).float()
+    if labels.dim() == 1:
+        labels = labels[None]
+    if labels.shape[0] == 1:
+        labels = labels.expand(n, labels.shape[1])
+    if labels.dim() != 2 or labels.shape[0] != n:
+        raise ValueError('expected labels (1, L) or (%d, L), got %s' % (n, tuple(labels.shape)))
+    return labels
+
+
+def decode_points_device(model, points, labels=None, apply_inverse_transform=True, chunk_size=200):
+    """A table of latents ``(P, D)`` through the path ``get_reconstruction`` takes for 2-D inputs, in chunks of
+    ``chunk_size`` points, the frames left on the DEVICE: cond-AE / cond-VAE get ``labels`` (one row for all, or one
+    per point) appended, AEMSP / PS-VAE / MSPS-VAE latents are mapped back (``apply_inverse_transform``).  Eval mode,
+    ``no_grad``.  Returns ``(P, C, H, W)`` fp32 unit floats -- or, under ``hparams['hip_decode_dtype'] = 'bf16'`` on a
+    served decoder, the uint8 grey levels its last layer writes (``quantising_frames``)."""
+    cls = model.hparams['model_class']
+    if cls not in _LATENTS_AT:
+        raise ValueError('Invalid model class %s' % cls)
+    model.eval()
+    dev = next(model.parameters()).device
+    t = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32))
+    t = t.to(dev).float()
+    if t.dim() != 2:
+        raise ValueError('expected a table of points (P, D), got %s' % (tuple(t.shape),))
+    n = t.shape[0]
+    labels = _point_labels(model, labels, n)
+    dtype = decode_dtype_of(model)
+    parts = []
+    with torch.no_grad(), decode_precision(dtype):
+        for beg in range(0, n, chunk_size):
+            z = t[beg:beg + chunk_size]
+            if labels is not None:
+                z = torch.cat((z, labels[beg:beg + chunk_size]), dim=1)
+            elif cls in ('cond-ae-msp', 'ps-vae', 'msps-vae') and apply_inverse_transform:
+                z = model.get_inverse_transformed_latents(z, as_numpy=False)
+            with (quantising_frames() if dtype == 'bf16' else contextlib.nullcontext()) as req:
+                x_hat = model.decoding(z, None, None, dataset=None)
+            parts.append(req.frames if req is not None and req.frames is not None else x_hat)
+    if not parts:
+        raise ValueError('a traversal needs at least one point')
+    if len(set(p.dtype for p in parts)) != 1:          # (a decoder is served for every chunk or for none)
+        parts = [p if p.dtype == torch.uint8 else _hip.unit_float_to_u8(p.contiguous()) for p in parts]
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+
+def traverse_latents_device(model, latents_0, mins, maxes, input_idxs, n_frames, mode='1d', labels_0=None,
+                            apply_inverse_transform=True, crop_kwargs=None, ch=0, chunk_size=200):
+    """A latent traversal as ONE uint8 DEVICE image ``(rows * Hc, cols * Wc)``: what the reference shows with
+    ``interpolate_1d`` / ``interpolate_2d`` + ``plot_1d_frame_array`` / ``plot_2d_frame_array``
+    (plotting/cond_ae_utils.py) after P single-frame ``get_reconstruction`` calls and P copies to the host.
+
+    ``traversal_points`` makes the ``(P, D)`` table from ``latents_0``, ``decode_points_device`` decodes it in one
+    batch, and one launch (``bn_frame_mosaic_u8``) picks channel ``ch``, crops to ``crop_kwargs`` (the reference's
+    keys x_0, x_ext, y_0, y_ext; zero-filled past the bottom and right edge as ``get_crop`` fills; a negative origin
+    is a ValueError), quantises (``unit_float_to_u8``'s rule) and tiles panel (i0, i1) at row i0, column i1.  Only
+    the image crosses to the host.  ``labels_0``: the labels of a cond-AE / cond-VAE.
+
+    The bytes are the quantised frames of the decoder called on each chunk.  Where the fp32 decoder's kernels choose
+    their route by the batch size (2x128x128 frames: batches up to 16 against 24 and more), a frame's x_hat moves in
+    its last bits with ``chunk_size`` and with P, as ``get_reconstruction``'s does, and a grey level may turn where
+    ``x_hat * 255`` lies at a half."""
+    table, (rows, cols) = traversal_points(latents_0, mins, maxes, input_idxs, n_frames, mode)
+    dim = (table.shape[0], int(model.hparams['n_input_channels']), int(model.hparams['y_pixels']),
+           int(model.hparams['x_pixels']))
+    crop = _crop_window(crop_kwargs)
+    _hip.check_mosaic_args(dim, ch, crop)          # (argument errors before anything is decoded)
+    frames = decode_points_device(model, table, labels_0, apply_inverse_transform, chunk_size)
+    src = np.arange(rows * cols, dtype=np.int32).reshape(1, rows, cols)
+    return _hip.frame_mosaic_u8(frames, src, ch, crop)[0]
+
+
+def traverse_latents(model, latents_0, mins, maxes, input_idxs, n_frames, mode='1d', labels_0=None,
+                     apply_inverse_transform=True, crop_kwargs=None, ch=0, chunk_size=200):
+    """``traverse_latents_device`` as a numpy array ``(rows * Hc, cols * Wc)`` of uint8."""
+    return traverse_latents_device(model, latents_0, mins, maxes, input_idxs, n_frames, mode, labels_0,
+                                   apply_inverse_transform, crop_kwargs, ch, chunk_size).cpu().numpy()
+
+
+def movie_src(n_base, n_dims, n_frames, n_cols, beg=0, end=None):
+    """The source table ``(end - beg, n_rows, n_cols)`` of movie frames ``[beg, end)``: at time ``b * n_frames + i``
+    panel ``k`` -- row ``k // n_cols``, column ``k % n_cols`` -- shows point ``(b * n_dims + k) * n_frames + i`` of the
+    movie's table; panels from ``n_dims`` on are blank (-1)."""
+    end = n_base * n_frames if end is None else end
+    n_rows = -(-n_dims // n_cols)
+    t = np.arange(beg, end)
+    b, i = t // n_frames, t % n_frames
+    src = np.full((end - beg, n_rows * n_cols), -1, dtype=np.int32)
+    src[:, :n_dims] = (b[:, None] * n_dims + np.arange(n_dims)[None, :]) * n_frames + i[:, None]
+    return src.reshape(end - beg, n_rows, n_cols)
+
+
+def traversal_movie_device(model, base_latents, mins, maxes, input_idxs, n_frames, n_cols=None, labels_0=None,
+                           apply_inverse_transform=True, crop_kwargs=None, ch=0, chunk_size=200):
+    """The frames of the reference's latent traversal movie (``make_latent_traversal_movie``,
+    plotting/cond_ae_utils.py) as a uint8 DEVICE tensor ``(B * n_frames, n_rows * Hc, n_cols * Wc)``: one panel per
+    swept dimension, row-major in ``n_cols`` columns (default 3, the reference's) and ``n_rows = ceil(K / n_cols)``
+    rows, trailing panels blank (zeros); the base points ``base_latents`` (B, D) follow each other in time.  At time
+    ``b * n_frames + i`` panel ``k`` shows base ``b`` with dimension ``input_idxs[k]`` at
+    ``np.linspace(mins[d], maxes[d], n_frames)[i]``.
+
+    All ``B * K * n_frames`` points are decoded in one batched pass (``decode_points_device``) and tiled by one
+    mosaic launch per ``chunk_size`` movie frames; only the movie crosses to the host.  ``labels_0``: (1, L) or
+    (B, L) labels of a cond-AE / cond-VAE; the other arguments as in ``traverse_latents_device``."""
+    base = np.asarray(base_latents)
+    if base.ndim == 1:
+        base = base[None]
+    if base.ndim != 2 or base.shape[0] < 1:
+        raise ValueError('traversal_movie: expected base points (B, D), got %s' % (base.shape,))
+    n_base, n_dims = base.shape[0], len(input_idxs)
+    n_cols = 3 if n_cols is None else int(n_cols)
+    if n_dims < 1 or n_cols < 1:
+        raise ValueError('traversal_movie: %d swept dimensions in %d columns' % (n_dims, n_cols))
+    tables = [traversal_points(b, mins, maxes, input_idxs, n_frames, '1d')[0] for b in base]
+    table = np.concatenate(tables, axis=0)
+    per_base = n_dims * int(n_frames)
+    dim = (table.shape[0], int(model.hparams['n_input_channels']), int(model.hparams['y_pixels']),
+           int(model.hparams['x_pixels']))
+    crop = _crop_window(crop_kwargs)
+    _hip.check_mosaic_args(dim, ch, crop)
+    labels = _point_labels(model, labels_0, n_base)
+    if labels is not None:
+        labels = labels.repeat_interleave(per_base, dim=0)
+    frames = decode_points_device(model, table, labels, apply_inverse_transform, chunk_size)
+    n_t = n_base * int(n_frames)
+    parts = []
+    for beg in range(0, n_t, chunk_size):          # (one launch per chunk of time)
+        src = movie_src(n_base, n_dims, int(n_frames), n_cols, beg, min(beg + chunk_size, n_t))
+        parts.append(_hip.frame_mosaic_u8(frames, src, ch, crop))
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+
+def traversal_movie(model, base_latents, mins, maxes, input_idxs, n_frames, n_cols=None, labels_0=None,
+                    apply_inverse_transform=True, crop_kwargs=None, ch=0, chunk_size=200):
+    """``traversal_movie_device`` as a numpy array ``(B * n_frames, n_rows * Hc, n_cols * Wc)`` of uint8."""
+    return traversal_movie_device(model, base_latents, mins, maxes, input_idxs, n_frames, n_cols, labels_0,
+                                  apply_inverse_transform, crop_kwargs, ch, chunk_size).cpu().numpy()

@@ -1,0 +1,142 @@
+"""Latent and label traversals with the reference's signatures (``behavenet/plotting/cond_ae_utils.py``:
+``interpolate_1d``, ``interpolate_2d``), decoded in ONE batch.
+
+The reference calls ``get_reconstruction`` once per point: P launch chains of one frame and P copies to the host.
+Here the points are collected into one table (``fitting.eval.traversal_points``) and ``get_reconstruction`` is called
+once on it; the lists that come back have the reference's nesting and dtypes.  For an image instead of lists --
+cropped, quantised and tiled on the device, with only the uint8 result crossing to the host -- see
+``fitting.eval.traverse_latents`` and ``traversal_movie``.  Nothing here imports matplotlib."""
+
+import numpy as np
+import torch
+
+from behavenet_amd.fitting.eval import get_reconstruction, traversal_points
+from behavenet_amd.plotting import get_crop
+
+__all__ = ['interpolate_1d', 'interpolate_2d']
+
+_PLAIN = ('ae', 'vae', 'beta-tcvae', 'ps-vae', 'msps-vae')
+_COND = ('cond-ae', 'cond-vae')
+_MSP = ('cond-ae-msp', 'ps-vae', 'msps-vae')
+
+
+def _get_updated_scaled_labels(labels_og, idxs=None, vals=None):
+    """A copy ``(1, n)`` of the scaled labels with ``labels_sc[0, idx] = val`` for every pair of ``idxs`` / ``vals``
+    (one int and one float, or two sequences of equal length); None stays None.  4-d one-hot maps ``(1, L, H, W)``
+    are read back as coordinates first: the x of every hot pixel, then the y (ref cond_ae_utils.py:847-874)."""
+    if labels_og is None:
+        return None
+    labels_og = np.asarray(labels_og)
+    if labels_og.ndim == 4:
+        _, y, x = np.where(labels_og[0] == 1)
+        labels_sc = np.hstack([x, y])[None, :]
+    else:
+        labels_sc = np.copy(labels_og)
+    if idxs is not None:
+        if isinstance(idxs, (int, np.integer)):
+            assert isinstance(vals, (float, np.floating))
+            idxs, vals = [idxs], [vals]
+        assert len(idxs) == len(vals)
+        for idx, val in zip(idxs, vals):
+            labels_sc[0, idx] = val
+    return labels_sc
+
+
+def _device_of(model):
+    return next(model.parameters()).device
+
+
+def _interpolate(mode, interp_type, model, ims_0, latents_0, labels_0, labels_sc_0, mins, maxes, input_idxs, n_frames,
+                 crop_type, mins_sc, maxes_sc, crop_kwargs, marker_idxs, ch):
+    cls = model.hparams['model_class']
+    if interp_type not in ('latents', 'labels'):
+        raise NotImplementedError('interp_type must be "latents" or "labels", got %r' % (interp_type,))
+    if mode == '2d':
+        assert len(input_idxs) == 2
+    inputs_sc = None
+    if mins_sc is not None and maxes_sc is not None:
+        inputs_sc = [np.linspace(mins_sc[d], maxes_sc[d], n_frames) for d in input_idxs]
+    elif interp_type == 'labels':
+        raise NotImplementedError('interpolating labels needs mins_sc and maxes_sc')
+    if interp_type == 'latents' and cls not in _PLAIN + _COND + ('cond-ae-msp',):
+        raise NotImplementedError('model class %s' % cls)
+    if interp_type == 'labels' and cls not in _MSP and np.ndim(labels_sc_0) == 4:
+        raise NotImplementedError(
+            'interpolating the labels of a %s with 4-d labels_sc_0 (a conditional encoder) is not served: the maps '
+            'of every point would have to be built and sent through the encoder; pass 1-d scaled labels' % cls)
+
+    # every point of the traversal in one table, one batched decode
+    if interp_type == 'latents' or cls in _MSP:
+        table, (rows, cols) = traversal_points(latents_0, mins, maxes, input_idxs, n_frames, mode)
+        labels = None
+        if cls in _COND:
+            labels = torch.from_numpy(np.asarray(labels_0)).float().to(_device_of(model)).expand(table.shape[0], -1)
+        ims = get_reconstruction(model, table, labels=labels, apply_inverse_transform=True)
+    else:
+        table, (rows, cols) = traversal_points(labels_0, mins, maxes, input_idxs, n_frames, mode)
+        ims_rep = ims_0.to(_device_of(model)).expand(table.shape[0], -1, -1, -1).contiguous()
+        ims = get_reconstruction(model, ims_rep, labels=torch.from_numpy(table).to(_device_of(model)), labels_2d=None)
+
+    y_min = crop_kwargs['y_0'] - crop_kwargs['y_ext'] if crop_type else 0
+    x_min = crop_kwargs['x_0'] - crop_kwargs['x_ext'] if crop_type else 0
+    ims_list, labels_list, ims_crop_list = [], [], []
+    for i0 in range(rows):
+        ims_tmp, labels_tmp, ims_crop_tmp = [], [], []
+        for i1 in range(cols):
+            im = ims[i0 * cols + i1]
+            ims_tmp.append(np.copy(im[ch]))
+            if interp_type == 'labels':
+                if mode == '1d':
+                    labels_sc = _get_updated_scaled_labels(labels_sc_0, input_idxs[i0], inputs_sc[i0][i1])
+                else:
+                    labels_sc = _get_updated_scaled_labels(
+                        labels_sc_0, input_idxs, [inputs_sc[0][i0], inputs_sc[1][i1]])
+                labels_tmp.append([np.copy(labels_sc[0, input_idxs[0]]) - y_min,
+                                   np.copy(labels_sc[0, input_idxs[1]]) - x_min])
+            elif labels_sc_0 is not None:
+                labels_sc = _get_updated_scaled_labels(labels_sc_0)
+                labels_tmp.append([np.copy(labels_sc[0, marker_idxs[0]]) - y_min,
+                                   np.copy(labels_sc[0, marker_idxs[1]]) - x_min])
+            else:
+                labels_tmp.append([np.nan, np.nan])
+            if crop_type:
+                # (the reference crops channel 0 whatever ``ch`` says; kept)
+                ims_crop_tmp.append(get_crop(
+                    im[0], crop_kwargs['y_0'], crop_kwargs['y_ext'], crop_kwargs['x_0'], crop_kwargs['x_ext']))
+            else:
+                ims_crop_tmp.append([])
+        ims_list.append(ims_tmp)
+        labels_list.append(labels_tmp)
+        ims_crop_list.append(ims_crop_tmp)
+    return ims_list, labels_list, ims_crop_list
+
+
+def interpolate_2d(
+        interp_type, model, ims_0, latents_0, labels_0, labels_sc_0, mins, maxes, input_idxs,
+        n_frames, crop_type=None, mins_sc=None, maxes_sc=None, crop_kwargs=None,
+        marker_idxs=None, ch=0):
+    """Reconstructions on the ``n_frames x n_frames`` grid spanned by two latents (``interp_type='latents'``) or two
+    labels (``'labels'``) between ``mins`` and ``maxes``, the reference's ``interpolate_2d`` (cond_ae_utils.py:346-540)
+    with its parameters in its order.  Returns ``(ims_list, labels_list, ims_crop_list)``, each a list over the first
+    swept dimension of lists over the second: float32 frames ``(y_pix, x_pix)`` of channel ``ch``; marker pairs
+    ``[y, x]`` shifted by the crop's origin (``[nan, nan]`` without scaled labels); float64 zero-filled crops
+    (``get_crop``; ``[]`` without ``crop_type``).  ``input_idxs`` for labels: y first, then x.
+
+    Labels of a cond-ae-msp / ps-vae / msps-vae are changed in the latents and mapped back through the inverse
+    transform; labels of a cond-ae / cond-vae go with ``ims_0``, repeated, through the whole model.  A cond-ae /
+    cond-vae with 4-d ``labels_sc_0`` (a conditional encoder) is a NotImplementedError for ``'labels'``; so is
+    ``'labels'`` without ``mins_sc`` / ``maxes_sc``, as in the reference."""
+    return _interpolate('2d', interp_type, model, ims_0, latents_0, labels_0, labels_sc_0, mins, maxes, input_idxs,
+                        n_frames, crop_type, mins_sc, maxes_sc, crop_kwargs, marker_idxs, ch)
+
+
+def interpolate_1d(
+        interp_type, model, ims_0, latents_0, labels_0, labels_sc_0, mins, maxes, input_idxs,
+        n_frames, crop_type=None, mins_sc=None, maxes_sc=None, crop_kwargs=None,
+        marker_idxs=None, ch=0):
+    """One row of ``n_frames`` reconstructions per entry of ``input_idxs``, that latent (or label) alone swept between
+    its ``mins`` and ``maxes``: the reference's ``interpolate_1d`` (cond_ae_utils.py:543-730) with its parameters in
+    its order.  Returns and refusals as ``interpolate_2d``; the marker pair of a label traversal is read at
+    ``input_idxs[0]`` and ``input_idxs[1]``, as there."""
+    return _interpolate('1d', interp_type, model, ims_0, latents_0, labels_0, labels_sc_0, mins, maxes, input_idxs,
+                        n_frames, crop_type, mins_sc, maxes_sc, crop_kwargs, marker_idxs, ch)

@@ -568,6 +568,29 @@ int bn_u8_to_unit_float(const unsigned char* in, float* out, size_t n, bn_stream
 int bn_cond_encoder_input(const void* frames, int frames_is_u8, const float* coords, int ld,
                           int n, int c, int h, int w, int n_maps, float* out, bn_stream_t stream);
 
+/* One channel of decoded frames, cropped, quantised and tiled into a uint8 mosaic in one pass (replaces the
+ * host-side get_crop of plotting/__init__.py:41-73 and the panel grids of plot_2d_frame_array and
+ * make_latent_traversal_movie, plotting/cond_ae_utils.py): out uint8 (t, r * hc, cc * wc),
+ *   out[i, j * hc + y, k * wc + x] = 0                        s < 0, y_min + y >= h or x_min + x >= w
+ *                                  = quantise(frames[s, ch, y_min + y, x_min + x])     fp32 frames
+ *                                  = frames[s, ch, y_min + y, x_min + x]               frames_u8
+ * with s = src[(i * r + j) * cc + k].  frames: (p, c, h, w) fp32 unit floats, or with frames_u8 uint8 grey
+ * levels; quantise is the rule of bn_unit_float_to_u8 (NaN -> 0, else clamp(rint(v * 255), 0, 255), round half
+ * to even).  (y_min, x_min, hc, wc) is the crop window, the whole frame being (0, 0, h, w); where it passes
+ * the bottom or right edge the mosaic is zero, as get_crop fills.  src: DEVICE int32 (t, r, cc), read on the
+ * device; -1 is a blank panel, an index may repeat.  The caller keeps src below p: the kernel shows a panel
+ * with s >= p as blank and reads nothing for it.  Every output byte is written once, by plain stores; no
+ * memset is needed and no atomics are used.  16-byte stores where `out` and cc * wc are multiples of 16,
+ * with four 16-byte loads (frames_u8: one) where the 16 bytes lie in one panel, inside the frame and on a
+ * 16-byte boundary of the source; byte by byte otherwise, with the same values.
+ * t * r * cc == 0 returns 0 and launches nothing.  BN_E_SHAPE (nothing written): a negative count, c, h or
+ * w <= 0, ch outside [0, c), y_min or x_min < 0 (a numpy slice would wrap there), hc or wc <= 0, t * r * hc
+ * or cc * wc or a window's end at 2^31 or beyond, a grid of 2^32 threads or more, src or fp32 frames off a
+ * 4-byte boundary.  BN_E_BADARG: a NULL pointer (frames may be NULL when p == 0). */
+int bn_frame_mosaic_u8(const void* frames, int frames_u8, int p, int c, int h, int w, int ch,
+                       int y_min, int x_min, int hc, int wc, const int* src, int t, int r, int cc,
+                       unsigned char* out, bn_stream_t stream);
+
 /* unit-float frames -> stored uint8 grey levels, the inverse of bn_u8_to_unit_float on k / 255:
  *   out[i] = NaN -> 0, else clamp(rint(in[i] * 255), 0, 255)
  * The product is one fp32 multiplication and rint rounds half to even, i.e. numpy's
