@@ -145,6 +145,8 @@ SIGNATURES = {
     'bn_unit_float_to_u8': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     'bn_cond_encoder_input': (_c_int, [_c_void_p, _c_int, _c_void_p] + [_c_int] * 6 + [_c_void_p, _c_void_p]),
     'bn_frame_mosaic_u8': (_c_int, [_c_void_p] + [_c_int] * 10 + [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_void_p]),
+    'bn_recon_panels_u8': (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p] + [_c_int] * 6
+                           + [_c_void_p, _c_size_t, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
     'bn_prof_read': (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
@@ -1140,6 +1142,65 @@ def frame_mosaic_u8(frames, src, ch=0, crop=None):
         _ptr(frames, 'frames', dtype=frames.dtype), int(frames.dtype == torch.uint8), P, C, H, W, int(ch), y_min,
         x_min, Hc, Wc, _ptr(src, 'src', dtype=torch.int32), T, R, Cc, _ptr(out, 'out', dtype=torch.uint8), _stream()),
         'bn_frame_mosaic_u8')
+    return out
+
+
+def recon_panels_u8(orig, recon, mask=None, show_orig=True, out=None, row=0, n_rows=1):
+    """Frames ``orig`` and their reconstruction ``recon``, both (N, C, H, W) and each fp32 unit floats or uint8 grey
+    levels (value / 255), -> row ``row`` of the uint8 DEVICE movie (N, n_rows * H, 3 * C * W): per frame and image row
+    three panels with the channels side by side, the original (times ``mask``; black without ``show_orig``), the
+    reconstruction and the residual ``0.5 + (orig * mask - recon)``, each step in fp32 and quantised by
+    ``unit_float_to_u8``'s rule.  ``mask``: None, fp32 (N, C, H, W) or one fp32 (C, H, W) for all frames; it masks the
+    original alone.  ``out``: the movie to fill (its other rows are left alone), made here when None.  Dtypes,
+    shapes, devices and contiguity are checked before any call (``ValueError``).  One pass on the current stream
+    (csrc/recon_panels.hip)."""
+    who = 'recon_panels_u8'
+    for name, t in (('orig', orig), ('recon', recon)):
+        if not torch.is_tensor(t) or t.dim() != 4:
+            raise ValueError('%s: expected %s (N, C, H, W), got %s'
+                             % (who, name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+        if t.dtype not in (torch.uint8, torch.float32):
+            raise ValueError('%s: %s must be uint8 or float32, got %s' % (who, name, t.dtype))
+    if tuple(recon.shape) != tuple(orig.shape):
+        raise ValueError('%s: orig %s and recon %s must share a shape' % (who, tuple(orig.shape), tuple(recon.shape)))
+    N, C, H, W = (int(v) for v in orig.shape)
+    if min(C, H, W) < 1:
+        raise ValueError('%s: frames of %d x %d x %d pixels' % (who, C, H, W))
+    per_frame = False
+    if mask is not None:
+        if not torch.is_tensor(mask) or mask.dtype != torch.float32:
+            raise ValueError('%s: the mask must be a float32 tensor, got %s'
+                             % (who, mask.dtype if torch.is_tensor(mask) else type(mask).__name__))
+        if tuple(mask.shape) not in ((C, H, W), (N, C, H, W)):
+            raise ValueError('%s: expected a mask %s or %s, got %s'
+                             % (who, (C, H, W), (N, C, H, W), tuple(mask.shape)))
+        per_frame = mask.dim() == 4
+    row, n_rows = int(row), int(n_rows)
+    if n_rows < 1 or not 0 <= row < n_rows:
+        raise ValueError('%s: row %d of a movie of %d rows' % (who, row, n_rows))
+    shape = (N, n_rows * H, 3 * C * W)
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != shape):
+        raise ValueError('%s: expected out uint8 %s, got %s'
+                         % (who, shape, '%s %s' % (out.dtype, tuple(out.shape)) if torch.is_tensor(out)
+                            else type(out).__name__))
+    named = [('orig', orig), ('recon', recon), ('mask', mask), ('out', out)]
+    for name, t in named:
+        if t is not None and not t.is_contiguous():
+            raise ValueError('%s: %s must be contiguous' % (who, name))
+    for name, t in named:
+        if t is not None and not t.is_cuda:
+            raise ValueError('%s: expected %s on the GPU, got device %s (the HIP path has no CPU fallback)'
+                             % (who, name, t.device))
+    for name, t in named[1:]:
+        if t is not None and t.device != orig.device:
+            raise ValueError('%s: orig is on %s, %s on %s' % (who, orig.device, name, t.device))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=orig.device)
+    strip = 3 * C * H * W
+    _check(load().bn_recon_panels_u8(
+        orig.data_ptr(), int(orig.dtype == torch.uint8), recon.data_ptr(), int(recon.dtype == torch.uint8),
+        None if mask is None else mask.data_ptr(), int(per_frame), N, C, H, W, int(bool(show_orig)),
+        out.data_ptr() + row * strip, n_rows * strip, _stream()), 'bn_recon_panels_u8')
     return out
 
 

@@ -93,6 +93,13 @@ bool bn_frame_mosaic_ok(int P, int C, int H, int W, int ch, int y_min, int x_min
 int bn_launch_frame_mosaic(const void* frames, int frames_u8, int P, int C, int H, int W, int ch, int y_min, int x_min,
                            int Hc, int Wc, const int* src, int T, int R, int Cc, unsigned char* out, hipStream_t st);
 
+// recon_panels.hip: frames, their reconstruction and the residual 0.5 + (orig * mask - recon) as three uint8 panels
+// per row, channels side by side, into frames of out_frame_stride >= 3 C H W bytes (one row of a movie)
+bool bn_recon_panels_ok(int N, int C, int H, int W, size_t out_frame_stride);
+int bn_launch_recon_panels(const void* orig, int orig_u8, const void* recon, int recon_u8, const float* mask,
+                           int mask_per_frame, int N, int C, int H, int W, int show_orig, unsigned char* out,
+                           size_t out_frame_stride, hipStream_t st);
+
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);
 int bn_launch_bn_stats(const float* x, float* mean, float* var, int N, int C, int HW, void* ws,

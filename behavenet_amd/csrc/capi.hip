@@ -1969,6 +1969,22 @@ extern "C" int bn_frame_mosaic_u8(const void* frames, int frames_u8, int p, int 
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Frames and their reconstruction -> original | reconstruction | residual strips (recon_panels.hip): the
+// reconstruction movie.
+extern "C" int bn_recon_panels_u8(const void* orig, int orig_u8, const void* recon, int recon_u8, const float* mask,
+                                  int mask_per_frame, int n, int c, int h, int w, int show_orig, unsigned char* out,
+                                  size_t out_frame_stride, bn_stream_t stream) {
+    if (!bn_recon_panels_ok(n, c, h, w, out_frame_stride)) return BN_E_SHAPE;
+    if (n == 0) return 0;
+    if (!orig || !recon || !out) return BN_E_BADARG;
+    // (fp32 operands that are not even 4-byte aligned cannot be read at all)
+    if (((uintptr_t)mask & 3) || (!orig_u8 && ((uintptr_t)orig & 3)) || (!recon_u8 && ((uintptr_t)recon & 3)))
+        return BN_E_SHAPE;
+    return bn_launch_recon_panels(orig, orig_u8, recon, recon_u8, mask, mask_per_frame, n, c, h, w, show_orig, out,
+                                  out_frame_stride, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // fp32 unit-float frames -> stored uint8 grey levels (recon_u8.hip): NaN -> 0, else clamp(rint(x * 255), 0, 255).
 extern "C" int bn_unit_float_to_u8(const float* in, unsigned char* out, size_t n, bn_stream_t stream) {
     if (!in || !out) return BN_E_BADARG;

@@ -1,7 +1,7 @@
 """Inference-only passes over every trial: latents -> ``*_latents.pkl`` (BASELINE config 5), per-frame
 reconstruction errors -> ``*_frame_errors.pkl``, uint8 reconstructions -> ``*_reconstructions.npz`` and per-pixel
-error / moment maps -> ``*_pixel_stats.pkl``; and latent traversals as uint8 mosaics and movies, decoded in one batch
-and tiled on the device.
+error / moment maps -> ``*_pixel_stats.pkl``; latent traversals as uint8 mosaics and movies, decoded in one batch
+and tiled on the device; and reconstruction movies (original, reconstruction, residual) as uint8 strips.
 
 Mirror of ``export_latents`` in the reference ``behavenet/fitting/eval.py:6-118``: same pickle
 schema ``{'latents': [per-trial (T x D) arrays, empty for gap trials], 'trials': batch_idxs}``
@@ -29,7 +29,7 @@ __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconst
            'frame_errors', 'frame_errors_device', 'export_reconstructions', 'reconstruct_trial',
            'reconstruct_trial_device', 'export_pixel_stats', 'pixel_stats', 'pixel_stats_device',
            'summarise_pixel_stats', 'traversal_points', 'traverse_latents', 'traverse_latents_device',
-           'traversal_movie', 'traversal_movie_device']
+           'traversal_movie', 'traversal_movie_device', 'reconstruction_movie', 'reconstruction_movie_device']
 
 
 def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -1025,3 +1025,85 @@ def traversal_movie(model, base_latents, mins, maxes, input_idxs, n_frames, n_co
     """``traversal_movie_device`` as a numpy array ``(B * n_frames, n_rows * Hc, n_cols * Wc)`` of uint8."""
     return traversal_movie_device(model, base_latents, mins, maxes, input_idxs, n_frames, n_cols, labels_0,
                                   apply_inverse_transform, crop_kwargs, ch, chunk_size).cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------ reconstruction movies
+def reconstruction_movie_device(model, y, sess=None, masks=None, labels=None, labels_2d=None, max_frames=400,
+                                chunk_size=200, extra_models=()):
+    """The frames of the reference's reconstruction movie (``make_ae_reconstruction_movie_wrapper``,
+    plotting/ae_utils.py) as a uint8 DEVICE tensor ``(T, R * H, 3 * C * W)``, ``T = min(len(y), max_frames)``: per
+    frame the original, the reconstruction and the residual ``0.5 + (original - reconstruction)`` next to each
+    other, each panel with its channels side by side (the reference's ``concat``), clipped to [0, 1] as its
+    ``imshow(vmin=0, vmax=1)`` clips and quantised by ``unit_float_to_u8``'s rule.  ``imshow(movie[t], cmap='gray',
+    vmin=0, vmax=255)`` shows frame t.
+
+    ``y``: fp32 frames or stored uint8 frames (value / 255; they go into a conv encoder as they are).  ``masks``: one
+    (C, H, W) mask or per-frame masks; as in the reference they multiply the ORIGINAL alone -- the model sees the
+    frames unmasked -- in its panel and inside the residual.  Every model of ``extra_models`` (the reference's
+    ``include_linear``: the linear AE with the same latents) adds a row below with a black first panel, so R = 1 +
+    ``len(extra_models)``.  Eval mode, ``no_grad``, the posterior mean for every variational class.
+
+    Each chunk of ``chunk_size`` frames is one forward pass and ONE launch of ``bn_recon_panels_u8``, which reads the
+    frames, the masks and the reconstruction and writes the chunk's strips into the movie; only the movie crosses to
+    the host.  ``hparams['hip_encode_dtype']`` and ``['hip_decode_dtype']`` of each model are honoured: under
+    ``'bf16'`` a served decoder's last layer writes uint8 grey levels (``quantising_frames``), which are the
+    reconstruction panel as they are and enter the residual as value / 255.  The fp32 decoder's last bits can depend
+    on the batch it is given (traversals), so ``chunk_size`` may turn a grey level there."""
+    models = [model] + list(extra_models)
+    for m in models:
+        if m.hparams['model_class'] not in _LATENTS_AT:
+            raise ValueError('Invalid model class %s' % m.hparams['model_class'])
+        decode_dtype_of(m), encode_dtype_of(m)          # (an invalid key is an error before anything runs)
+    if not torch.is_tensor(y) or y.dim() != 4:
+        raise ValueError('reconstruction_movie: expected frames (T, C, H, W), got %s'
+                         % (tuple(y.shape) if torch.is_tensor(y) else type(y).__name__,))
+    if y.dtype not in (torch.uint8, torch.float32):
+        raise ValueError('reconstruction_movie: frames must be uint8 or float32, got %s' % y.dtype)
+    max_frames = int(max_frames)
+    if max_frames < 0 or int(chunk_size) < 1:
+        raise ValueError('reconstruction_movie: max_frames %d, chunk_size %d' % (max_frames, chunk_size))
+    y = y[:max_frames].contiguous()
+    n, c, h, w = (int(v) for v in y.shape)
+    per_frame = False
+    if masks is not None:
+        # one (C, H, W) mask per trial, or per-frame masks (models.aes.frame_masks)
+        if masks.dim() == 4 and masks.shape[0] == 1:
+            masks = masks[0]
+        per_frame = masks.dim() == 4
+        if tuple(masks.shape[-3:]) != (c, h, w) or masks.dim() not in (3, 4) or \
+                (per_frame and masks.shape[0] < n):
+            raise ValueError('reconstruction_movie: expected masks %s or (T, %d, %d, %d), got %s'
+                             % ((c, h, w), c, h, w, tuple(masks.shape)))
+        masks = (masks[:n] if per_frame else masks).float().contiguous()
+    labels = None if labels is None else labels[:max_frames]
+    labels_2d = None if labels_2d is None else labels_2d[:max_frames]
+    out = torch.empty((n, len(models) * h, 3 * c * w), dtype=torch.uint8, device=y.device)
+    floats = None          # (the fp32 copy of stored frames, made once for the models that need it)
+    for row, m in enumerate(models):
+        cls = m.hparams['model_class']
+        m.eval()
+        x = y
+        if y.dtype == torch.uint8 and _wants_float_frames(m, labels_2d):
+            floats = _hip.u8_to_unit_float(y) if floats is None else floats
+            x = floats
+        kwargs = _forward_kwargs(cls, sess)
+        with torch.no_grad(), encode_precision(encode_dtype_of(m)), decode_precision(decode_dtype_of(m)):
+            for beg in range(0, n, chunk_size):
+                end = min(beg + chunk_size, n)
+                if cls in ('cond-ae', 'cond-vae'):
+                    kwargs.update(labels=labels[beg:end],
+                                  labels_2d=None if labels_2d is None else labels_2d[beg:end])
+                with quantising_frames() as req:
+                    x_hat = m(x[beg:end], **kwargs)[0]
+                recon = req.frames if req.frames is not None else x_hat
+                recon = recon.contiguous().view(y[beg:end].shape)
+                _hip.recon_panels_u8(y[beg:end], recon, masks[beg:end] if per_frame else masks, show_orig=row == 0,
+                                     out=out[beg:end], row=row, n_rows=len(models))
+    return out
+
+
+def reconstruction_movie(model, y, sess=None, masks=None, labels=None, labels_2d=None, max_frames=400, chunk_size=200,
+                         extra_models=()):
+    """``reconstruction_movie_device`` as a numpy array ``(T, R * H, 3 * C * W)`` of uint8."""
+    return reconstruction_movie_device(model, y, sess, masks, labels, labels_2d, max_frames, chunk_size,
+                                       extra_models).cpu().numpy()

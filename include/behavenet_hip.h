@@ -591,6 +591,32 @@ int bn_frame_mosaic_u8(const void* frames, int frames_u8, int p, int c, int h, i
                        int y_min, int x_min, int hc, int wc, const int* src, int t, int r, int cc,
                        unsigned char* out, bn_stream_t stream);
 
+/* The strips of a reconstruction movie in one pass (replaces the three fp32 arrays ims_orig, ims_recon and
+ * 0.5 + (ims_orig - ims_recon) of make_ae_reconstruction_movie_wrapper, plotting/ae_utils.py:147-186, their
+ * concat per frame and matplotlib's vmin=0, vmax=1 clip): for frame i and row y three panels of c * w bytes,
+ * the channels side by side,
+ *   o  = orig[i, k, y, x]                        fp32 unit float, or with orig_u8 stored uint8 as value / 255.f
+ *   om = mask ? o * mask[i or 0, k, y, x] : o    (the original alone is masked, as the reference masks)
+ *   r  = recon[i, k, y, x]                       fp32 unit float, or with recon_u8 uint8 grey levels as value / 255.f
+ *   panel 0: show_orig ? quantise(om) : 0        (no mask and orig_u8: the stored byte, which is the same value)
+ *   panel 1: recon_u8 ? the byte : quantise(r)
+ *   panel 2: quantise(0.5f + (om - r))
+ *   out[i * out_frame_stride + y * (3 * c * w) + p * (c * w) + k * w + x]
+ * quantise is the rule of bn_unit_float_to_u8 (NaN -> 0, else clamp(rint(v * 255), 0, 255), round half to even).
+ * Every step is one fp32 operation, none contracted into an fma: numpy's float32 arithmetic bit for bit.
+ * orig, recon: (n, c, h, w); mask: NULL, fp32 (n, c, h, w) with mask_per_frame, else fp32 (c, h, w) for all
+ * frames.  out_frame_stride >= 3 * c * h * w bytes: a larger stride writes one row of a movie of several rows
+ * (row j of r at out + j * h * 3 * c * w with stride r * h * 3 * c * w; show_orig = 0 leaves panel 0 black).
+ * A call writes each byte of its n strips once, by plain stores, and nothing else.  16-byte stores where out,
+ * out_frame_stride and 3 * c * w are multiples of 16, with 16-byte loads where the 16 bytes lie inside one
+ * channel of one panel and the operands sit on a 16-byte boundary; byte by byte otherwise, with the same values.
+ * n == 0 returns 0 and launches nothing.  BN_E_SHAPE (nothing written): n < 0, c, h or w <= 0,
+ * out_frame_stride < 3 * c * h * w, n * h or 3 * c * w or c * h * w at 2^31 or beyond, a grid of 2^32 threads
+ * or more, an fp32 operand off a 4-byte boundary.  BN_E_BADARG: orig, recon or out NULL. */
+int bn_recon_panels_u8(const void* orig, int orig_u8, const void* recon, int recon_u8, const float* mask,
+                       int mask_per_frame, int n, int c, int h, int w, int show_orig, unsigned char* out,
+                       size_t out_frame_stride, bn_stream_t stream);
+
 /* unit-float frames -> stored uint8 grey levels, the inverse of bn_u8_to_unit_float on k / 255:
  *   out[i] = NaN -> 0, else clamp(rint(in[i] * 255), 0, 255)
  * The product is one fp32 multiplication and rint rounds half to even, i.e. numpy's
