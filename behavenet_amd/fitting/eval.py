@@ -21,8 +21,8 @@ import torch
 from behavenet_amd import _hip
 from behavenet_amd.fitting import distributed as bdist
 from behavenet_amd.data.utils import label_maps_of
-from behavenet_amd.hip_functions import (DECODE_DTYPES, ENCODE_DTYPES, decode_precision, encode_precision,
-                                         quantising_frames, scoring_frames)
+from behavenet_amd.hip_functions import (DECODE_DTYPES, ENCODE_DTYPES, FrameErrRequest, FrameU8Request,
+                                         decode_precision, encode_precision, quantising_frames, scoring_frames)
 from behavenet_amd.models.aes import encoder_input
 
 __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconstruction', 'export_frame_errors',
@@ -37,15 +37,19 @@ def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
     return encode_trial_device(model, y, sess, labels_2d, chunk_size).cpu().numpy()
 
 
+def _dtype_key(model, key, env, allowed):
+    """``hparams[key]``, else the environment's ``env``, else 'f32'; a value outside ``allowed`` is a ValueError."""
+    dtype = model.hparams.get(key, os.environ.get(env, 'f32'))
+    if dtype not in allowed:
+        raise ValueError("hparams['%s'] (or %s) must be one of %s, got %r" % (key, env, allowed, dtype))
+    return dtype
+
+
 def encode_dtype_of(model):
     """'f32' (default) or 'bf16': ``hparams['hip_encode_dtype']``, else the environment's BN_ENCODE_DTYPE.
     bf16 runs the conv encoder on bf16 operands with fp32 accumulation (hip_functions.conv_stack_bf16)
     for a model in eval mode; it costs about 1e-3 of max|z|."""
-    dtype = model.hparams.get('hip_encode_dtype', os.environ.get('BN_ENCODE_DTYPE', 'f32'))
-    if dtype not in ENCODE_DTYPES:
-        raise ValueError("hparams['hip_encode_dtype'] (or BN_ENCODE_DTYPE) must be one of %s, got %r"
-                         % (ENCODE_DTYPES, dtype))
-    return dtype
+    return _dtype_key(model, 'hip_encode_dtype', 'BN_ENCODE_DTYPE', ENCODE_DTYPES)
 
 
 def decode_dtype_of(model):
@@ -53,19 +57,19 @@ def decode_dtype_of(model):
     bf16 runs the transposed-conv decoder on bf16 operands with fp32 accumulation
     (hip_functions.convT_stack_bf16) in ``get_reconstruction``; it costs about one grey level of 255 on a
     reconstruction."""
-    dtype = model.hparams.get('hip_decode_dtype', os.environ.get('BN_DECODE_DTYPE', 'f32'))
-    if dtype not in DECODE_DTYPES:
-        raise ValueError("hparams['hip_decode_dtype'] (or BN_DECODE_DTYPE) must be one of %s, got %r"
-                         % (DECODE_DTYPES, dtype))
-    return dtype
+    return _dtype_key(model, 'hip_decode_dtype', 'BN_DECODE_DTYPE', DECODE_DTYPES)
 
 
-def _wants_float_frames(model, labels_2d):
-    """Stored uint8 frames have to be converted before the model sees them: for the linear models, and where dense
-    label maps (N, L, H, W) are concatenated onto them.  Label coordinates (N, 2 L) leave them uint8
-    (``models.aes.encoder_input`` divides by 255 in the pass that builds the maps)."""
+def _model_frames(model, y, labels_2d, floats=None):
+    """The frames as the model takes them.  Stored uint8 frames have to be converted before the model sees them
+    (``floats``, where the caller has that copy already): for the linear models, and where dense label maps
+    (N, L, H, W) are concatenated onto the float tensor.  Conv encoders take the stored uint8 frames as they are:
+    value / 255 is fused into the first layer, csrc k_down_c1s<.., U8>; label COORDINATES (N, 2 L) go with the uint8
+    frames into the one pass that builds the encoder's input (``models.aes.encoder_input`` divides by 255 there)."""
     dense = labels_2d is not None and not (torch.is_tensor(labels_2d) and labels_2d.dim() == 2)
-    return dense or model.hparams.get('model_type', 'conv') != 'conv'
+    if y.dtype == torch.uint8 and (dense or model.hparams.get('model_type', 'conv') != 'conv'):
+        return _hip.u8_to_unit_float(y.contiguous()) if floats is None else floats
+    return y
 
 
 def encode_trial_device(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -77,11 +81,7 @@ def encode_trial_device(model, y, sess=None, labels_2d=None, chunk_size=200):
 
 def _encode_trial_device(model, y, sess, labels_2d, chunk_size):
     mc = model.hparams['model_class']
-    if y.dtype == torch.uint8 and _wants_float_frames(model, labels_2d):
-        # (conv encoders take the stored uint8 frames as they are: value / 255 is fused into the
-        # first layer, csrc k_down_c1s<.., U8>; dense label maps are concatenated onto the float tensor, label
-        # COORDINATES go with the uint8 frames into the one pass that builds the encoder's input)
-        y = _hip.u8_to_unit_float(y.contiguous())
+    y = _model_frames(model, y, labels_2d)
     n = y.shape[0]
     parts = []
     with torch.no_grad():
@@ -168,11 +168,32 @@ class _GraphedTrialEncoder(object):
         return rec
 
 
-def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond_enc, sink=None, sink_sharded=False):
+def _is_cond_encoder(model):
+    """A cond-AE whose ENCODER sees the labels too (as ``labels_sc``: dense maps or coordinates)."""
+    return model.hparams['model_class'] == 'cond-ae' and model.hparams.get('conditional_encoder', False)
+
+
+def _batch_fields(model, data):
+    """``(masks, labels, labels_2d)`` of a one-trial batch: the masks if it has any, the labels for the conditional
+    classes, ``labels_sc`` for a conditional encoder; None otherwise."""
+    masks = data['masks'][0] if 'masks' in data else None
+    labels = data['labels'][0] if model.hparams['model_class'] in ('cond-ae', 'cond-vae') else None
+    labels_2d = data['labels_sc'][0] if _is_cond_encoder(model) else None
+    return masks, labels, labels_2d
+
+
+def _export_setup(model):
+    """The exporters' frames per forward pass; an invalid dtype key is an error before any trial is read."""
+    decode_dtype_of(model), encode_dtype_of(model)
+    return int(model.hparams.get('export_chunk_frames', 1024))
+
+
+def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn=None, sink=None, sink_sharded=False):
     """The trial walk the exporters share: every train / val / test trial of every session goes once through
-    ``on_device_fn(images, sess, data)`` (device-resident frames; the results stay on the device and come to the
-    host in ONE transfer at the end) or ``on_host_fn(images, sess, data)`` (-> numpy).  Under
-    ``torch.distributed`` a trial is owned by its identity and the results are gathered on rank 0.
+    ``on_device_fn(images, sess, data, trial)`` (device-resident frames; the results stay on the device and come to
+    the host in ONE transfer at the end) or ``on_host_fn(images, sess, data, trial)`` (-> numpy; by default the
+    device function's result brought to the host).  Under ``torch.distributed`` a trial is owned by its identity and
+    the results are gathered on rank 0.
     -> per session a list with one array per trial (empty for trials in no split), or None on the other ranks.
 
     With ``sink`` nothing piles up: every result, device tensor or numpy array, goes to ``sink(sess, trial, result)``
@@ -185,6 +206,9 @@ def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond
     single = {'return_multiple': False} \
         if getattr(data_generator, 'n_sessions_per_batch', 1) > 1 else {}
     model.eval()
+    if on_host_fn is None:
+        def on_host_fn(*args):
+            return on_device_fn(*args).cpu().numpy()
     rank, world = (0, 1) if (sink is not None and not sink_sharded) else (bdist.rank(), bdist.world_size())
 
     results = [[np.array([]) for _ in range(ds.n_trials)] for ds in data_generator.datasets]
@@ -207,7 +231,7 @@ def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond
     # (a conditional encoder takes them too once its label maps are built on the device: hip_label_maps = 'device';
     # a generator that serves dense maps all the same is still served, models.aes.encoder_input converts for them)
     conv_u8 = model.hparams.get('model_type', 'conv') == 'conv' and \
-        (not cond_enc or label_maps_of(model.hparams) == 'device')
+        (not _is_cond_encoder(model) or label_maps_of(model.hparams) == 'device')
     serve_prev = getattr(data_generator, 'serve_uint8', None)
     if serve_prev is not None and conv_u8:
         data_generator.serve_uint8 = True
@@ -235,11 +259,11 @@ def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn, cond
                 if not torch.is_tensor(images):      # generators serving numpy arrays (as_numpy)
                     images = torch.from_numpy(np.asarray(images))
                 if sink is not None:
-                    sink(sess, idx, (on_device_fn if images.is_cuda else on_host_fn)(images, sess, data))
+                    sink(sess, idx, (on_device_fn if images.is_cuda else on_host_fn)(images, sess, data, idx))
                 elif images.is_cuda:
-                    on_device[(sess, idx)] = on_device_fn(images, sess, data)
+                    on_device[(sess, idx)] = on_device_fn(images, sess, data, idx)
                 else:
-                    results[sess][idx] = on_host_fn(images, sess, data)
+                    results[sess][idx] = on_host_fn(images, sess, data, idx)
     finally:
         if serve_prev is not None:
             data_generator.serve_uint8 = serve_prev
@@ -292,16 +316,12 @@ def _write_per_session(data_generator, model, filename, suffix, key, results, wh
 
 def export_latents(data_generator, model, filename=None):
     """Encode train/val/test trials of every session and pickle them (ref eval.py:6-118)."""
-    cond_enc = model.hparams['model_class'] == 'cond-ae' and \
-        model.hparams.get('conditional_encoder', False)
     encode = _GraphedTrialEncoder(model)
-
-    def labels_2d_of(data):
-        return data['labels_sc'][0] if cond_enc else None
+    # (host trials go through ``encode_trial``: 200-frame chunks, as the reference encodes them)
     latents = _export_per_trial(
         'export_latents', data_generator, model,
-        lambda images, sess, data: encode(images, sess, labels_2d_of(data)),
-        lambda images, sess, data: encode_trial(model, images, sess, labels_2d_of(data)), cond_enc)
+        lambda images, sess, data, trial: encode(images, sess, _batch_fields(model, data)[2]),
+        lambda images, sess, data, trial: encode_trial(model, images, sess, _batch_fields(model, data)[2]))
     if latents is None:
         return []
     return _write_per_session(data_generator, model, filename, 'latents', 'latents', latents, 'latents')
@@ -312,6 +332,17 @@ def export_latents(data_generator, model, filename=None):
 # mu, logvar, y_hat), where the reference takes mu
 _LATENTS_AT = {'ae': 1, 'cond-ae': 1, 'cond-ae-msp': 1, 'vae': 1, 'beta-tcvae': 1, 'cond-vae': 1, 'ps-vae': 2,
                'msps-vae': 2}
+
+
+def _complete_latents(model, z, labels, apply_inverse_transform):
+    """Latents as the decoder takes them: cond-AE / cond-VAE get their ``labels`` appended, AEMSP / PS-VAE / MSPS-VAE
+    latents given in the transformed space are mapped back (``apply_inverse_transform``)."""
+    cls = model.hparams['model_class']
+    if cls in ('cond-ae', 'cond-vae'):
+        return torch.cat((z, labels), dim=1)
+    if cls in ('cond-ae-msp', 'ps-vae', 'msps-vae') and apply_inverse_transform:
+        return model.get_inverse_transformed_latents(z, as_numpy=False)
+    return z
 
 
 def get_reconstruction(model, inputs, dataset=None, return_latents=False, labels=None, labels_2d=None,
@@ -348,10 +379,7 @@ def get_reconstruction(model, inputs, dataset=None, return_latents=False, labels
             out = model(t, **kwargs)
             recon, latents = out[0], out[_LATENTS_AT[cls]]
         else:
-            if cls in ('cond-ae', 'cond-vae'):
-                t = torch.cat((t, labels), dim=1)
-            elif cls in ('cond-ae-msp', 'ps-vae', 'msps-vae') and apply_inverse_transform:
-                t = model.get_inverse_transformed_latents(t, as_numpy=False)
+            t = _complete_latents(model, t, labels, apply_inverse_transform)
             recon, latents = model.decoding(t, None, None, dataset=None), t
         if as_uint8:
             recon = req.frames if req.frames is not None else _hip.unit_float_to_u8(recon.contiguous())
@@ -359,9 +387,9 @@ def get_reconstruction(model, inputs, dataset=None, return_latents=False, labels
     return (recon, latents) if return_latents else recon
 
 
-# ------------------------------------------------------------------------------------------ frame errors
+# ------------------------------------------------------------------------------------------ a trial in chunks
 def _forward_kwargs(cls, sess):
-    """How ``frame_errors_device`` calls each class's ``forward`` (the conditional classes get their chunk's labels
+    """How ``_forward_chunks`` calls each class's ``forward`` (the conditional classes get their chunk's labels
     on top): the posterior mean for every variational class, cond-VAE included -- a score must not depend on a draw."""
     kwargs = {'dataset': sess}
     if cls in ('vae', 'beta-tcvae', 'ps-vae', 'msps-vae', 'cond-vae'):
@@ -369,53 +397,80 @@ def _forward_kwargs(cls, sess):
     return kwargs
 
 
-def _frame_errors_device(model, y, sess, masks, labels, labels_2d, chunk_size, fused=True):
-    """``frame_errors_device`` inside whatever precision blocks the caller opened.  ``fused=False`` keeps the
-    decoder from scoring in its last layer (tools/bench_frame_errors.py measures both)."""
+def _check_frames(who, y):
+    if not torch.is_tensor(y) or y.dim() != 4:
+        raise ValueError('%s: expected frames (T, C, H, W), got %s'
+                         % (who, tuple(y.shape) if torch.is_tensor(y) else type(y).__name__))
+    if y.dtype not in (torch.uint8, torch.float32):
+        raise ValueError('%s: frames must be uint8 or float32, got %s' % (who, y.dtype))
+
+
+def _trial_masks(masks, y):
+    """``(masks, per_frame)`` for the frames ``y`` of a trial: fp32 and contiguous, per-frame masks
+    (models.aes.frame_masks) as they came, one mask for the trial -- (C, H, W) or (1, C, H, W) -- as (C, H, W);
+    ``(None, False)`` without masks.  A chunk's mask is ``masks[beg:end] if per_frame else masks``."""
+    if masks is None:
+        return None, False
+    if masks.dim() == y.dim() and masks.shape[0] == 1:
+        masks = masks[0]
+    return masks.float().contiguous(), masks.dim() == y.dim()
+
+
+def _forward_chunks(who, model, y, sess, labels, labels_2d, chunk_size, per_chunk, request=None, x=None):
+    """One trial through ``model`` in chunks of ``chunk_size`` frames, inside whatever precision blocks the caller
+    opened: eval mode, ``no_grad``, ``_forward_kwargs`` plus the chunk's labels for the conditional classes.
+    ``y``: fp32 frames or stored uint8 frames (T, C, H, W); ``x``: the frames as the model takes them, where the
+    caller has them already (``_model_frames``).  ``request(beg, end)``, if given, is the context manager the chunk's
+    ONE model call runs in (``scoring_frames``, ``quantising_frames``); it is closed again when
+    ``per_chunk(beg, end, x_hat, req)`` gets the reconstruction and what the request yielded (None without one).
+
+    A function with a callback, not a generator: the requests are thread-local and a consumer that stopped early
+    would leave one open until the generator is collected."""
     cls = model.hparams['model_class']
     if cls not in _LATENTS_AT:
         raise ValueError('Invalid model class %s' % cls)
-    if y.dim() != 4:
-        raise ValueError('frame_errors: expected frames (T, C, H, W), got %s' % (tuple(y.shape),))
-    if y.dtype not in (torch.uint8, torch.float32):
-        raise ValueError('frame_errors: frames must be uint8 or float32, got %s' % y.dtype)
+    _check_frames(who, y)
     model.eval()
     y = y.contiguous()
-    n, d = y.shape[0], y[0].numel()
-    if masks is not None:
-        # one (C, H, W) mask per trial, or per-frame masks (models.aes.frame_masks)
-        if masks.dim() == y.dim() - 1:
-            masks = masks.unsqueeze(0)
-        if masks.dtype != torch.float32:
-            masks = masks.float()
-    # (conv encoders take the stored uint8 frames as they are, as in _encode_trial_device; the TARGET stays
-    # uint8 either way: the kernels divide by 255 as bn_u8_to_unit_float does)
-    x = y
-    if y.dtype == torch.uint8 and _wants_float_frames(model, labels_2d):
-        x = _hip.u8_to_unit_float(y)
+    x = _model_frames(model, y, labels_2d) if x is None else x
     kwargs = _forward_kwargs(cls, sess)
-    out = torch.empty((n,), dtype=torch.float32, device=y.device)
+    n = y.shape[0]
     with torch.no_grad():
         for beg in range(0, n, chunk_size):
             end = min(beg + chunk_size, n)
-            target = y[beg:end]
-            mask = None
-            if masks is not None:
-                mask = masks[beg:end] if masks.shape[0] != 1 else masks
-                if mask.shape[0] == 1 and end - beg != 1:
-                    mask = mask.expand_as(target)
-                mask = mask.contiguous()
             if cls in ('cond-ae', 'cond-vae'):
                 kwargs.update(labels=labels[beg:end], labels_2d=None if labels_2d is None else labels_2d[beg:end])
-            if fused:
-                with scoring_frames(target, mask, 1.0 / d) as req:
-                    x_hat = model(x[beg:end], **kwargs)[0]
-                scores = req.scores
-            else:
-                x_hat, scores = model(x[beg:end], **kwargs)[0], None
-            if scores is None:
-                scores = _hip.frame_sq_err(x_hat.contiguous().view(target.shape), target, mask, 1.0 / d)
-            out[beg:end].copy_(scores)
+            with (contextlib.nullcontext() if request is None else request(beg, end)) as req:
+                x_hat = model(x[beg:end], **kwargs)[0]
+            per_chunk(beg, end, x_hat, req)
+
+
+# ------------------------------------------------------------------------------------------ frame errors
+def _frame_errors_device(model, y, sess, masks, labels, labels_2d, chunk_size, fused=True):
+    """``frame_errors_device`` inside whatever precision blocks the caller opened.  ``fused=False`` keeps the
+    decoder from scoring in its last layer (tools/bench_frame_errors.py measures both)."""
+    y = y.contiguous()
+    masks, per_frame = _trial_masks(masks, y)
+    out = torch.empty((y.shape[0],), dtype=torch.float32, device=y.device)
+
+    def request(beg, end):
+        # (the TARGET stays uint8 where the frames are stored so: the kernels divide by 255 as bn_u8_to_unit_float
+        # does; a single mask is expanded because ``_hip._err_operands`` asks for the target's shape)
+        target, mask = y[beg:end], masks
+        if per_frame:
+            mask = masks[beg:end]
+        elif masks is not None:
+            mask = masks.expand_as(target).contiguous()
+        operands = (target, mask, 1.0 / target[0].numel())
+        return scoring_frames(*operands) if fused else contextlib.nullcontext(FrameErrRequest(*operands))
+
+    def score(beg, end, x_hat, req):
+        scores = req.scores
+        if scores is None:
+            scores = _hip.frame_sq_err(x_hat.contiguous().view(req.target.shape), req.target, req.mask, req.scale)
+        out[beg:end].copy_(scores)
+
+    _forward_chunks('frame_errors', model, y, sess, labels, labels_2d, chunk_size, score, request)
     return out
 
 
@@ -452,20 +507,11 @@ def export_frame_errors(data_generator, model, filename=None):
     at the end); every trial goes through ``frame_errors_device`` with the batch's masks and, for the conditional
     classes, labels.  Launched eagerly: the scoring has no HIP-graph replay (``hip_graph_encode`` covers the
     latents alone)."""
-    cls = model.hparams['model_class']
-    cond_enc = cls == 'cond-ae' and model.hparams.get('conditional_encoder', False)
-    decode_dtype_of(model), encode_dtype_of(model)          # (an invalid key is an error before any trial is read)
-    chunk = int(model.hparams.get('export_chunk_frames', 1024))
+    chunk = _export_setup(model)
 
-    def score(images, sess, data):
-        masks = data['masks'][0] if 'masks' in data else None
-        labels = data['labels'][0] if cls in ('cond-ae', 'cond-vae') else None
-        labels_2d = data['labels_sc'][0] if cond_enc else None
-        return frame_errors_device(model, images, sess, masks, labels, labels_2d, chunk)
-
-    def score_host(images, sess, data):
-        return np.asarray(score(images, sess, data).cpu().numpy(), dtype=np.float32)
-    errors = _export_per_trial('export_frame_errors', data_generator, model, score, score_host, cond_enc)
+    def score(images, sess, data, trial):
+        return frame_errors_device(model, images, sess, *_batch_fields(model, data), chunk)
+    errors = _export_per_trial('export_frame_errors', data_generator, model, score)
     if errors is None:
         return []
     return _write_per_session(data_generator, model, filename, 'frame_errors', 'mse', errors, 'frame errors')
@@ -475,36 +521,24 @@ def export_frame_errors(data_generator, model, filename=None):
 def _reconstruct_trial_device(model, y, sess, labels, labels_2d, chunk_size, fused=True):
     """``reconstruct_trial_device`` inside whatever precision blocks the caller opened.  ``fused=False`` keeps the
     decoder from quantising in its last layer (tools/bench_reconstructions.py measures both)."""
-    cls = model.hparams['model_class']
-    if cls not in _LATENTS_AT:
-        raise ValueError('Invalid model class %s' % cls)
-    if y.dim() != 4:
-        raise ValueError('reconstruct_trial: expected frames (T, C, H, W), got %s' % (tuple(y.shape),))
-    if y.dtype not in (torch.uint8, torch.float32):
-        raise ValueError('reconstruct_trial: frames must be uint8 or float32, got %s' % y.dtype)
-    model.eval()
-    x = y.contiguous()
-    n = x.shape[0]
-    # (conv encoders take the stored uint8 frames as they are, as in _encode_trial_device)
-    if x.dtype == torch.uint8 and _wants_float_frames(model, labels_2d):
-        x = _hip.u8_to_unit_float(x)
-    kwargs = _forward_kwargs(cls, sess)
     out = None
-    with torch.no_grad():
-        for beg in range(0, n, chunk_size):
-            end = min(beg + chunk_size, n)
-            if cls in ('cond-ae', 'cond-vae'):
-                kwargs.update(labels=labels[beg:end], labels_2d=None if labels_2d is None else labels_2d[beg:end])
-            with (quantising_frames() if fused else contextlib.nullcontext()) as req:
-                x_hat = model(x[beg:end], **kwargs)[0]
-            frames = req.frames if fused else None
-            if frames is None:
-                frames = _hip.unit_float_to_u8(x_hat.contiguous())
-            if beg == 0 and end == n:
-                return frames          # (one pass: the decoder's own tensor, no copy)
-            if out is None:
-                out = torch.empty((n,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=frames.device)
-            out[beg:end].copy_(frames)
+
+    def request(beg, end):
+        return quantising_frames() if fused else contextlib.nullcontext(FrameU8Request())
+
+    def store(beg, end, x_hat, req):
+        nonlocal out
+        frames = req.frames
+        if frames is None:
+            frames = _hip.unit_float_to_u8(x_hat.contiguous())
+        if end - beg == len(y):
+            out = frames          # (one pass: the decoder's own tensor, no copy)
+            return
+        if out is None:
+            out = torch.empty((len(y),) + tuple(frames.shape[1:]), dtype=torch.uint8, device=frames.device)
+        out[beg:end].copy_(frames)
+
+    _forward_chunks('reconstruct_trial', model, y, sess, labels, labels_2d, chunk_size, store, request)
     if out is None:          # (a trial without frames)
         out = torch.empty((0,) + tuple(y.shape[1:]), dtype=torch.uint8, device=y.device)
     return out
@@ -601,20 +635,12 @@ def export_reconstructions(data_generator, model, filename=None):
     ``filename`` names the one file of a single-session generator (``ValueError`` with several sessions).
     -> the list of file names."""
     from behavenet_amd.data.trial_store import NpzSessionWriter
-    cls = model.hparams['model_class']
-    cond_enc = cls == 'cond-ae' and model.hparams.get('conditional_encoder', False)
-    decode_dtype_of(model), encode_dtype_of(model)          # (an invalid key is an error before any trial is read)
+    chunk = _export_setup(model)
     if bdist.world_size() > 1 and bdist.rank() != 0:
         return []
-    chunk = int(model.hparams.get('export_chunk_frames', 1024))
 
-    def reconstruct(images, sess, data):
-        labels = data['labels'][0] if cls in ('cond-ae', 'cond-vae') else None
-        labels_2d = data['labels_sc'][0] if cond_enc else None
-        return reconstruct_trial_device(model, images, sess, labels, labels_2d, chunk)
-
-    def reconstruct_host(images, sess, data):
-        return reconstruct(images, sess, data).cpu().numpy()
+    def reconstruct(images, sess, data, trial):
+        return reconstruct_trial_device(model, images, sess, *_batch_fields(model, data)[1:], chunk)
 
     if filename is not None and data_generator.n_datasets > 1:
         raise ValueError('export_reconstructions: one file per session; an explicit filename serves one session, '
@@ -632,8 +658,7 @@ def export_reconstructions(data_generator, model, filename=None):
 
     sink = _PinnedTrialSink(write)
     try:
-        _export_per_trial('export_reconstructions', data_generator, model, reconstruct, reconstruct_host, cond_enc,
-                          sink=sink)
+        _export_per_trial('export_reconstructions', data_generator, model, reconstruct, sink=sink)
         sink.flush()
         for sess, dataset in enumerate(data_generator.datasets):
             if sess not in writers:
@@ -655,45 +680,24 @@ _PIXEL_SPLITS = ('train', 'val', 'test')
 
 def _pixel_stats_device(model, y, sess, masks, labels, labels_2d, chunk_size, out):
     """``pixel_stats_device`` inside whatever precision blocks the caller opened."""
-    cls = model.hparams['model_class']
-    if cls not in _LATENTS_AT:
-        raise ValueError('Invalid model class %s' % cls)
-    if y.dim() != 4:
-        raise ValueError('pixel_stats: expected frames (T, C, H, W), got %s' % (tuple(y.shape),))
-    if y.dtype not in (torch.uint8, torch.float32):
-        raise ValueError('pixel_stats: frames must be uint8 or float32, got %s' % y.dtype)
-    model.eval()
+    _check_frames('pixel_stats', y)          # (before ``out`` is held against their shape)
     y = y.contiguous()
-    n = y.shape[0]
     if out is None:
         out = torch.zeros((4,) + tuple(y.shape[1:]), dtype=torch.float64, device=y.device)
     elif tuple(out.shape) != (4,) + tuple(y.shape[1:]) or out.dtype != torch.float64:
         raise ValueError('pixel_stats: out must be a float64 tensor of shape %s, got %s %s'
                          % ((4,) + tuple(y.shape[1:]), out.dtype, tuple(out.shape)))
-    if masks is not None:
-        # one (C, H, W) mask per trial -- handed to the kernel as it is, not expanded -- or per-frame masks
-        if masks.dim() == y.dim() and masks.shape[0] == 1 and n != 1:
-            masks = masks[0]
-        if masks.dtype != torch.float32:
-            masks = masks.float()
-        masks = masks.contiguous()
-    # (conv encoders take the stored uint8 frames as they are, as in _encode_trial_device; the TARGET stays
-    # uint8 either way: the kernel divides by 255 as bn_u8_to_unit_float does)
-    x = y
-    if y.dtype == torch.uint8 and _wants_float_frames(model, labels_2d):
-        x = _hip.u8_to_unit_float(y)
-    kwargs = _forward_kwargs(cls, sess)
-    with torch.no_grad():
-        for beg in range(0, n, chunk_size):
-            end = min(beg + chunk_size, n)
-            target = y[beg:end]
-            mask = masks
-            if masks is not None and masks.dim() == y.dim():
-                mask = masks[beg:end]
-            if cls in ('cond-ae', 'cond-vae'):
-                kwargs.update(labels=labels[beg:end], labels_2d=None if labels_2d is None else labels_2d[beg:end])
-            x_hat = model(x[beg:end], **kwargs)[0]
-            _hip.pixel_stats_accum(x_hat.contiguous().view(target.shape), target, mask, out)
+    # (one mask for the trial is handed to the kernel as it is, not expanded)
+    masks, per_frame = _trial_masks(masks, y)
+
+    def accumulate(beg, end, x_hat, req):
+        # (the TARGET stays uint8 where the frames are stored so: the kernel divides by 255 as bn_u8_to_unit_float
+        # does)
+        target = y[beg:end]
+        _hip.pixel_stats_accum(x_hat.contiguous().view(target.shape), target, masks[beg:end] if per_frame else masks,
+                               out)
+
+    _forward_chunks('pixel_stats', model, y, sess, labels, labels_2d, chunk_size, accumulate)
     return out
 
 
@@ -768,25 +772,18 @@ def export_pixel_stats(data_generator, model, filename=None):
     in.  Every trial is added onto its (session, split) accumulator ON THE DEVICE; the accumulators alone come to
     the host.  Under ``torch.distributed`` they are gathered on rank 0 and added in rank order, and the other ranks
     return [].  Launched eagerly.  -> the list of file names."""
-    cls = model.hparams['model_class']
-    cond_enc = cls == 'cond-ae' and model.hparams.get('conditional_encoder', False)
-    decode_dtype_of(model), encode_dtype_of(model)          # (an invalid key is an error before any trial is read)
-    chunk = int(model.hparams.get('export_chunk_frames', 1024))
+    chunk = _export_setup(model)
     split_of = {(s_, int(t)): dt for s_, ds in enumerate(data_generator.datasets)
                 for dt in _PIXEL_SPLITS for t in ds.batch_idxs[dt]}
     accs, n_frames, done = {}, {}, []
 
-    def accumulate(images, sess, data):
-        idx = data['batch_idx']
-        key = (sess, split_of[(sess, idx.item() if hasattr(idx, 'item') else int(idx))])
-        masks = data['masks'][0] if 'masks' in data else None
-        labels = data['labels'][0] if cls in ('cond-ae', 'cond-vae') else None
-        labels_2d = data['labels_sc'][0] if cond_enc else None
-        accs[key] = pixel_stats_device(model, images, sess, masks, labels, labels_2d, chunk, out=accs.get(key))
+    def accumulate(images, sess, data, trial):
+        key = (sess, split_of[(sess, trial)])
+        accs[key] = pixel_stats_device(model, images, sess, *_batch_fields(model, data), chunk, out=accs.get(key))
         n_frames[key] = n_frames.get(key, 0) + int(images.shape[0])
         return None
 
-    _export_per_trial('export_pixel_stats', data_generator, model, accumulate, accumulate, cond_enc,
+    _export_per_trial('export_pixel_stats', data_generator, model, accumulate, accumulate,
                       sink=lambda sess, trial, result: done.append((sess, trial)), sink_sharded=True)
     mine = ({k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)) for k, v in accs.items()},
             n_frames, done)
@@ -879,6 +876,15 @@ def _crop_window(crop_kwargs):
     return y_0 - y_ext, x_0 - x_ext, 2 * y_ext, 2 * x_ext
 
 
+def _checked_crop(model, n_points, ch, crop_kwargs):
+    """``_crop_window(crop_kwargs)``, checked with channel ``ch`` against the ``n_points`` frames the model will
+    decode: argument errors before anything is decoded."""
+    crop = _crop_window(crop_kwargs)
+    _hip.check_mosaic_args((n_points, int(model.hparams['n_input_channels']), int(model.hparams['y_pixels']),
+                            int(model.hparams['x_pixels'])), ch, crop)
+    return crop
+
+
 def _point_labels(model, labels, n):
     """(n, L) fp32 device labels for the conditional classes from one row (1, L) / (L,) or one per point; else None."""
     if model.hparams['model_class'] not in ('cond-ae', 'cond-vae'):
@@ -919,11 +925,8 @@ def decode_points_device(model, points, labels=None, apply_inverse_transform=Tru
     parts = []
     with torch.no_grad(), decode_precision(dtype):
         for beg in range(0, n, chunk_size):
-            z = t[beg:beg + chunk_size]
-            if labels is not None:
-                z = torch.cat((z, labels[beg:beg + chunk_size]), dim=1)
-            elif cls in ('cond-ae-msp', 'ps-vae', 'msps-vae') and apply_inverse_transform:
-                z = model.get_inverse_transformed_latents(z, as_numpy=False)
+            z = _complete_latents(model, t[beg:beg + chunk_size],
+                                  None if labels is None else labels[beg:beg + chunk_size], apply_inverse_transform)
             with (quantising_frames() if dtype == 'bf16' else contextlib.nullcontext()) as req:
                 x_hat = model.decoding(z, None, None, dataset=None)
             parts.append(req.frames if req is not None and req.frames is not None else x_hat)
@@ -951,10 +954,7 @@ def traverse_latents_device(model, latents_0, mins, maxes, input_idxs, n_frames,
     its last bits with ``chunk_size`` and with P, as ``get_reconstruction``'s does, and a grey level may turn where
     ``x_hat * 255`` lies at a half."""
     table, (rows, cols) = traversal_points(latents_0, mins, maxes, input_idxs, n_frames, mode)
-    dim = (table.shape[0], int(model.hparams['n_input_channels']), int(model.hparams['y_pixels']),
-           int(model.hparams['x_pixels']))
-    crop = _crop_window(crop_kwargs)
-    _hip.check_mosaic_args(dim, ch, crop)          # (argument errors before anything is decoded)
+    crop = _checked_crop(model, table.shape[0], ch, crop_kwargs)
     frames = decode_points_device(model, table, labels_0, apply_inverse_transform, chunk_size)
     src = np.arange(rows * cols, dtype=np.int32).reshape(1, rows, cols)
     return _hip.frame_mosaic_u8(frames, src, ch, crop)[0]
@@ -1004,10 +1004,7 @@ def traversal_movie_device(model, base_latents, mins, maxes, input_idxs, n_frame
     tables = [traversal_points(b, mins, maxes, input_idxs, n_frames, '1d')[0] for b in base]
     table = np.concatenate(tables, axis=0)
     per_base = n_dims * int(n_frames)
-    dim = (table.shape[0], int(model.hparams['n_input_channels']), int(model.hparams['y_pixels']),
-           int(model.hparams['x_pixels']))
-    crop = _crop_window(crop_kwargs)
-    _hip.check_mosaic_args(dim, ch, crop)
+    crop = _checked_crop(model, table.shape[0], ch, crop_kwargs)
     labels = _point_labels(model, labels_0, n_base)
     if labels is not None:
         labels = labels.repeat_interleave(per_base, dim=0)
@@ -1054,51 +1051,37 @@ def reconstruction_movie_device(model, y, sess=None, masks=None, labels=None, la
         if m.hparams['model_class'] not in _LATENTS_AT:
             raise ValueError('Invalid model class %s' % m.hparams['model_class'])
         decode_dtype_of(m), encode_dtype_of(m)          # (an invalid key is an error before anything runs)
-    if not torch.is_tensor(y) or y.dim() != 4:
-        raise ValueError('reconstruction_movie: expected frames (T, C, H, W), got %s'
-                         % (tuple(y.shape) if torch.is_tensor(y) else type(y).__name__,))
-    if y.dtype not in (torch.uint8, torch.float32):
-        raise ValueError('reconstruction_movie: frames must be uint8 or float32, got %s' % y.dtype)
+    who = 'reconstruction_movie'
+    _check_frames(who, y)
     max_frames = int(max_frames)
     if max_frames < 0 or int(chunk_size) < 1:
-        raise ValueError('reconstruction_movie: max_frames %d, chunk_size %d' % (max_frames, chunk_size))
+        raise ValueError('%s: max_frames %d, chunk_size %d' % (who, max_frames, chunk_size))
     y = y[:max_frames].contiguous()
     n, c, h, w = (int(v) for v in y.shape)
-    per_frame = False
     if masks is not None:
-        # one (C, H, W) mask per trial, or per-frame masks (models.aes.frame_masks)
-        if masks.dim() == 4 and masks.shape[0] == 1:
-            masks = masks[0]
-        per_frame = masks.dim() == 4
+        # one (C, H, W) mask per trial, or per-frame masks (models.aes.frame_masks) for at least the movie's frames
         if tuple(masks.shape[-3:]) != (c, h, w) or masks.dim() not in (3, 4) or \
-                (per_frame and masks.shape[0] < n):
-            raise ValueError('reconstruction_movie: expected masks %s or (T, %d, %d, %d), got %s'
-                             % ((c, h, w), c, h, w, tuple(masks.shape)))
-        masks = (masks[:n] if per_frame else masks).float().contiguous()
+                (masks.dim() == 4 and masks.shape[0] != 1 and masks.shape[0] < n):
+            raise ValueError('%s: expected masks %s or (T, %d, %d, %d), got %s'
+                             % (who, (c, h, w), c, h, w, tuple(masks.shape)))
+        masks = masks[:n] if masks.dim() == 4 and masks.shape[0] > n else masks
+    masks, per_frame = _trial_masks(masks, y)
     labels = None if labels is None else labels[:max_frames]
     labels_2d = None if labels_2d is None else labels_2d[:max_frames]
     out = torch.empty((n, len(models) * h, 3 * c * w), dtype=torch.uint8, device=y.device)
     floats = None          # (the fp32 copy of stored frames, made once for the models that need it)
     for row, m in enumerate(models):
-        cls = m.hparams['model_class']
-        m.eval()
-        x = y
-        if y.dtype == torch.uint8 and _wants_float_frames(m, labels_2d):
-            floats = _hip.u8_to_unit_float(y) if floats is None else floats
-            x = floats
-        kwargs = _forward_kwargs(cls, sess)
-        with torch.no_grad(), encode_precision(encode_dtype_of(m)), decode_precision(decode_dtype_of(m)):
-            for beg in range(0, n, chunk_size):
-                end = min(beg + chunk_size, n)
-                if cls in ('cond-ae', 'cond-vae'):
-                    kwargs.update(labels=labels[beg:end],
-                                  labels_2d=None if labels_2d is None else labels_2d[beg:end])
-                with quantising_frames() as req:
-                    x_hat = m(x[beg:end], **kwargs)[0]
-                recon = req.frames if req.frames is not None else x_hat
-                recon = recon.contiguous().view(y[beg:end].shape)
-                _hip.recon_panels_u8(y[beg:end], recon, masks[beg:end] if per_frame else masks, show_orig=row == 0,
-                                     out=out[beg:end], row=row, n_rows=len(models))
+        def panels(beg, end, x_hat, req):
+            recon = req.frames if req.frames is not None else x_hat
+            recon = recon.contiguous().view(y[beg:end].shape)
+            _hip.recon_panels_u8(y[beg:end], recon, masks[beg:end] if per_frame else masks, show_orig=row == 0,
+                                 out=out[beg:end], row=row, n_rows=len(models))
+
+        x = _model_frames(m, y, labels_2d, floats)
+        floats = floats if x is y else x
+        with encode_precision(encode_dtype_of(m)), decode_precision(decode_dtype_of(m)):
+            _forward_chunks(who, m, y, sess, labels, labels_2d, chunk_size, panels,
+                            lambda beg, end: quantising_frames(), x)
     return out
 
 

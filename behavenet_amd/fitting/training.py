@@ -828,21 +828,14 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
         export_latents(data_generator, best_val_model)
     elif method == 'nll' and hparams.get('export_predictions', False):
         raise NotImplementedError('neural decoders are outside the MI355X hot path')
-    if method == 'ae' and hparams.get('export_frame_errors', False):
-        if is_main:
-            print('exporting frame errors')
-        from behavenet_amd.fitting.eval import export_frame_errors
-        export_frame_errors(data_generator, best_val_model)
-    if method == 'ae' and hparams.get('export_reconstructions', False):
-        if is_main:
-            print('exporting reconstructions')
-        from behavenet_amd.fitting.eval import export_reconstructions
-        export_reconstructions(data_generator, best_val_model)
-    if method == 'ae' and hparams.get('export_pixel_stats', False):
-        if is_main:
-            print('exporting pixel stats')
-        from behavenet_amd.fitting.eval import export_pixel_stats
-        export_pixel_stats(data_generator, best_val_model)
+    # (the hparams key is the exporter's name in fitting.eval; 'export_latents' above is a required key)
+    for key, what in (('export_frame_errors', 'frame errors'), ('export_reconstructions', 'reconstructions'),
+                      ('export_pixel_stats', 'pixel stats')):
+        if method == 'ae' and hparams.get(key, False):
+            if is_main:
+                print('exporting %s' % what)
+            from behavenet_amd.fitting import eval as bn_eval
+            getattr(bn_eval, key)(data_generator, best_val_model)
     if resume and is_main:
         if state_writer is not None:
             state_writer.wait()
