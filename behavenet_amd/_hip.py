@@ -147,6 +147,10 @@ SIGNATURES = {
     'bn_frame_mosaic_u8': (_c_int, [_c_void_p] + [_c_int] * 10 + [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_void_p]),
     'bn_recon_panels_u8': (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p] + [_c_int] * 6
                            + [_c_void_p, _c_size_t, _c_void_p]),
+    'bn_column_select_ws_bytes': (_c_size_t, [_c_int] * 3),
+    'bn_column_count': (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    'bn_column_select': (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t,
+                                                                _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
     'bn_prof_read': (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
@@ -1142,6 +1146,83 @@ def frame_mosaic_u8(frames, src, ch=0, crop=None):
         _ptr(frames, 'frames', dtype=frames.dtype), int(frames.dtype == torch.uint8), P, C, H, W, int(ch), y_min,
         x_min, Hc, Wc, _ptr(src, 'src', dtype=torch.int32), T, R, Cc, _ptr(out, 'out', dtype=torch.uint8), _stream()),
         'bn_frame_mosaic_u8')
+    return out
+
+
+# csrc/column_select.hip's partition, restated for the tests that have to name a row count by it (held against
+# bn_column_select_ws_bytes in tests/test_ranges_cpu.py): CS_HISTS, CS_MIN_ELEMS, CS_TARGET_GROUPS
+COLUMN_SELECT_HISTS, COLUMN_SELECT_MIN_ELEMS, COLUMN_SELECT_TARGET_GROUPS = 60, 1 << 16, 512
+COLUMN_SELECT_MAX_D, COLUMN_SELECT_MAX_R = 1024, 8
+
+
+def column_select_plan(n, d, r):
+    """``(cols, col_groups, slabs, rows)`` of ``bn_column_select`` on an (n, d) table with r rank slots a column:
+    the columns a workgroup takes, the column groups, the row blocks and the rows of a block (cs_plan; r = 0 is
+    the count pass, every column in one group)."""
+    cols = min(COLUMN_SELECT_HISTS // r, d) if r else d
+    col_groups = -(-d // cols)
+    for_chip = max(COLUMN_SELECT_TARGET_GROUPS // col_groups, 1)
+    min_rows = max(COLUMN_SELECT_MIN_ELEMS // d, 1)
+    want = min(for_chip, -(-n // min_rows))
+    rows = -(-n // want)
+    return cols, col_groups, -(-n // rows), rows
+
+
+def _column_table(who, x):
+    """(n, d, ld) of a table the column kernels take: fp32 on the GPU, two dimensions, unit stride along the rows'
+    elements and a row stride ld >= d (a column slice of a contiguous table is served as it is)."""
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise ValueError('%s: expected a table (n, d), got %s'
+                         % (who, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+    if x.dtype != torch.float32:
+        raise ValueError('%s: the table must be float32, got %s' % (who, x.dtype))
+    if not x.is_cuda:
+        raise ValueError('%s: expected the table on the GPU, got device %s (the HIP path has no CPU fallback)'
+                         % (who, x.device))
+    n, d = (int(v) for v in x.shape)
+    if n < 1 or not 1 <= d <= COLUMN_SELECT_MAX_D:
+        raise ValueError('%s: a table of %d rows and %d columns (1 to %d columns are served)'
+                         % (who, n, d, COLUMN_SELECT_MAX_D))
+    ld = d if n == 1 else int(x.stride(0))
+    if (d > 1 and x.stride(1) != 1) or ld < d:
+        raise ValueError('%s: the table\'s rows must be contiguous, got strides %s' % (who, tuple(x.stride())))
+    return n, d, ld
+
+
+def column_count(x):
+    """The number of non-NaN values in every column of the fp32 DEVICE table ``x`` (n, d) as an int64 device tensor
+    (d,), on the current stream (``bn_column_count``, csrc/column_select.hip)."""
+    n, d, ld = _column_table('column_count', x)
+    lib = load()
+    nbytes = lib.bn_column_select_ws_bytes(n, d, 1)
+    out = torch.empty((d,), dtype=torch.int64, device=x.device)
+    _check(lib.bn_column_count(x.data_ptr(), n, d, ld, out.data_ptr(), _arena(x.device, nbytes, 'column_select'), nbytes,
+                               _stream()), 'bn_column_count')
+    return out
+
+
+def column_select(x, ranks):
+    """Exact order statistics of the columns of the fp32 DEVICE table ``x`` (n, d): ``out[k, j]`` is the value of
+    column j with ``ranks[k, j]`` non-NaN values before it in ascending order, NaN where the rank is negative or not
+    below the column's number of non-NaN values.  ``ranks``: int64 (r, d), 1 <= r <= 8, a host array (uploaded) or a
+    device tensor.  -> fp32 device tensor (r, d).  Four passes over the table on the current stream
+    (``bn_column_select``, csrc/column_select.hip); the same bits on every call."""
+    n, d, ld = _column_table('column_select', x)
+    if not torch.is_tensor(ranks):
+        ranks = torch.from_numpy(np.ascontiguousarray(np.asarray(ranks), dtype=np.int64)).to(x.device)
+    if ranks.dim() != 2 or ranks.dtype != torch.int64 or ranks.shape[1] != d:
+        raise ValueError('column_select: expected ranks int64 (r, %d), got %s %s' % (d, ranks.dtype, tuple(ranks.shape)))
+    r = int(ranks.shape[0])
+    if not 1 <= r <= COLUMN_SELECT_MAX_R:
+        raise ValueError('column_select: %d ranks a column (1 to %d are served)' % (r, COLUMN_SELECT_MAX_R))
+    if ranks.device != x.device:
+        raise ValueError('column_select: the table is on %s, the ranks on %s' % (x.device, ranks.device))
+    ranks = ranks.contiguous()
+    lib = load()
+    nbytes = lib.bn_column_select_ws_bytes(n, d, r)
+    out = torch.empty((r, d), dtype=torch.float32, device=x.device)
+    _check(lib.bn_column_select(x.data_ptr(), n, d, ld, ranks.data_ptr(), r, out.data_ptr(),
+                                _arena(x.device, nbytes, 'column_select'), nbytes, _stream()), 'bn_column_select')
     return out
 
 

@@ -100,6 +100,15 @@ int bn_launch_recon_panels(const void* orig, int orig_u8, const void* recon, int
                            int mask_per_frame, int N, int C, int H, int W, int show_orig, unsigned char* out,
                            size_t out_frame_stride, hipStream_t st);
 
+// column_select.hip: exact per-column order statistics of an fp32 table (n, d) with leading dimension ld, NaNs taking
+// no part: the valid counts, and the values at r device ranks a column by a four-digit radix select
+bool bn_column_select_ok(int n, int d, int ld, int r);
+size_t bn_column_count_ws_bytes_impl(int n, int d);
+size_t bn_column_select_ws_bytes_impl(int n, int d, int r);
+int bn_launch_column_count(const float* x, int n, int d, int ld, long long* n_valid, void* ws, hipStream_t st);
+int bn_launch_column_select(const float* x, int n, int d, int ld, const long long* ranks, int r, float* out, void* ws,
+                            hipStream_t st);
+
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);
 int bn_launch_bn_stats(const float* x, float* mean, float* var, int N, int C, int HW, void* ws,

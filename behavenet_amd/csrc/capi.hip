@@ -1985,6 +1985,29 @@ extern "C" int bn_recon_panels_u8(const void* orig, int orig_u8, const void* rec
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Per-column order statistics of an fp32 table (column_select.hip): the ranges of latents and labels.
+extern "C" size_t bn_column_select_ws_bytes(int n, int d, int r) { return bn_column_select_ws_bytes_impl(n, d, r); }
+
+extern "C" int bn_column_count(const float* x, int n, int d, int ld, long long* n_valid, void* ws, size_t ws_bytes,
+                               bn_stream_t stream) {
+    if (!bn_column_select_ok(n, d, ld, 1)) return BN_E_SHAPE;
+    if (!x || !n_valid || !ws) return BN_E_BADARG;
+    // (an fp32 operand that is not even 4-byte aligned cannot be read at all)
+    if (((uintptr_t)x & 3) || ((uintptr_t)n_valid & 7) || !aligned16(ws)) return BN_E_SHAPE;
+    if (ws_bytes < bn_column_count_ws_bytes_impl(n, d)) return BN_E_SHAPE;
+    return bn_launch_column_count(x, n, d, ld, n_valid, ws, (hipStream_t)stream);
+}
+
+extern "C" int bn_column_select(const float* x, int n, int d, int ld, const long long* ranks, int r, float* out,
+                                void* ws, size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_column_select_ok(n, d, ld, r)) return BN_E_SHAPE;
+    if (!x || !ranks || !out || !ws) return BN_E_BADARG;
+    if (((uintptr_t)x & 3) || ((uintptr_t)out & 3) || ((uintptr_t)ranks & 7) || !aligned16(ws)) return BN_E_SHAPE;
+    if (ws_bytes < bn_column_select_ws_bytes_impl(n, d, r)) return BN_E_SHAPE;
+    return bn_launch_column_select(x, n, d, ld, ranks, r, out, ws, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // fp32 unit-float frames -> stored uint8 grey levels (recon_u8.hip): NaN -> 0, else clamp(rint(x * 255), 0, 255).
 extern "C" int bn_unit_float_to_u8(const float* in, unsigned char* out, size_t n, bn_stream_t stream) {
     if (!in || !out) return BN_E_BADARG;

@@ -1,7 +1,8 @@
 """Inference-only passes over every trial: latents -> ``*_latents.pkl`` (BASELINE config 5), per-frame
 reconstruction errors -> ``*_frame_errors.pkl``, uint8 reconstructions -> ``*_reconstructions.npz`` and per-pixel
 error / moment maps -> ``*_pixel_stats.pkl``; latent traversals as uint8 mosaics and movies, decoded in one batch
-and tiled on the device; and reconstruction movies (original, reconstruction, residual) as uint8 strips.
+and tiled on the device; reconstruction movies (original, reconstruction, residual) as uint8 strips; and the
+percentile ranges of latents and labels, selected on the device.
 
 Mirror of ``export_latents`` in the reference ``behavenet/fitting/eval.py:6-118``: same pickle
 schema ``{'latents': [per-trial (T x D) arrays, empty for gap trials], 'trials': batch_idxs}``
@@ -29,7 +30,9 @@ __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconst
            'frame_errors', 'frame_errors_device', 'export_reconstructions', 'reconstruct_trial',
            'reconstruct_trial_device', 'export_pixel_stats', 'pixel_stats', 'pixel_stats_device',
            'summarise_pixel_stats', 'traversal_points', 'traverse_latents', 'traverse_latents_device',
-           'traversal_movie', 'traversal_movie_device', 'reconstruction_movie', 'reconstruction_movie_device']
+           'traversal_movie', 'traversal_movie_device', 'reconstruction_movie', 'reconstruction_movie_device',
+           'percentile_plan', 'percentile_lerp', 'column_percentiles', 'compute_range', 'latent_ranges',
+           'latent_ranges_device']
 
 
 def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -1090,3 +1093,158 @@ def reconstruction_movie(model, y, sess=None, masks=None, labels=None, labels_2d
     """``reconstruction_movie_device`` as a numpy array ``(T, R * H, 3 * C * W)`` of uint8."""
     return reconstruction_movie_device(model, y, sess, masks, labels, labels_2d, max_frames, chunk_size,
                                        extra_models).cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------ ranges
+def percentile_plan(n_valid, ps, dtype=np.float32):
+    """Where ``np.nanpercentile(values, p, axis=0)`` of ``dtype`` values reads a column of ``n_valid[j]`` non-NaN
+    values, for every ``p`` of ``ps``: ``(ranks, gammas)`` with ``ranks`` int64 ``(2 len(ps), D)`` -- rows 2 i and
+    2 i + 1 are the zero-based ranks ``lo`` and ``hi`` of ``ps[i]`` among the column's sorted valid values -- and
+    ``gammas`` of ``dtype``, ``(len(ps), D)``, the weight between them.  numpy's own float arithmetic (2.2: the
+    'linear' method on float32 data with a Python-scalar percentile), restated:
+
+        q = p / dtype(100);  vi = dtype(m - 1) * q;  lo = floor(vi), hi = lo + 1, both m - 1 where vi >= m - 1;
+        gamma = vi - floor(vi)
+
+    An empty column (``m == 0``) gets rank -1, which the selection answers with NaN as ``nanpercentile`` does."""
+    m = np.asarray(n_valid, dtype=np.int64).reshape(-1)
+    ps = [ps] if np.isscalar(ps) else list(ps)
+    ranks = np.empty((2 * len(ps), m.size), dtype=np.int64)
+    gammas = np.empty((len(ps), m.size), dtype=dtype)
+    top = np.maximum(m - 1, 0)
+    top_f = top.astype(dtype)
+    for i, p in enumerate(ps):
+        q = np.true_divide(p, dtype(100))
+        vi = top_f * q
+        fl = np.floor(vi)
+        lo = np.minimum(fl.astype(np.int64), top)
+        hi = np.minimum(lo + 1, top)
+        above = vi >= top_f
+        lo[above] = top[above]
+        hi[above] = top[above]
+        ranks[2 * i] = np.where(m > 0, lo, -1)
+        ranks[2 * i + 1] = np.where(m > 0, hi, -1)
+        gammas[i] = vi - fl
+    return ranks, gammas
+
+
+def percentile_lerp(lo, hi, gammas):
+    """numpy's interpolation between the two selected neighbours, in their dtype: with ``diff = hi - lo``,
+    ``lo + diff * g`` where ``g < 0.5`` and ``hi - diff * (1 - g)`` elsewhere (``np.lib._function_base_impl._lerp``).
+    Two equal infinities give NaN, as they do there."""
+    lo, hi, g = np.asarray(lo), np.asarray(hi), np.asarray(gammas)
+    with np.errstate(invalid='ignore', over='ignore'):
+        diff = hi - lo
+        out = lo + diff * g
+        upper = hi - diff * (1 - g)
+    return np.where(g >= 0.5, upper, out).astype(lo.dtype, copy=False)
+
+
+def column_percentiles(table, ps):
+    """``np.nanpercentile(table, p, axis=0)`` for every ``p`` of ``ps`` (at most four) on a float32 DEVICE table
+    ``(n, D)``, as a float32 numpy array ``(len(ps), D)`` with numpy's bits: ONE ``bn_column_count`` for the columns'
+    valid counts (D integers to the host), the ranks named on the host (``percentile_plan``), ONE ``bn_column_select``
+    for both neighbours of every percentile, and numpy's float32 interpolation of the ``2 len(ps) D`` selected values
+    (``percentile_lerp``).  The table stays on the device and is not changed."""
+    ps = list(ps)
+    n_valid = _hip.column_count(table).cpu().numpy()
+    ranks, gammas = percentile_plan(n_valid, ps)
+    sel = _hip.column_select(table, torch.from_numpy(ranks).to(table.device)).cpu().numpy()
+    return percentile_lerp(sel[0::2], sel[1::2], gammas)
+
+
+def _table_ranges(table, min_p, max_p):
+    got = column_percentiles(table, (min_p, max_p, 50))
+    return {'min': got[0], 'max': got[1], 'med': got[2]}
+
+
+def _ranges_device():
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def stack_for_ranges(values_list, device=None):
+    """The entries of ``values_list`` -- numpy arrays or tensors ``(n_i, D)``, entries of length 0 skipped as the
+    reference's ``compute_range`` skips the gap trials of a latents pickle -- as ONE float32 device table: numpy
+    entries are stacked on the host and uploaded once, device entries concatenated where they are."""
+    kept = [v for v in values_list if len(v) != 0]
+    if not kept:
+        raise ValueError('compute_range: no values (every entry of values_list is empty)')
+    for v in kept:
+        if np.ndim(v) != 2 or v.shape[1] != kept[0].shape[1]:
+            raise ValueError('compute_range: expected entries (n_i, %d), got %s'
+                             % (kept[0].shape[1] if np.ndim(kept[0]) == 2 else -1, tuple(np.shape(v))))
+    tensors = [v for v in kept if torch.is_tensor(v)]
+    if device is None:
+        on_device = [t.device for t in tensors if t.is_cuda]
+        device = on_device[0] if on_device else _ranges_device()
+    parts = []
+    host = [np.asarray(v, dtype=np.float32) for v in kept if not torch.is_tensor(v)]
+    if host:
+        parts.append(torch.from_numpy(np.ascontiguousarray(np.vstack(host))).to(device))
+    parts.extend(t.detach().to(device=device, dtype=torch.float32) for t in tensors)
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+
+def compute_range(values_list, min_p=5, max_p=95):
+    """``plotting.cond_ae_utils.compute_range``: see there."""
+    return _table_ranges(stack_for_ranges(values_list), min_p, max_p)
+
+
+def _latent_table(data_generator, model, sess_idx):
+    """The latents of every train / val / test trial of the sessions ``sess_idx`` as ONE device table, encoded as
+    ``export_latents`` encodes them; None on the ranks other than 0."""
+    _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return None
+    n_sess = len(data_generator.datasets)
+    if sess_idx is None:
+        wanted = set(range(n_sess))
+    elif isinstance(sess_idx, (list, tuple, np.ndarray)):
+        wanted = set(int(s) for s in sess_idx)
+    else:
+        wanted = {int(sess_idx)}
+    if not wanted or min(wanted) < 0 or max(wanted) >= n_sess:
+        raise ValueError('latent_ranges: sessions %s of a generator with %d' % (sorted(wanted), n_sess))
+    encode = _GraphedTrialEncoder(model)
+    parts = []
+
+    def on_device(images, sess, data, trial):
+        return encode(images, sess, _batch_fields(model, data)[2]) if sess in wanted else None
+
+    def on_host(images, sess, data, trial):
+        return encode_trial(model, images, sess, _batch_fields(model, data)[2]) if sess in wanted else None
+
+    def sink(sess, trial, result):
+        if result is not None and len(result):
+            parts.append(result)
+    _export_per_trial('latent_ranges', data_generator, model, on_device, on_host, sink=sink)
+    if not parts:
+        raise ValueError('latent_ranges: the sessions %s have no train, val or test trial' % sorted(wanted))
+    return stack_for_ranges(parts, device=next(model.parameters()).device)
+
+
+def latent_ranges(data_generator, model, sess_idx=None, min_p=5, max_p=95):
+    """The ranges of a model's latents, ``{'min', 'max', 'med'}`` as ``(D,)`` float32 arrays: the ``min_p``-th,
+    ``max_p``-th and 50th percentile per latent over every frame of every train / val / test trial of the sessions
+    ``sess_idx`` (one index, a list, or None for all) -- what the reference's ``get_input_range('latents', ...)``
+    computes from a latents pickle (``compute_range``, plotting/cond_ae_utils.py:148-178) and hands to its traversals
+    as ``mins`` and ``maxes``.
+
+    The trials are walked and encoded as ``export_latents`` walks and encodes them (the same per-trial encoder and
+    batch fields, so the latents have its bits; ``hparams['hip_encode_dtype']`` is honoured), but they stay in one
+    device table and the percentiles are selected there (``column_percentiles``): the counts and the selected
+    neighbours are all that crosses to the host.
+
+    Under ``torch.distributed`` order statistics do not combine across ranks the way sums do: rank 0 alone walks
+    every trial (the one-process sink form of the trial walk, no collective is entered) and the other ranks return
+    None at once."""
+    table = _latent_table(data_generator, model, sess_idx)
+    return None if table is None else _table_ranges(table, min_p, max_p)
+
+
+def latent_ranges_device(data_generator, model, sess_idx=None, min_p=5, max_p=95):
+    """``latent_ranges`` as a float32 DEVICE tensor ``(3, D)``: the rows min, max, med (None off rank 0)."""
+    table = _latent_table(data_generator, model, sess_idx)
+    if table is None:
+        return None
+    return torch.from_numpy(column_percentiles(table, (min_p, max_p, 50))).to(table.device)

@@ -1,5 +1,6 @@
 """Latent and label traversals with the reference's signatures (``behavenet/plotting/cond_ae_utils.py``:
-``interpolate_1d``, ``interpolate_2d``), decoded in ONE batch.
+``interpolate_1d``, ``interpolate_2d``), decoded in ONE batch, and the ranges they sweep (``get_input_range``,
+``compute_range``), selected on the device.
 
 The reference calls ``get_reconstruction`` once per point: P launch chains of one frame and P copies to the host.
 Here the points are collected into one table (``fitting.eval.traversal_points``) and ``get_reconstruction`` is called
@@ -7,13 +8,17 @@ once on it; the lists that come back have the reference's nesting and dtypes.  F
 cropped, quantised and tiled on the device, with only the uint8 result crossing to the host -- see
 ``fitting.eval.traverse_latents`` and ``traversal_movie``.  Nothing here imports matplotlib."""
 
+import os
+import pickle
+
 import numpy as np
 import torch
 
+from behavenet_amd.fitting import eval as _eval
 from behavenet_amd.fitting.eval import get_reconstruction, traversal_points
 from behavenet_amd.plotting import get_crop
 
-__all__ = ['interpolate_1d', 'interpolate_2d']
+__all__ = ['interpolate_1d', 'interpolate_2d', 'get_input_range', 'compute_range']
 
 _PLAIN = ('ae', 'vae', 'beta-tcvae', 'ps-vae', 'msps-vae')
 _COND = ('cond-ae', 'cond-vae')
@@ -140,3 +145,95 @@ def interpolate_1d(
     ``input_idxs[0]`` and ``input_idxs[1]``, as there."""
     return _interpolate('1d', interp_type, model, ims_0, latents_0, labels_0, labels_sc_0, mins, maxes, input_idxs,
                         n_frames, crop_type, mins_sc, maxes_sc, crop_kwargs, marker_idxs, ch)
+
+
+# ------------------------------------------------------------------------------------------ ranges
+def compute_range(values_list, min_p=5, max_p=95):
+    """The ``min_p``-th, ``max_p``-th and 50th percentile of every column of the vertically stacked ``values_list``,
+    NaNs ignored: ``{'min', 'max', 'med'}``, each a ``(D,)`` float32 array -- the reference's ``compute_range``
+    (cond_ae_utils.py:148-178) with its parameters, and ``np.nanpercentile``'s float32 numbers bit for bit.
+
+    The entries are numpy arrays or device tensors ``(n_i, D)``; entries of length 0 (the gap trials of a latents
+    pickle) are skipped; numpy entries are stacked and uploaded once and anything else is made float32.  The three
+    percentiles come from ONE count and ONE select call on the device table (``fitting.eval.column_percentiles``:
+    exact order statistics by a radix select, csrc/column_select.hip); the valid counts and the six selected
+    neighbours of every column are all that comes back.  There is no CPU fallback."""
+    return _eval.compute_range(values_list, min_p=min_p, max_p=max_p)
+
+
+def _session_list(sess_idx):
+    return [int(s) for s in sess_idx] if isinstance(sess_idx, (list, tuple, np.ndarray)) else [sess_idx]
+
+
+def _latents_file(hparams, sess_ids, s_idx, version):
+    ids = sess_ids[s_idx] if (sess_ids is not None and s_idx is not None) else hparams
+    name = '%s_%s_%s_%s_latents.pkl' % (ids['lab'], ids['expt'], ids['animal'], ids['session'])
+    return os.path.join(hparams['expt_dir'], 'version_%i' % version, name)
+
+
+def _trial_signal(dataset, signal, trial):
+    """One trial's ``signal`` (T, L) as a float32 numpy array from a session of a data generator: read from a
+    file-backed session's store with its transform applied, or taken from a synthetic session's list."""
+    if hasattr(dataset, 'read') and signal in getattr(dataset, 'signals', ()):
+        arr = np.asarray(dataset.read(signal, trial)).astype(np.float32)
+        transform = dataset.transforms.get(signal)
+        return transform(arr) if transform else arr
+    trials = getattr(dataset, signal, None)
+    if trials is None:
+        raise KeyError(signal)
+    arr = trials[trial]
+    return (arr.detach().cpu().numpy() if torch.is_tensor(arr) else np.asarray(arr)).astype(np.float32)
+
+
+def _session_signal(data_gen, signal, sessions):
+    out = []
+    for s_idx in sessions:
+        dataset = data_gen.datasets[0 if s_idx is None else s_idx]
+        for dtype in ('train', 'val', 'test'):
+            out.extend(_trial_signal(dataset, signal, int(t)) for t in dataset.batch_idxs[dtype])
+    return out
+
+
+def get_input_range(input_type, hparams, sess_ids=None, sess_idx=0, model=None, data_gen=None, version=0, min_p=5,
+                    max_p=95, apply_label_masks=False):
+    """The range of one kind of input, ``{'min', 'max', 'med'}`` (``compute_range``), with the reference's signature
+    (cond_ae_utils.py:43-145).
+
+    ``'latents'``: from the latents pickle(s) of session ``sess_idx`` (one index or a list) in
+    ``hparams['expt_dir']/version_<version>`` where they exist -- named by ``sess_ids[sess_idx]``, or by ``hparams``
+    without ``sess_ids`` -- and otherwise from ``fitting.eval.latent_ranges(data_gen, model, sess_idx)``, which
+    encodes the trials as ``export_latents`` would and gives the same numbers without writing and re-reading a file.
+    ``'labels'`` / ``'labels_sc'``: that signal of every train, val and test trial of the session(s), taken from
+    ``data_gen`` -- the reference rebuilds a generator from ``hparams``; here ``data_gen`` is required (ValueError
+    without it).  ``apply_label_masks`` sets the labels whose ``labels_masks`` entry is 0 to NaN first, and NaNs take
+    no part in a percentile.  Any other ``input_type`` is a NotImplementedError."""
+    sessions = _session_list(sess_idx)
+    if input_type == 'latents':
+        files = [_latents_file(hparams, sess_ids, s_idx, version) for s_idx in sessions]
+        if all(os.path.exists(f) for f in files):
+            inputs = []
+            for f in files:
+                with open(f, 'rb') as fh:
+                    inputs += list(pickle.load(fh)['latents'])
+            return compute_range(inputs, min_p=min_p, max_p=max_p)
+        if model is None or data_gen is None:
+            raise ValueError('get_input_range: no latents file at %s; pass model and data_gen to compute the latents'
+                             % [f for f in files if not os.path.exists(f)][0])
+        return _eval.latent_ranges(data_gen, model, sess_idx, min_p=min_p, max_p=max_p)
+    if input_type not in ('labels', 'labels_sc'):
+        raise NotImplementedError(input_type)
+    if data_gen is None:
+        raise ValueError('get_input_range: %r needs data_gen, the generator that serves the session\'s %s'
+                         % (input_type, input_type))
+    try:
+        inputs = _session_signal(data_gen, input_type, sessions)
+    except KeyError:
+        raise ValueError('get_input_range: data_gen does not serve %r' % input_type)
+    if apply_label_masks and input_type == 'labels':
+        try:
+            masks = _session_signal(data_gen, 'labels_masks', sessions)
+        except KeyError:
+            print('no label masks!')
+            masks = []
+        inputs = [np.where(m == 0, np.float32(np.nan), i) for i, m in zip(inputs, masks)] if masks else inputs
+    return compute_range(inputs, min_p=min_p, max_p=max_p)

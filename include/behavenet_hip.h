@@ -617,6 +617,32 @@ int bn_recon_panels_u8(const void* orig, int orig_u8, const void* recon, int rec
                        int mask_per_frame, int n, int c, int h, int w, int show_orig, unsigned char* out,
                        size_t out_frame_stride, bn_stream_t stream);
 
+/* Exact per-column order statistics of a table, selected on the device (replaces the np.nanpercentile calls of
+ * compute_range, plotting/cond_ae_utils.py:148-178, on the stacked latents or labels): x is fp32 (n, d), row-major
+ * with leading dimension ld >= d (columns from d on are not counted), and is never written.  Values are ordered by
+ * the key that flips all bits of a negative value and the sign bit of any other: infinities and denormals are
+ * ordinary values, -0.0 sorts directly below +0.0 (a selected zero may carry either sign; the two are equal under
+ * ==), and a NaN of any sign or payload takes no part.
+ *
+ * bn_column_count: n_valid[j], int64 (d,) = the number of non-NaN values of column j -- what a caller needs
+ * before it can name ranks among the valid values.
+ * bn_column_select: ranks is a DEVICE table int64 (r, d), zero-based among a column's valid values in ascending
+ * order; out fp32 (r, d), out[k, j] = the value of column j with exactly ranks[k, j] valid values before it in
+ * sorted order, NaN for a rank below 0 or at least n_valid[j] (an all-NaN column is reported so; no error).  A
+ * rank may repeat among a column's slots.  Four passes over the table, one per 8-bit digit of the key, each
+ * followed by a small launch that sums the workgroups' histograms and narrows every slot's prefix; counts are
+ * integers and no global atomics are used, so the result is the same bits on every call.
+ * ws: bn_column_select_ws_bytes(n, d, r) bytes on a 16-byte boundary (it serves bn_column_count for the same n and
+ * d too, for any r).  Nothing is read from it that the call has not written.
+ * BN_E_SHAPE (nothing written): n < 1, d < 1 or d > 1024, ld < d, r < 1 or r > 8 (the query returns 0 for
+ * these), a workspace smaller than the query's, x or out off a 4-byte, ranks or n_valid off an 8-byte, ws off a
+ * 16-byte boundary.  BN_E_BADARG: a NULL pointer. */
+size_t bn_column_select_ws_bytes(int n, int d, int r);
+int bn_column_count(const float* x, int n, int d, int ld, long long* n_valid, void* ws, size_t ws_bytes,
+                    bn_stream_t stream);
+int bn_column_select(const float* x, int n, int d, int ld, const long long* ranks, int r, float* out,
+                     void* ws, size_t ws_bytes, bn_stream_t stream);
+
 /* unit-float frames -> stored uint8 grey levels, the inverse of bn_u8_to_unit_float on k / 255:
  *   out[i] = NaN -> 0, else clamp(rint(in[i] * 255), 0, 255)
  * The product is one fp32 multiplication and rint rounds half to even, i.e. numpy's
