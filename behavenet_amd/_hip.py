@@ -151,6 +151,9 @@ SIGNATURES = {
     'bn_column_count': (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     'bn_column_select': (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_size_t,
                                                                 _c_void_p]),
+    'bn_segment_label_sums_ws_bytes': (_c_size_t, [_c_int] * 3),
+    'bn_segment_label_sums': (_c_int, [_c_void_p, _c_int] * 3 + [_c_void_p] + [_c_int] * 3
+                              + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
     'bn_prof_read': (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
@@ -1223,6 +1226,63 @@ def column_select(x, ranks):
     out = torch.empty((r, d), dtype=torch.float32, device=x.device)
     _check(lib.bn_column_select(x.data_ptr(), n, d, ld, ranks.data_ptr(), r, out.data_ptr(),
                                 _arena(x.device, nbytes, 'column_select'), nbytes, _stream()), 'bn_column_select')
+    return out
+
+
+# csrc/segment_sums.hip's partition, restated for the tests that have to name a row count by it (held against
+# bn_segment_label_sums_ws_bytes in tests/test_label_r2_cpu.py): SL_MIN_ELEMS, SL_TARGET_GROUPS, SL_MAX_L
+_SEGMENT_SUMS_MIN_ELEMS, _SEGMENT_SUMS_TARGET_GROUPS, _SEGMENT_SUMS_MAX_L = 1 << 14, 1024, 64
+
+
+def _segment_sums_plan(n, L):
+    """``(blocks, rows)`` of ``bn_segment_label_sums`` on tables of n rows and L columns: the row blocks and the rows
+    of a block, the last block taking what is left (sl_plan)."""
+    if n < 1:
+        return 0, 1
+    want = min(-(-n // (_SEGMENT_SUMS_MIN_ELEMS // L)), _SEGMENT_SUMS_TARGET_GROUPS)
+    rows = -(-n // want)
+    return -(-n // rows), rows
+
+
+def _label_table(name, x, like=None):
+    """(n, L, ld) of a table ``bn_segment_label_sums`` takes (``_column_table``'s conditions, at most 64 columns, and
+    the shape of ``like``)."""
+    n, L, ld = _column_table('segment_label_sums (%s)' % name, x)
+    if L > _SEGMENT_SUMS_MAX_L:
+        raise ValueError('segment_label_sums: %d columns (1 to %d are served)' % (L, _SEGMENT_SUMS_MAX_L))
+    if like is not None and x.shape != like.shape:
+        raise ValueError('segment_label_sums: pred is %s, %s is %s' % (tuple(like.shape), name, tuple(x.shape)))
+    return n, L, ld
+
+
+def segment_label_sums(pred, truth, mask, offsets):
+    """Per row segment and column, the count, ``sum y``, ``sum y^2`` and ``sum (y - p)^2`` over the valid entries of
+    the fp32 DEVICE tables ``pred`` (p) and ``truth`` (y), both (n, L) with L <= 64: a float64 device tensor
+    ``(S, L, 4)``, on the current stream (``bn_segment_label_sums``, csrc/segment_sums.hip).  ``mask`` is None (every
+    entry is valid) or a table (n, L): an entry is valid where the mask is exactly 1.  ``offsets``: int64 (S + 1), a
+    host array (uploaded) or a device tensor; segment s is the rows ``[offsets[s], offsets[s + 1])``.  The tables may
+    be the first L columns of wider ones.  Terms and sums are float64; the same bits on every call."""
+    n, L, ld_pred = _label_table('pred', pred)
+    ld_truth = _label_table('truth', truth, pred)[2]
+    ld_mask = 0 if mask is None else _label_table('mask', mask, pred)[2]
+    if not torch.is_tensor(offsets):
+        offsets = torch.from_numpy(np.ascontiguousarray(np.asarray(offsets), dtype=np.int64)).to(pred.device)
+    if offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.numel() < 1:
+        raise ValueError('segment_label_sums: expected offsets int64 (S + 1,), got %s %s'
+                         % (offsets.dtype, tuple(offsets.shape)))
+    for name, t in (('truth', truth), ('mask', mask), ('offsets', offsets)):
+        if t is not None and t.device != pred.device:
+            raise ValueError('segment_label_sums: pred is on %s, %s on %s' % (pred.device, name, t.device))
+    offsets = offsets.contiguous()
+    S = int(offsets.numel()) - 1
+    lib = load()
+    nbytes = lib.bn_segment_label_sums_ws_bytes(n, S, L)
+    out = torch.empty((S, L, 4), dtype=torch.float64, device=pred.device)
+    if S:
+        _check(lib.bn_segment_label_sums(pred.data_ptr(), ld_pred, truth.data_ptr(), ld_truth,
+                                         None if mask is None else mask.data_ptr(), ld_mask, offsets.data_ptr(), S, L,
+                                         n, out.data_ptr(), _arena(pred.device, nbytes, 'segment_sums'), nbytes,
+                                         _stream()), 'bn_segment_label_sums')
     return out
 
 

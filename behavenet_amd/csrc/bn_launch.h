@@ -109,6 +109,14 @@ int bn_launch_column_count(const float* x, int n, int d, int ld, long long* n_va
 int bn_launch_column_select(const float* x, int n, int d, int ld, const long long* ranks, int r, float* out, void* ws,
                             hipStream_t st);
 
+// segment_sums.hip: per row segment and column, the count, sum y, sum y^2 and sum (y - p)^2 of the valid entries of
+// fp32 tables (n, L) in float64 -- the sums behind the per-trial label R^2 and MSE
+bool bn_segment_label_sums_ok(int n, int S, int L);
+size_t bn_segment_label_sums_ws_bytes_impl(int n, int S, int L);
+int bn_launch_segment_label_sums(const float* pred, int ld_pred, const float* truth, int ld_truth, const float* mask,
+                                 int ld_mask, const long long* offsets, int S, int L, int n, double* out, void* ws,
+                                 hipStream_t st);
+
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);
 int bn_launch_bn_stats(const float* x, float* mean, float* var, int N, int C, int HW, void* ws,

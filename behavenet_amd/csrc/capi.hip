@@ -2008,6 +2008,25 @@ extern "C" int bn_column_select(const float* x, int n, int d, int ld, const long
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Masked column sums per row segment (segment_sums.hip): the sums behind the per-trial label R^2 and MSE.
+extern "C" size_t bn_segment_label_sums_ws_bytes(int n, int S, int L) {
+    return bn_segment_label_sums_ws_bytes_impl(n, S, L);
+}
+
+extern "C" int bn_segment_label_sums(const float* pred, int ld_pred, const float* truth, int ld_truth,
+                                     const float* mask, int ld_mask, const long long* offsets, int S, int L, int n,
+                                     double* out, void* ws, size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_segment_label_sums_ok(n, S, L) || ld_pred < L || ld_truth < L || (mask && ld_mask < L)) return BN_E_SHAPE;
+    if (!pred || !truth || !offsets || !out || !ws) return BN_E_BADARG;
+    if (((uintptr_t)pred & 3) || ((uintptr_t)truth & 3) || ((uintptr_t)mask & 3) || ((uintptr_t)offsets & 7) ||
+        ((uintptr_t)out & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_segment_label_sums_ws_bytes_impl(n, S, L)) return BN_E_SHAPE;
+    return bn_launch_segment_label_sums(pred, ld_pred, truth, ld_truth, mask, ld_mask, offsets, S, L, n, out, ws,
+                                        (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // fp32 unit-float frames -> stored uint8 grey levels (recon_u8.hip): NaN -> 0, else clamp(rint(x * 255), 0, 255).
 extern "C" int bn_unit_float_to_u8(const float* in, unsigned char* out, size_t n, bn_stream_t stream) {
     if (!in || !out) return BN_E_BADARG;

@@ -1,8 +1,9 @@
 """Inference-only passes over every trial: latents -> ``*_latents.pkl`` (BASELINE config 5), per-frame
 reconstruction errors -> ``*_frame_errors.pkl``, uint8 reconstructions -> ``*_reconstructions.npz`` and per-pixel
 error / moment maps -> ``*_pixel_stats.pkl``; latent traversals as uint8 mosaics and movies, decoded in one batch
-and tiled on the device; reconstruction movies (original, reconstruction, residual) as uint8 strips; and the
-percentile ranges of latents and labels, selected on the device.
+and tiled on the device; reconstruction movies (original, reconstruction, residual) as uint8 strips; the
+percentile ranges of latents and labels, selected on the device; and the per-trial label R^2 and MSE of the models
+with supervised latents -> ``r2_supervised.csv``, reduced on the device.
 
 Mirror of ``export_latents`` in the reference ``behavenet/fitting/eval.py:6-118``: same pickle
 schema ``{'latents': [per-trial (T x D) arrays, empty for gap trials], 'trials': batch_idxs}``
@@ -32,7 +33,7 @@ __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconst
            'summarise_pixel_stats', 'traversal_points', 'traverse_latents', 'traverse_latents_device',
            'traversal_movie', 'traversal_movie_device', 'reconstruction_movie', 'reconstruction_movie_device',
            'percentile_plan', 'percentile_lerp', 'column_percentiles', 'compute_range', 'latent_ranges',
-           'latent_ranges_device']
+           'latent_ranges_device', 'summarise_label_sums', 'label_r2', 'export_label_r2']
 
 
 def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -191,8 +192,10 @@ def _export_setup(model):
     return int(model.hparams.get('export_chunk_frames', 1024))
 
 
-def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn=None, sink=None, sink_sharded=False):
-    """The trial walk the exporters share: every train / val / test trial of every session goes once through
+def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn=None, sink=None, sink_sharded=False,
+                      dtypes=('train', 'val', 'test')):
+    """The trial walk the exporters share: every train / val / test trial of every session (or the trials of the splits
+    ``dtypes`` alone, in that order; the trials of other splits are not read) goes once through
     ``on_device_fn(images, sess, data, trial)`` (device-resident frames; the results stay on the device and come to
     the host in ONE transfer at the end) or ``on_host_fn(images, sess, data, trial)`` (-> numpy; by default the
     device function's result brought to the host).  Under ``torch.distributed`` a trial is owned by its identity and
@@ -219,7 +222,7 @@ def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn=None,
     # sorted list of all (session, trial) pairs), not of the order in which the generator
     # happens to serve it on this rank
     wanted = sorted((s_, int(t)) for s_, ds in enumerate(data_generator.datasets)
-                    for dt in ('train', 'val', 'test') for t in ds.batch_idxs[dt])
+                    for dt in dtypes for t in ds.batch_idxs[dt])
     owner = {key: i % world for i, key in enumerate(wanted)}
     # generators that can be told to pass over a trial (this package's) are asked not to read,
     # copy or convert the other ranks' trials -- round 4 fetched every trial on every rank -- and to
@@ -240,7 +243,7 @@ def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn=None,
         data_generator.serve_uint8 = True
     on_device = {}          # (session, trial) -> device tensor: ONE transfer to the host at the end
     try:
-        for dtype in ['train', 'val', 'test']:
+        for dtype in dtypes:
             data_generator.reset_iterators(dtype)
             n_batches = data_generator.n_tot_batches[dtype]
             if single and dtype == 'train':      # the multi generator counts training ITERATIONS
@@ -1190,12 +1193,8 @@ def compute_range(values_list, min_p=5, max_p=95):
     return _table_ranges(stack_for_ranges(values_list), min_p, max_p)
 
 
-def _latent_table(data_generator, model, sess_idx):
-    """The latents of every train / val / test trial of the sessions ``sess_idx`` as ONE device table, encoded as
-    ``export_latents`` encodes them; None on the ranks other than 0."""
-    _export_setup(model)
-    if bdist.world_size() > 1 and bdist.rank() != 0:
-        return None
+def _wanted_sessions(who, data_generator, sess_idx):
+    """The sessions ``sess_idx`` names -- one index, a list, or None for all -- as a set."""
     n_sess = len(data_generator.datasets)
     if sess_idx is None:
         wanted = set(range(n_sess))
@@ -1204,7 +1203,17 @@ def _latent_table(data_generator, model, sess_idx):
     else:
         wanted = {int(sess_idx)}
     if not wanted or min(wanted) < 0 or max(wanted) >= n_sess:
-        raise ValueError('latent_ranges: sessions %s of a generator with %d' % (sorted(wanted), n_sess))
+        raise ValueError('%s: sessions %s of a generator with %d' % (who, sorted(wanted), n_sess))
+    return wanted
+
+
+def _latent_table(data_generator, model, sess_idx):
+    """The latents of every train / val / test trial of the sessions ``sess_idx`` as ONE device table, encoded as
+    ``export_latents`` encodes them; None on the ranks other than 0."""
+    _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return None
+    wanted = _wanted_sessions('latent_ranges', data_generator, sess_idx)
     encode = _GraphedTrialEncoder(model)
     parts = []
 
@@ -1248,3 +1257,182 @@ def latent_ranges_device(data_generator, model, sess_idx=None, min_p=5, max_p=95
     if table is None:
         return None
     return torch.from_numpy(column_percentiles(table, (min_p, max_p, 50))).to(table.device)
+
+
+# ------------------------------------------------------------------------------------------ label scores
+LABEL_R2_CLASSES = ('ps-vae', 'msps-vae', 'cond-ae-msp')          # the classes with a supervised block of latents
+LABEL_R2_MODEL = 'MSPS-VAE'          # the 'Model' column of r2_supervised.csv: the reference's literal, for every class
+
+
+def _check_label_r2_class(who, model_class):
+    if model_class not in LABEL_R2_CLASSES:
+        raise ValueError('%s: model class %r has no supervised latents (label scores are served for %s)'
+                         % (who, model_class, ', '.join(LABEL_R2_CLASSES)))
+
+
+def _scores_from_sums(n, sy, syy, sd):
+    """``(r2, mse, ss_tot)`` from the four sums, elementwise in float64: ``mse = sd / n``, ``ss_tot = syy - sy^2 / n``,
+    ``r2 = 1 - sd / ss_tot``; where ``ss_tot`` is zero sklearn's rule for a constant ``y_true`` holds (1.0 for a
+    perfect prediction, else 0.0).  ``ss_tot`` is a difference of two sums that each carry a rounding error of up to
+    ``n 2^-53`` of their size, so a value within ``8 n 2^-53 syy`` of zero IS zero as far as the sums can tell (a
+    column that is constant over its valid entries lands there, exactly zero only when its sums happen to be exact)
+    and is set to it.  Entries without a valid value are NaN."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mse = sd / n
+        ss_tot = syy - sy * sy / n
+        ss_tot = np.where(np.abs(ss_tot) <= 8.0 * n * 2.0 ** -53 * np.abs(syy), 0.0, ss_tot)
+        r2 = 1.0 - sd / ss_tot
+    r2 = np.where(ss_tot == 0, np.where(sd == 0, 1.0, 0.0), r2)
+    # (a NaN among the valid entries stays one: ss_tot == 0 and sd == 0 are both False for it)
+    r2 = np.where(np.isnan(ss_tot) | np.isnan(sd), np.nan, r2)
+    empty = n == 0
+    return np.where(empty, np.nan, r2), np.where(empty, np.nan, mse), np.where(empty, np.nan, ss_tot)
+
+
+def summarise_label_sums(sums, min_valid=10):
+    """Label scores from the sums ``bn_segment_label_sums`` returns, ``(S, L, 4)`` = per segment and label the count,
+    ``sum y``, ``sum y^2`` and ``sum (y - y_hat)^2`` of the valid entries, in numpy float64 on the host:
+
+    ``{'n', 'r2', 'mse'}``, each ``(S, L)`` -- what the reference's ``get_label_r2`` computes per trial and label with
+    ``sklearn.metrics.r2_score`` and ``np.mean(np.square(...))`` (cond_ae_utils.py:1257-1265), ``r2`` and ``mse`` NaN
+    where ``n <= min_valid`` as there (``len(y_true) > 10``) -- and ``'pooled'``, from the sums added over the segments
+    and regardless of ``min_valid``: ``{'n', 'r2', 'mse'}`` per label ``(L,)`` and the scalar
+    ``'r2_variance_weighted'``, sklearn's variance-weighted R^2 over the labels, ``1 - sum_j sd_j / sum_j ss_tot_j``
+    (labels with ``ss_tot == 0`` weigh nothing; all of them so: the plain mean) -- the quantity the training step logs
+    as ``label_r2`` (``models.vaes._r2_variance_weighted``)."""
+    sums = np.asarray(sums, dtype=np.float64)
+    if sums.ndim != 3 or sums.shape[2] != 4:
+        raise ValueError('summarise_label_sums: expected sums (S, L, 4), got %s' % (tuple(sums.shape),))
+    n = sums[..., 0]
+    r2, mse, _ = _scores_from_sums(n, sums[..., 1], sums[..., 2], sums[..., 3])
+    few = n <= min_valid
+    out = {'n': n.astype(np.int64), 'r2': np.where(few, np.nan, r2), 'mse': np.where(few, np.nan, mse)}
+    tot = sums.sum(axis=0)
+    p_r2, p_mse, p_ss = _scores_from_sums(tot[:, 0], tot[:, 1], tot[:, 2], tot[:, 3])
+    scored = tot[:, 0] > 0
+    if not scored.any():
+        weighted = np.nan
+    elif np.any(p_ss[scored] != 0):
+        weighted = float(np.average(p_r2[scored], weights=p_ss[scored]))
+    else:
+        weighted = float(np.mean(p_r2[scored]))
+    out['pooled'] = {'n': tot[:, 0].astype(np.int64), 'r2': p_r2, 'mse': p_mse, 'r2_variance_weighted': weighted}
+    return out
+
+
+def _splits(who, dtype):
+    dtypes = [dtype] if isinstance(dtype, str) else list(dtype)
+    if not dtypes or any(d not in ('train', 'val', 'test') for d in dtypes) or len(set(dtypes)) != len(dtypes):
+        raise ValueError("%s: dtype must be 'train', 'val' or 'test' or a list of them, got %r" % (who, dtype))
+    return dtypes
+
+
+def label_r2(data_generator, model, dtype='val', sess_idx=None):
+    """How well a model's supervised latents reconstruct each label, per trial and label: the numbers of the
+    reference's ``get_label_r2`` (plotting/cond_ae_utils.py:1234-1279) for a ``ps-vae``, ``msps-vae`` or
+    ``cond-ae-msp`` model (any other class: ValueError) over the trials of the split ``dtype`` -- or a list of splits;
+    the trials of other splits are not read -- of the sessions ``sess_idx`` (one index, a list, or None for all).
+
+    The trials are walked and encoded as ``export_latents`` walks and encodes them (the same per-trial encoder and
+    batch fields; ``hparams['hip_encode_dtype']`` is honoured; host-resident generators go through ``encode_trial``).
+    A trial's prediction is the first ``n_labels`` columns of its latents in the transformed space -- what the
+    reference's ``get_transformed_latents(images)`` returns: for ``ps-vae`` / ``msps-vae``
+    ``model.get_transformed_latents(latents, as_numpy=False)`` (the label map ``D`` on the supervised block), for
+    ``cond-ae-msp`` the encoded latents as they are, since the trial encoder has applied ``U`` already (as
+    ``export_latents`` does for that class) and a second ``U`` would score other numbers.  Predictions,
+    ``labels`` and ``labels_masks`` (where the batches have them) stay on the device in three tables with one offsets
+    vector, ONE ``bn_segment_label_sums`` launch reduces all trials, and ``(S, L, 4)`` doubles cross to the host.
+
+    -> ``summarise_label_sums``'s dict (``'n'``, ``'r2'``, ``'mse'`` as ``(S, L)``, ``'pooled'``) plus ``'session'`` and
+    ``'trial'``, int arrays ``(S,)`` in walk order, and ``'sums'`` ``(S, L, 4)``.  Under ``torch.distributed`` rank 0
+    walks every trial and the other ranks return None, as ``latent_ranges`` does."""
+    _check_label_r2_class('label_r2', model.hparams['model_class'])
+    dtypes = _splits('label_r2', dtype)
+    _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return None
+    wanted = _wanted_sessions('label_r2', data_generator, sess_idx)
+    n_labels = int(model.hparams['n_labels'])
+    device = next(model.parameters()).device
+    encode = _GraphedTrialEncoder(model)
+    # (the trial encoder returns U z for an AE-MSP, ``_encode_trial_device``: the transformed space already)
+    transformed = model.hparams['model_class'] == 'cond-ae-msp'
+    preds, truths, masks, sessions, trials = [], [], [], [], []
+
+    def on_device(images, sess, data, trial):
+        return (encode(images, sess, _batch_fields(model, data)[2]), data) if sess in wanted else None
+
+    def on_host(images, sess, data, trial):
+        if sess not in wanted:
+            return None
+        z = encode_trial(model, images, sess, _batch_fields(model, data)[2])
+        return torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(device), data
+
+    def table(value):
+        value = value[0]
+        return (value if torch.is_tensor(value) else torch.from_numpy(np.asarray(value))).to(device, torch.float32)
+
+    def sink(sess, trial, result):
+        if result is None:
+            return
+        z, data = result
+        if 'labels' not in data:
+            raise ValueError('label_r2: the generator serves no labels (session %d, trial %d)' % (sess, trial))
+        if transformed:
+            pred = z
+        else:
+            with torch.no_grad():
+                pred = model.get_transformed_latents(z, as_numpy=False)
+        truth = table(data['labels'])
+        if truth.dim() != 2 or truth.shape != (pred.shape[0], n_labels):
+            raise ValueError('label_r2: labels %s for %d frames and %d labels (session %d, trial %d)'
+                             % (tuple(truth.shape), pred.shape[0], n_labels, sess, trial))
+        preds.append(pred)
+        truths.append(truth)
+        masks.append(table(data['labels_masks']) if 'labels_masks' in data else None)
+        sessions.append(sess)
+        trials.append(trial)
+    _export_per_trial('label_r2', data_generator, model, on_device, on_host, sink=sink, dtypes=dtypes)
+    if not preds:
+        raise ValueError('label_r2: the sessions %s have no %s trial' % (sorted(wanted), ' or '.join(dtypes)))
+    offsets = np.concatenate(([0], np.cumsum([p.shape[0] for p in preds]))).astype(np.int64)
+    pred = torch.cat(preds, dim=0)
+    mask = None
+    if any(m is not None for m in masks):
+        mask = torch.cat([torch.ones_like(t) if m is None else m for m, t in zip(masks, truths)], dim=0)
+    sums = _hip.segment_label_sums(pred[:, :n_labels], torch.cat(truths, dim=0), mask, offsets).cpu().numpy()
+    out = summarise_label_sums(sums)
+    out.update({'session': np.asarray(sessions, dtype=np.int64), 'trial': np.asarray(trials, dtype=np.int64),
+                'sums': sums})
+    return out
+
+
+def export_label_r2(data_generator, model, label_names=None, dtype='val', filename=None):
+    """``label_r2`` as the table the reference's ``get_label_r2`` saves and its hyperparameter searches read:
+    ``r2_supervised.csv`` in the model's version directory (or ``filename``), one row per (trial, label) in walk order
+    with the reference's columns in its order -- ``Trial, Label, R2, MSE, Model``, the last one its literal string --
+    and one trailing column ``Session``, the session's index (the reference's table cannot tell two sessions' trials
+    apart).  ``label_names`` defaults to ``label_0, label_1, ...``; a NaN is an empty field, as pandas writes it.
+    Written with the ``csv`` module.  -> the path (None on the ranks other than 0)."""
+    import csv
+    scores = label_r2(data_generator, model, dtype=dtype)
+    if scores is None:
+        return None
+    n_labels = scores['r2'].shape[1]
+    if label_names is None:
+        label_names = ['label_%i' % i for i in range(n_labels)]
+    if len(label_names) != n_labels:
+        raise ValueError('export_label_r2: %d label names for %d labels' % (len(label_names), n_labels))
+    if filename is None:
+        filename = os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, 'r2_supervised.csv')
+
+    def field(v):
+        return '' if np.isnan(v) else repr(float(v))
+    with open(filename, 'w', newline='') as f:
+        writer = csv.writer(f, lineterminator='\n')
+        writer.writerow(['Trial', 'Label', 'R2', 'MSE', 'Model', 'Session'])
+        for k, (sess, trial) in enumerate(zip(scores['session'], scores['trial'])):
+            for i, name in enumerate(label_names):
+                writer.writerow([int(trial), name, field(scores['r2'][k, i]), field(scores['mse'][k, i]),
+                                 LABEL_R2_MODEL, int(sess)])
+    return filename

@@ -583,6 +583,10 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
          state_writer=None):
     if hparams.get('dp_shard') is not None:
         bdist.set_shard_mode(hparams['dp_shard'])
+    if method == 'ae' and hparams.get('export_label_r2', False):
+        # (asked of a class without supervised latents: an error now, not after the last epoch)
+        from behavenet_amd.fitting.eval import _check_label_r2_class
+        _check_label_r2_class("fit: hparams['export_label_r2']", model.hparams['model_class'])
     # hparams['shard_optimizer'] (BN_SHARD_OPTIMIZER=0/1): reduce-scatter -> Adam on this rank's 1/R
     # shard of the arena -> all-gather, instead of all-reduce + R identical steps
     # (fitting/distributed.py sharded_step, default_shard_optimizer: on for frame sharding over >= 4 ranks)
@@ -830,7 +834,7 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
         raise NotImplementedError('neural decoders are outside the MI355X hot path')
     # (the hparams key is the exporter's name in fitting.eval; 'export_latents' above is a required key)
     for key, what in (('export_frame_errors', 'frame errors'), ('export_reconstructions', 'reconstructions'),
-                      ('export_pixel_stats', 'pixel stats')):
+                      ('export_pixel_stats', 'pixel stats'), ('export_label_r2', 'label R^2 and MSE of the val trials')):
         if method == 'ae' and hparams.get(key, False):
             if is_main:
                 print('exporting %s' % what)

@@ -1,6 +1,7 @@
 """Latent and label traversals with the reference's signatures (``behavenet/plotting/cond_ae_utils.py``:
-``interpolate_1d``, ``interpolate_2d``), decoded in ONE batch, and the ranges they sweep (``get_input_range``,
-``compute_range``), selected on the device.
+``interpolate_1d``, ``interpolate_2d``), decoded in ONE batch, the ranges they sweep (``get_input_range``,
+``compute_range``), selected on the device, and the per-trial label scores of the models with supervised latents
+(``get_label_r2``), reduced on the device.
 
 The reference calls ``get_reconstruction`` once per point: P launch chains of one frame and P copies to the host.
 Here the points are collected into one table (``fitting.eval.traversal_points``) and ``get_reconstruction`` is called
@@ -18,7 +19,7 @@ from behavenet_amd.fitting import eval as _eval
 from behavenet_amd.fitting.eval import get_reconstruction, traversal_points
 from behavenet_amd.plotting import get_crop
 
-__all__ = ['interpolate_1d', 'interpolate_2d', 'get_input_range', 'compute_range']
+__all__ = ['interpolate_1d', 'interpolate_2d', 'get_input_range', 'compute_range', 'get_label_r2']
 
 _PLAIN = ('ae', 'vae', 'beta-tcvae', 'ps-vae', 'msps-vae')
 _COND = ('cond-ae', 'cond-vae')
@@ -237,3 +238,29 @@ def get_input_range(input_type, hparams, sess_ids=None, sess_idx=0, model=None, 
             masks = []
         inputs = [np.where(m == 0, np.float32(np.nan), i) for i, m in zip(inputs, masks)] if masks else inputs
     return compute_range(inputs, min_p=min_p, max_p=max_p)
+
+
+# ------------------------------------------------------------------------------------------ label scores
+def get_label_r2(hparams, model, data_generator, version, label_names, dtype='val', overwrite=False):
+    """R^2 and MSE of every label under the model's supervised latents, per trial of the split ``dtype``: the
+    reference's ``get_label_r2`` (cond_ae_utils.py:1234-1279) with its signature, its messages and its file,
+    ``r2_supervised.csv`` in ``hparams['expt_dir']/version_<version>`` -- read where it exists and ``overwrite`` is
+    false (neither the model nor the generator is touched then), computed and written otherwise
+    (``fitting.eval.export_label_r2``: the trials' predictions and labels stay on the device, one launch reduces them,
+    no sklearn call).  -> a pandas DataFrame with the columns ``Trial, Label, R2, MSE, Model`` and, after them,
+    ``Session``, one row per (trial, label).  pandas is imported here, not with the package."""
+    import pandas as pd
+    save_file = os.path.join(hparams['expt_dir'], 'version_%i' % version, 'r2_supervised.csv')
+    if not os.path.exists(save_file) or overwrite:
+        if not os.path.exists(save_file):
+            print('R^2 metrics do not exist; computing from scratch')
+        else:
+            print('overwriting metrics at %s' % save_file)
+        print('saving results to %s' % save_file)
+        if _eval.export_label_r2(data_generator, model, label_names=list(label_names), dtype=dtype,
+                                 filename=save_file) is None:
+            return None          # (torch.distributed: rank 0 alone computes and writes)
+    else:
+        print('loading results from %s' % save_file)
+    # (round_trip: the file holds the shortest decimals that name the float64 scores, and they are read back as those)
+    return pd.read_csv(save_file, float_precision='round_trip')

@@ -643,6 +643,34 @@ int bn_column_count(const float* x, int n, int d, int ld, long long* n_valid, vo
 int bn_column_select(const float* x, int n, int d, int ld, const long long* ranks, int r, float* out,
                      void* ws, size_t ws_bytes, bn_stream_t stream);
 
+/* Masked column sums per row segment, reduced on the device: the sums behind the per-trial, per-label R^2 and MSE of
+ * get_label_r2 (plotting/cond_ae_utils.py:1234-1279, an sklearn call per trial and label on the host).  pred, truth
+ * and mask are fp32 tables of n rows, row-major with leading dimensions ld_* >= L; only the first L columns are read
+ * (pred is in practice the (n, D) table of transformed latents, ld_pred = D > L) and none is ever written.  mask may
+ * be NULL: every entry is valid.  Otherwise entry (i, j) is valid where mask[i, j] == 1.0f exactly; any other value,
+ * NaN included, is not.
+ *
+ * offsets: DEVICE int64 (S + 1).  Made safe first: e[i] = the largest of offsets[0 .. i], each clamped into [0, n].
+ * Segment s is the rows [e[s], e[s+1]): a segment may be empty, an offset that steps back gives an empty segment, the
+ * segments never overlap, and rows outside [e[0], e[S]) are never read.
+ *
+ * out: DEVICE float64 (S, L, 4); for segment s and column j, over the valid entries of the segment's rows,
+ *   { count, sum y, sum y^2, sum (y - p)^2 }     with y = (double)truth[i, j], p = (double)pred[i, j]
+ * Every term is formed in float64 from the fp32 operands and summed in float64.  An invalid entry is selected out,
+ * not multiplied by zero: a NaN or Inf under a mask that is not one reaches no sum; a NaN under a one mask propagates.
+ * Every element of out is written (zeros for an empty segment).  Long segments are cut into row blocks whose partial
+ * sums are combined in block order, short ones are finished where they are read; no global atomics, and the order of
+ * every sum is fixed by (n, S, L) and the offsets: the same bits on every call.
+ * ws: bn_segment_label_sums_ws_bytes(n, S, L) bytes on a 16-byte boundary; nothing is read from it that the call has
+ * not written.
+ * BN_E_SHAPE (nothing written): L < 1 or L > 64, S < 0, n < 0 (the query returns 0 for these), a leading dimension
+ * below L, a workspace smaller than the query's, a table off a 4-byte, offsets or out off an 8-byte, ws off a 16-byte
+ * boundary.  BN_E_BADARG: pred, truth, offsets, out or ws NULL. */
+size_t bn_segment_label_sums_ws_bytes(int n, int S, int L);
+int bn_segment_label_sums(const float* pred, int ld_pred, const float* truth, int ld_truth, const float* mask,
+                          int ld_mask, const long long* offsets, int S, int L, int n, double* out, void* ws,
+                          size_t ws_bytes, bn_stream_t stream);
+
 /* unit-float frames -> stored uint8 grey levels, the inverse of bn_u8_to_unit_float on k / 255:
  *   out[i] = NaN -> 0, else clamp(rint(in[i] * 255), 0, 255)
  * The product is one fp32 multiplication and rint rounds half to even, i.e. numpy's
