@@ -154,6 +154,9 @@ SIGNATURES = {
     'bn_segment_label_sums_ws_bytes': (_c_size_t, [_c_int] * 3),
     'bn_segment_label_sums': (_c_int, [_c_void_p, _c_int] * 3 + [_c_void_p] + [_c_int] * 3
                               + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    'bn_segment_gram_ws_bytes': (_c_size_t, [_c_int] * 3),
+    'bn_segment_gram': (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p] + [_c_int] * 3
+                        + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
     'bn_prof_read': (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
@@ -1283,6 +1286,59 @@ def segment_label_sums(pred, truth, mask, offsets):
                                          None if mask is None else mask.data_ptr(), ld_mask, offsets.data_ptr(), S, L,
                                          n, out.data_ptr(), _arena(pred.device, nbytes, 'segment_sums'), nbytes,
                                          _stream()), 'bn_segment_label_sums')
+    return out
+
+
+# csrc/segment_gram.hip's partition, restated for the tests that have to name a row count by it (held against
+# bn_segment_gram_ws_bytes in tests/test_latent_corr_cpu.py): SG_MIN_ELEMS, SG_TARGET_GROUPS, SG_SLAB_BYTES, SG_MAX_D
+_SEGMENT_GRAM_MIN_ELEMS, _SEGMENT_GRAM_TARGET_GROUPS = 1 << 14, 1024
+_SEGMENT_GRAM_SLAB_BYTES, _SEGMENT_GRAM_MAX_D = 32 << 20, 64
+
+
+def _segment_gram_plan(n, D):
+    """``(blocks, rows)`` of ``bn_segment_gram`` on a table of n rows and D columns: the row blocks and the rows of a
+    block, the last block taking what is left (sg_plan); two partial matrices a block fit into 32 MiB."""
+    if n < 1:
+        return 0, 1
+    cap = min(_SEGMENT_GRAM_SLAB_BYTES // (2 * (D + 1) * (D + 1) * 8), _SEGMENT_GRAM_TARGET_GROUPS)
+    want = min(-(-n // (_SEGMENT_GRAM_MIN_ELEMS // D)), cap)
+    rows = -(-n // want)
+    return -(-n // rows), rows
+
+
+def segment_gram(table, offsets, shift=None):
+    """Per row segment the augmented second-moment matrix of the fp32 DEVICE ``table`` (n, D), D <= 64: a float64
+    device tensor ``(S, D + 1, D + 1)``, the sum over the segment's rows of ``a^T a`` with ``a = (1, z - shift)`` in
+    float64 -- ``[0, 0]`` the row count, ``[0, 1:]`` the column sums, ``[1:, 1:]`` the second moments -- on the current
+    stream (``bn_segment_gram``, csrc/segment_gram.hip).  ``offsets``: int64 (S + 1), a host array (uploaded) or a
+    device tensor; segment s is the rows ``[offsets[s], offsets[s + 1])``.  ``shift``: None (zeros) or D fp32 values
+    on the device.  The table may be a column slice of a wider one (row stride >= D, unit column stride).  The same
+    bits on every call."""
+    n, D, ld = _column_table('segment_gram', table)
+    if D > _SEGMENT_GRAM_MAX_D:
+        raise ValueError('segment_gram: %d columns (1 to %d are served)' % (D, _SEGMENT_GRAM_MAX_D))
+    if not torch.is_tensor(offsets):
+        offsets = torch.from_numpy(np.ascontiguousarray(np.asarray(offsets), dtype=np.int64)).to(table.device)
+    if offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.numel() < 1:
+        raise ValueError('segment_gram: expected offsets int64 (S + 1,), got %s %s'
+                         % (offsets.dtype, tuple(offsets.shape)))
+    if shift is not None and (not torch.is_tensor(shift) or shift.dtype != torch.float32 or shift.shape != (D,)):
+        raise ValueError('segment_gram: expected shift float32 (%d,), got %s'
+                         % (D, (shift.dtype, tuple(shift.shape)) if torch.is_tensor(shift) else type(shift).__name__))
+    for name, t in (('shift', shift), ('offsets', offsets)):
+        if t is not None and t.device != table.device:
+            raise ValueError('segment_gram: the table is on %s, %s on %s (the HIP path has no CPU fallback)'
+                             % (table.device, name, t.device))
+    offsets = offsets.contiguous()
+    shift = None if shift is None else shift.contiguous()
+    S = int(offsets.numel()) - 1
+    lib = load()
+    nbytes = lib.bn_segment_gram_ws_bytes(n, S, D)
+    out = torch.empty((S, D + 1, D + 1), dtype=torch.float64, device=table.device)
+    if S:
+        _check(lib.bn_segment_gram(table.data_ptr(), ld, None if shift is None else shift.data_ptr(),
+                                   offsets.data_ptr(), S, D, n, out.data_ptr(),
+                                   _arena(table.device, nbytes, 'segment_gram'), nbytes, _stream()), 'bn_segment_gram')
     return out
 
 

@@ -116,6 +116,14 @@ size_t bn_segment_label_sums_ws_bytes_impl(int n, int S, int L);
 int bn_launch_segment_label_sums(const float* pred, int ld_pred, const float* truth, int ld_truth, const float* mask,
                                  int ld_mask, const long long* offsets, int S, int L, int n, double* out, void* ws,
                                  hipStream_t st);
+int bn_launch_segment_offsets(const long long* offsets, int count, int n, int* e, hipStream_t st);
+
+// segment_gram.hip: per row segment the augmented second-moment matrix sum a^T a of a = (1, z - c) over the rows of
+// an fp32 table (n, D), float64 (S, D + 1, D + 1) -- the sums behind the latent correlation matrices
+bool bn_segment_gram_ok(int n, int S, int D);
+size_t bn_segment_gram_ws_bytes_impl(int n, int S, int D);
+int bn_launch_segment_gram(const float* z, int ld, const float* c, const long long* offsets, int S, int D, int n,
+                           double* out, void* ws, hipStream_t st);
 
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);

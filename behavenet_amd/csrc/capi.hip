@@ -2027,6 +2027,20 @@ extern "C" int bn_segment_label_sums(const float* pred, int ld_pred, const float
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// Augmented second-moment matrices per row segment (segment_gram.hip): the sums behind the latent correlations.
+extern "C" size_t bn_segment_gram_ws_bytes(int n, int S, int D) { return bn_segment_gram_ws_bytes_impl(n, S, D); }
+
+extern "C" int bn_segment_gram(const float* z, int ld, const float* c, const long long* offsets, int S, int D, int n,
+                               double* out, void* ws, size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_segment_gram_ok(n, S, D) || ld < D) return BN_E_SHAPE;
+    if (!z || !offsets || !out || !ws) return BN_E_BADARG;
+    if (((uintptr_t)z & 3) || ((uintptr_t)c & 3) || ((uintptr_t)offsets & 7) || ((uintptr_t)out & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_segment_gram_ws_bytes_impl(n, S, D)) return BN_E_SHAPE;
+    return bn_launch_segment_gram(z, ld, c, offsets, S, D, n, out, ws, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // fp32 unit-float frames -> stored uint8 grey levels (recon_u8.hip): NaN -> 0, else clamp(rint(x * 255), 0, 255).
 extern "C" int bn_unit_float_to_u8(const float* in, unsigned char* out, size_t n, bn_stream_t stream) {
     if (!in || !out) return BN_E_BADARG;

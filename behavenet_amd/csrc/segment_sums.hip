@@ -278,6 +278,13 @@ size_t bn_segment_label_sums_ws_bytes_impl(int n, int S, int L) {
     return sl_offsets_bytes(S) + (size_t)sl_plan(n, L).blocks * 2 * L * 4 * sizeof(double);
 }
 
+// e[i] = max_{k <= i} clamp(offsets[k], 0, n) for count offsets (segment_gram.hip makes its segments safe by it too)
+int bn_launch_segment_offsets(const long long* offsets, int count, int n, int* e, hipStream_t st) {
+    hipLaunchKernelGGL(k_sl_offsets, dim3(1), dim3(SL_SCAN_THREADS), 0, st, offsets, count, n, e);
+    BN_LAUNCH_CHECK();
+    return 0;
+}
+
 int bn_launch_segment_label_sums(const float* pred, int ld_pred, const float* truth, int ld_truth, const float* mask,
                                  int ld_mask, const long long* offsets, int S, int L, int n, double* out, void* ws,
                                  hipStream_t st) {
@@ -286,8 +293,8 @@ int bn_launch_segment_label_sums(const float* pred, int ld_pred, const float* tr
     const SlPlan p = sl_plan(n, L);
     int* e = reinterpret_cast<int*>(ws);
     double* slabs = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + sl_offsets_bytes(S));
-    hipLaunchKernelGGL(k_sl_offsets, dim3(1), dim3(SL_SCAN_THREADS), 0, st, offsets, S + 1, n, e);
-    BN_LAUNCH_CHECK();
+    const int rc = bn_launch_segment_offsets(offsets, S + 1, n, e, st);
+    if (rc) return rc;
     if (p.blocks) {
         hipLaunchKernelGGL(k_sl_stream, dim3((unsigned)p.blocks), dim3(SL_THREADS), 0, st, pred, ld_pred, truth,
                            ld_truth, mask, ld_mask, (const int*)e, S, L, n, p.rows, out, slabs);

@@ -2,8 +2,9 @@
 reconstruction errors -> ``*_frame_errors.pkl``, uint8 reconstructions -> ``*_reconstructions.npz`` and per-pixel
 error / moment maps -> ``*_pixel_stats.pkl``; latent traversals as uint8 mosaics and movies, decoded in one batch
 and tiled on the device; reconstruction movies (original, reconstruction, residual) as uint8 strips; the
-percentile ranges of latents and labels, selected on the device; and the per-trial label R^2 and MSE of the models
-with supervised latents -> ``r2_supervised.csv``, reduced on the device.
+percentile ranges of latents and labels, selected on the device; the per-trial label R^2 and MSE of the models
+with supervised latents -> ``r2_supervised.csv``, reduced on the device; and the correlation matrices of the latents
+per batch, trial or session -> ``corr_unsupervised.csv``, from second moments reduced on the device.
 
 Mirror of ``export_latents`` in the reference ``behavenet/fitting/eval.py:6-118``: same pickle
 schema ``{'latents': [per-trial (T x D) arrays, empty for gap trials], 'trials': batch_idxs}``
@@ -33,7 +34,8 @@ __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconst
            'summarise_pixel_stats', 'traversal_points', 'traverse_latents', 'traverse_latents_device',
            'traversal_movie', 'traversal_movie_device', 'reconstruction_movie', 'reconstruction_movie_device',
            'percentile_plan', 'percentile_lerp', 'column_percentiles', 'compute_range', 'latent_ranges',
-           'latent_ranges_device', 'summarise_label_sums', 'label_r2', 'export_label_r2']
+           'latent_ranges_device', 'summarise_label_sums', 'label_r2', 'export_label_r2', 'summarise_gram',
+           'latent_correlations', 'export_latent_correlations']
 
 
 def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -1436,3 +1438,224 @@ def export_label_r2(data_generator, model, label_names=None, dtype='val', filena
                 writer.writerow([int(trial), name, field(scores['r2'][k, i]), field(scores['mse'][k, i]),
                                  LABEL_R2_MODEL, int(sess)])
     return filename
+
+
+# ------------------------------------------------------------------------------------------ latent correlations
+LATENT_CORR_MAX_COLUMNS = 64
+
+
+def _moments_from_gram(A, shift):
+    """``{'n', 'mean', 'cov', 'corr', 'mean_abs_offdiag'}`` from augmented moment matrices ``(..., D + 1, D + 1)``."""
+    n = A[..., 0, 0]
+    s = A[..., 0, 1:]
+    G = A[..., 1:, 1:]
+    D = s.shape[-1]
+    nn = n[..., None]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mean = s / nn + (0.0 if shift is None else shift)
+        ss = G - s[..., :, None] * s[..., None, :] / nn[..., None]          # the centred sums of products
+        cov = ss / (nn[..., None] - 1.0)
+        gd = np.diagonal(G, axis1=-2, axis2=-1)
+        sd = np.diagonal(ss, axis1=-2, axis2=-1)
+        # a centred sum of squares within the rounding noise of the two sums it is the difference of: the column is
+        # constant as far as the sums can tell (the rule of _scores_from_sums)
+        flat = np.abs(sd) <= 8.0 * nn * 2.0 ** -53 * np.abs(gd)
+        var = np.where(flat | (nn < 2), np.nan, sd)
+        corr = ss / np.sqrt(var[..., :, None] * var[..., None, :])
+    few = np.broadcast_to((nn < 2)[..., None], cov.shape)
+    cov = np.where(few, np.nan, cov)
+    mean = np.where(np.broadcast_to(nn < 1, mean.shape), np.nan, mean)
+    corr = np.clip(corr, -1.0, 1.0)
+    if D > 1:
+        iu = np.triu_indices(D, 1)
+        offdiag = np.abs(corr[..., iu[0], iu[1]]).mean(axis=-1)
+    else:
+        offdiag = np.full(n.shape, np.nan)
+    return {'n': n.astype(np.int64), 'mean': mean, 'cov': cov, 'corr': corr, 'mean_abs_offdiag': offdiag}
+
+
+def summarise_gram(A, shift=None):
+    """Means, covariances and correlations from the matrices ``bn_segment_gram`` returns, ``(S, D + 1, D + 1)`` = per
+    segment the sum of ``a^T a`` with ``a = (1, z - shift)``, in numpy float64 on the host:
+
+    ``'n' (S,)``; ``'mean' (S, D)`` = ``shift + s / n``; ``'cov' (S, D, D)`` = ``(G - s s^T / n) / (n - 1)``, ``ddof = 1``
+    as ``np.cov``; ``'corr' (S, D, D)``, ``cov`` normalised by its diagonal and clipped to [-1, 1] as ``np.corrcoef``
+    does; ``'mean_abs_offdiag' (S,)``, the mean of ``|corr|`` over the pairs ``i < j`` (NaN for D = 1) -- the "average
+    over all pairs" the reference's docstring promises; and ``'pooled'``, the same keys without the segment axis from
+    the matrices added over the segments (all segments share the one shift, so their matrices add).
+
+    With ``n < 2``, or for a column whose centred sum of squares is within ``8 n 2^-53`` of its raw one -- rounding
+    noise of the sums: a column that is constant as far as they can tell --, the entries of ``corr`` that involve the
+    column are NaN (``np.corrcoef`` divides zero by zero there)."""
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim != 3 or A.shape[1] != A.shape[2] or A.shape[1] < 2:
+        raise ValueError('summarise_gram: expected matrices (S, D + 1, D + 1), got %s' % (tuple(A.shape),))
+    if shift is not None:
+        shift = np.asarray(shift, dtype=np.float64)
+        if shift.shape != (A.shape[1] - 1,):
+            raise ValueError('summarise_gram: %d columns, shift %s' % (A.shape[1] - 1, tuple(shift.shape)))
+    out = _moments_from_gram(A, shift)
+    out['pooled'] = _moments_from_gram(A.sum(axis=0), shift)
+    return out
+
+
+def _corr_columns(who, hparams, n_latents, columns):
+    """The columns ``latent_correlations`` reads -> ``(start, stop)`` for a contiguous ascending range (served without
+    a copy) or an int64 index array.  None: the unsupervised block of the model class."""
+    if columns is None:
+        model_class = hparams['model_class']
+        first = 0
+        if model_class in ('ps-vae', 'msps-vae'):
+            first = int(hparams['n_labels'])
+        if model_class == 'msps-vae':
+            first += int(hparams['n_background'])
+        columns = slice(first, n_latents)
+    if isinstance(columns, slice):
+        if columns.step not in (None, 1):
+            columns = np.arange(n_latents)[columns]
+        else:
+            start, stop, _ = columns.indices(n_latents)
+            columns = np.arange(start, stop)
+    idx = np.asarray(columns)
+    if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in 'iu':
+        raise ValueError('%s: columns must name at least one latent of %d by index, got %r' % (who, n_latents, columns))
+    idx = idx.astype(np.int64)
+    if idx.min() < 0 or idx.max() >= n_latents:
+        raise ValueError('%s: columns %s of a model with %d latents' % (who, idx.tolist(), n_latents))
+    if idx.size > LATENT_CORR_MAX_COLUMNS:
+        raise ValueError('%s: %d columns (1 to %d are served)' % (who, idx.size, LATENT_CORR_MAX_COLUMNS))
+    if np.array_equal(idx, np.arange(idx[0], idx[0] + idx.size)):
+        return int(idx[0]), int(idx[0]) + int(idx.size)
+    return idx
+
+
+def _corr_trial_order(batch_idxs, dtypes, wanted):
+    """``[(session, trial)]`` in the order the reference's ``np.vstack`` of ``load_latents(..., dtype)`` stacks the
+    rows: sessions ascending, and within a session the trials of each split in turn, in ``batch_idxs[dtype]`` order.
+    ``batch_idxs``: one dict a session."""
+    return [(s, int(t)) for s, idxs in enumerate(batch_idxs) if s in wanted for dt in dtypes for t in idxs[dt]]
+
+
+def _corr_segments(who, keys, lengths, segments):
+    """Offsets of the segments over the pooled table whose trials ``keys`` = ``[(session, trial)]`` hold ``lengths``
+    rows each -> ``(offsets int64 (S + 1,), session, trial)``; the last two are int64 ``(S,)`` arrays for ``'trial'``
+    (both) and ``'session'`` (the first) and None otherwise.  None: one segment over everything; an int ``b``:
+    consecutive batches of ``b`` rows, across trial and session boundaries, the last one ragged."""
+    ends = np.cumsum(np.asarray(lengths, dtype=np.int64))
+    total = int(ends[-1]) if len(ends) else 0
+    sessions = np.asarray([k[0] for k in keys], dtype=np.int64)
+    if segments is None:
+        return np.asarray([0, total], dtype=np.int64), None, None
+    if isinstance(segments, (int, np.integer)) and not isinstance(segments, bool):
+        if segments < 1:
+            raise ValueError('%s: batches of %d rows' % (who, segments))
+        b = int(segments)
+        return np.minimum(np.arange(-(-total // b) + 1, dtype=np.int64) * b, total), None, None
+    if isinstance(segments, str) and segments == 'trial':
+        return np.concatenate(([0], ends)).astype(np.int64), sessions, np.asarray([k[1] for k in keys], dtype=np.int64)
+    if isinstance(segments, str) and segments == 'session':
+        present = np.unique(sessions)
+        last = np.asarray([ends[np.nonzero(sessions == s)[0][-1]] for s in present], dtype=np.int64)
+        return np.concatenate(([0], last)).astype(np.int64), present.astype(np.int64), None
+    raise ValueError("%s: segments must be None, a batch size, 'trial' or 'session', got %r" % (who, segments))
+
+
+def latent_correlations(data_generator, model, dtype='train', sess_idx=None, segments=None, columns=None):
+    """Mean, covariance and correlation matrix of a model's latents per batch, trial or session or over all time
+    points: the third number the reference's PS-VAE and MSPS-VAE hyperparameter searches read next to pixel MSE and
+    label R^2 (plotting/cond_ae_utils.py:1679-1700, 2802-2835: the latents pickles of every session stacked on the
+    host and ``np.corrcoef`` once per ``batch_size`` rows).
+
+    The trials of the split ``dtype`` (or a list of splits) of the sessions ``sess_idx`` (one index, a list, or None
+    for all) are walked and encoded as ``export_latents`` walks and encodes them (``hparams['hip_encode_dtype']`` is
+    honoured; host-resident generators go through ``encode_trial``) and put into ONE device table in the order of the
+    reference's stack: sessions ascending, within a session the trials in ``batch_idxs[dtype]`` order, split after
+    split.  ``segments``: None (one segment over everything, the reference's ``batch_size=None``), an int ``b``
+    (consecutive batches of ``b`` rows of that table, across trial and session boundaries as the reference's, the last
+    one ragged), ``'trial'`` or ``'session'``.  ``columns``: a slice or a list of latent indices, 64 at most; by
+    default the unsupervised block (from ``n_labels`` on for ``ps-vae``, from ``n_labels + n_background`` on for
+    ``msps-vae``, every latent otherwise).  A contiguous range is read in place, any other list is gathered once on the
+    device.  The shift is the first row of the selected table, taken on the device.  ONE ``bn_segment_gram`` launch
+    reduces all segments; ``(S, D + 1, D + 1)`` doubles and the D shift values cross to the host.
+
+    -> ``summarise_gram``'s dict plus ``'gram'``, ``'shift'``, ``'rows' (S, 2)`` (begin and end row of each segment),
+    ``'abs_corr_01' (S,)`` = ``|corr[0, 1]|``, the number the reference plots (NaN for fewer than two columns), and for
+    ``'trial'`` / ``'session'`` segments the int arrays ``'session'`` (and ``'trial'``).  Under ``torch.distributed``
+    rank 0 walks every trial and the other ranks return None, as ``label_r2`` does."""
+    who = 'latent_correlations'
+    dtypes = _splits(who, dtype)
+    cols = _corr_columns(who, model.hparams, int(model.hparams['n_ae_latents']), columns)
+    _corr_segments(who, [], [], segments)          # (a bad value: an error before the walk)
+    _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return None
+    wanted = _wanted_sessions(who, data_generator, sess_idx)
+    device = next(model.parameters()).device
+    encode = _GraphedTrialEncoder(model)
+    parts = {}
+
+    def on_device(images, sess, data, trial):
+        return encode(images, sess, _batch_fields(model, data)[2]) if sess in wanted else None
+
+    def on_host(images, sess, data, trial):
+        if sess not in wanted:
+            return None
+        z = encode_trial(model, images, sess, _batch_fields(model, data)[2])
+        return torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(device)
+
+    def sink(sess, trial, result):
+        if result is not None and len(result):
+            parts[(sess, int(trial))] = result
+    _export_per_trial(who, data_generator, model, on_device, on_host, sink=sink, dtypes=dtypes)
+    # (the generator serves the trials in its own order: the table is put together in the reference's)
+    keys = [k for k in _corr_trial_order([ds.batch_idxs for ds in data_generator.datasets], dtypes, wanted)
+            if k in parts]
+    if not keys:
+        raise ValueError('%s: the sessions %s have no %s trial' % (who, sorted(wanted), ' or '.join(dtypes)))
+    table = torch.cat([parts[k] for k in keys], dim=0).to(torch.float32)
+    offsets, sessions, trials = _corr_segments(who, keys, [parts[k].shape[0] for k in keys], segments)
+    if isinstance(cols, tuple):
+        selected = table[:, cols[0]:cols[1]]
+    else:
+        selected = table[:, torch.from_numpy(cols).to(device)]
+    shift = selected[0].contiguous()
+    gram = _hip.segment_gram(selected, offsets, shift)
+    host = torch.cat([gram.reshape(-1), shift.to(torch.float64)]).cpu().numpy()          # one transfer
+    D = selected.shape[1]
+    gram, shift = host[:host.size - D].reshape(len(offsets) - 1, D + 1, D + 1), host[host.size - D:]
+    out = summarise_gram(gram, shift)
+    out.update({'gram': gram, 'shift': shift, 'rows': np.stack([offsets[:-1], offsets[1:]], axis=1),
+                'abs_corr_01': np.abs(out['corr'][:, 0, 1]) if D > 1 else np.full(len(offsets) - 1, np.nan)})
+    if sessions is not None:
+        out['session'] = sessions
+    if trials is not None:
+        out['trial'] = trials
+    return out
+
+
+def _write_latent_corr_csv(filename, scores):
+    import csv
+
+    def field(v):
+        return '' if np.isnan(v) else repr(float(v))
+    with open(filename, 'w', newline='') as f:
+        writer = csv.writer(f, lineterminator='\n')
+        writer.writerow(['Segment', 'RowBegin', 'RowEnd', 'N', 'AbsCorr01', 'MeanAbsCorr'])
+        for k, (begin, end) in enumerate(scores['rows']):
+            writer.writerow([k, int(begin), int(end), int(scores['n'][k]), field(scores['abs_corr_01'][k]),
+                             field(scores['mean_abs_offdiag'][k])])
+    return filename
+
+
+def export_latent_correlations(data_generator, model, dtype='train', segments=None, columns=None, filename=None):
+    """``latent_correlations`` as a table: ``corr_unsupervised.csv`` in the model's version directory (or
+    ``filename``), one row per segment with the columns ``Segment, RowBegin, RowEnd, N, AbsCorr01, MeanAbsCorr`` --
+    ``AbsCorr01`` the reference's ``|corr[0, 1]|`` of the first two selected columns, ``MeanAbsCorr`` the mean of
+    ``|corr|`` over all pairs.  Written with the ``csv`` module, ``repr(float)`` fields, a NaN an empty field.
+    -> the path (None on the ranks other than 0)."""
+    scores = latent_correlations(data_generator, model, dtype=dtype, segments=segments, columns=columns)
+    if scores is None:
+        return None
+    if filename is None:
+        filename = os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, 'corr_unsupervised.csv')
+    return _write_latent_corr_csv(filename, scores)

@@ -587,6 +587,10 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
         # (asked of a class without supervised latents: an error now, not after the last epoch)
         from behavenet_amd.fitting.eval import _check_label_r2_class
         _check_label_r2_class("fit: hparams['export_label_r2']", model.hparams['model_class'])
+    if method == 'ae' and hparams.get('export_latent_corr', False):
+        # (any class has latents to correlate; a bad batch size is an error now, not after the last epoch)
+        from behavenet_amd.fitting.eval import _corr_segments
+        _corr_segments("fit: hparams['latent_corr_batch_size']", [], [], hparams.get('latent_corr_batch_size'))
     # hparams['shard_optimizer'] (BN_SHARD_OPTIMIZER=0/1): reduce-scatter -> Adam on this rank's 1/R
     # shard of the arena -> all-gather, instead of all-reduce + R identical steps
     # (fitting/distributed.py sharded_step, default_shard_optimizer: on for frame sharding over >= 4 ranks)
@@ -840,6 +844,12 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
                 print('exporting %s' % what)
             from behavenet_amd.fitting import eval as bn_eval
             getattr(bn_eval, key)(data_generator, best_val_model)
+    if method == 'ae' and hparams.get('export_latent_corr', False):
+        if is_main:
+            print('exporting latent correlations of the train trials')
+        from behavenet_amd.fitting.eval import export_latent_correlations
+        export_latent_correlations(data_generator, best_val_model, dtype='train',
+                                   segments=hparams.get('latent_corr_batch_size'))
     if resume and is_main:
         if state_writer is not None:
             state_writer.wait()

@@ -1,7 +1,7 @@
 """Latent and label traversals with the reference's signatures (``behavenet/plotting/cond_ae_utils.py``:
 ``interpolate_1d``, ``interpolate_2d``), decoded in ONE batch, the ranges they sweep (``get_input_range``,
-``compute_range``), selected on the device, and the per-trial label scores of the models with supervised latents
-(``get_label_r2``), reduced on the device.
+``compute_range``), selected on the device, the per-trial label scores of the models with supervised latents
+(``get_label_r2``) and the correlations of the unsupervised latents (``get_latent_corr``), reduced on the device.
 
 The reference calls ``get_reconstruction`` once per point: P launch chains of one frame and P copies to the host.
 Here the points are collected into one table (``fitting.eval.traversal_points``) and ``get_reconstruction`` is called
@@ -19,7 +19,7 @@ from behavenet_amd.fitting import eval as _eval
 from behavenet_amd.fitting.eval import get_reconstruction, traversal_points
 from behavenet_amd.plotting import get_crop
 
-__all__ = ['interpolate_1d', 'interpolate_2d', 'get_input_range', 'compute_range', 'get_label_r2']
+__all__ = ['interpolate_1d', 'interpolate_2d', 'get_input_range', 'compute_range', 'get_label_r2', 'get_latent_corr']
 
 _PLAIN = ('ae', 'vae', 'beta-tcvae', 'ps-vae', 'msps-vae')
 _COND = ('cond-ae', 'cond-vae')
@@ -263,4 +263,31 @@ def get_label_r2(hparams, model, data_generator, version, label_names, dtype='va
     else:
         print('loading results from %s' % save_file)
     # (round_trip: the file holds the shortest decimals that name the float64 scores, and they are read back as those)
+    return pd.read_csv(save_file, float_precision='round_trip')
+
+
+# ------------------------------------------------------------------------------------------ latent correlations
+def get_latent_corr(hparams, model, data_generator, version, batch_size=None, dtype='train', overwrite=False):
+    """The correlation of the model's unsupervised latents per batch of ``batch_size`` rows, or across all time
+    points (``batch_size=None``), over the trials of the split ``dtype``: the third number of the reference's PS-VAE
+    and MSPS-VAE hyperparameter searches (cond_ae_utils.py:1679-1700, 2802-2835), saved and loaded as ``get_label_r2``
+    saves and loads its table.  ``corr_unsupervised.csv`` in ``hparams['expt_dir']/version_<version>`` is read where
+    it exists and ``overwrite`` is false (neither the model nor the generator is touched then), computed and written
+    otherwise (``fitting.eval.export_latent_correlations``: the latents stay on the device, one launch reduces them).
+    -> a pandas DataFrame with the columns ``Segment, RowBegin, RowEnd, N, AbsCorr01, MeanAbsCorr``, one row per
+    batch.  pandas is imported here, not with the package."""
+    import pandas as pd
+    save_file = os.path.join(hparams['expt_dir'], 'version_%i' % version, 'corr_unsupervised.csv')
+    if not os.path.exists(save_file) or overwrite:
+        if not os.path.exists(save_file):
+            print('latent correlations do not exist; computing from scratch')
+        else:
+            print('overwriting metrics at %s' % save_file)
+        print('saving results to %s' % save_file)
+        if _eval.export_latent_correlations(data_generator, model, dtype=dtype, segments=batch_size,
+                                            filename=save_file) is None:
+            return None          # (torch.distributed: rank 0 alone computes and writes)
+    else:
+        print('loading results from %s' % save_file)
+    # (round_trip: the file holds the shortest decimals that name the float64 values, and they are read back as those)
     return pd.read_csv(save_file, float_precision='round_trip')

@@ -671,6 +671,37 @@ int bn_segment_label_sums(const float* pred, int ld_pred, const float* truth, in
                           int ld_mask, const long long* offsets, int S, int L, int n, double* out, void* ws,
                           size_t ws_bytes, bn_stream_t stream);
 
+/* Augmented second-moment matrices per row segment, reduced on the device: the sums behind the correlation of the
+ * unsupervised latents "per batch or across all time points" that the PS-VAE and MSPS-VAE hyperparameter searches
+ * plot (plotting/cond_ae_utils.py:1679-1700, 2802-2835: np.vstack + np.corrcoef per batch on the host).
+ * z: fp32 table of n rows and D columns, 1 <= D <= 64, row-major with leading dimension ld >= D, on any 4-byte
+ * boundary (a column slice of a wider table is served as it is; the columns from D on are never read).  c: D fp32
+ * values, the shift, or NULL for zeros.  Neither is ever written.
+ *
+ * offsets: DEVICE int64 (S + 1), made safe as bn_segment_label_sums makes them: e[i] = the largest of
+ * offsets[0 .. i], each clamped into [0, n]; segment s is the rows [e[s], e[s+1]) and rows outside [e[0], e[S]) are
+ * never read.
+ *
+ * out: DEVICE float64 (S, D + 1, D + 1); for segment s, with a = (1, (double)z_0 - (double)c_0, ...,
+ * (double)z_{D-1} - (double)c_{D-1}) per row,
+ *   out[s] = sum over the segment's rows of a^T a
+ * i.e. out[s][0][0] the row count (an exact integer), out[s][0][1 + j] = out[s][1 + j][0] = sum a_j and
+ * out[s][1 + i][1 + j] = sum a_i a_j.  Both triangles are written, with the same bits in [i][j] and [j][i].  Every term
+ * is formed in float64 from the fp32 operands and summed in float64 (covariance is shift-invariant: a shift near the
+ * data keeps the raw moments from losing digits where |mean| >> std).  A NaN or Inf in column j of a segment reaches
+ * row and column 1 + j of that segment's matrix and nothing else.  Every element of out is written exactly once
+ * (zeros for an empty segment).  Long segments are cut into row blocks whose partial matrices are combined in block
+ * order, short ones are finished where they are read; no global atomics, and the order of every sum is fixed by
+ * (n, S, D) and the offsets: the same bits on every call.
+ * ws: bn_segment_gram_ws_bytes(n, S, D) bytes (32 MiB of partials at most) on a 16-byte boundary; nothing is read from
+ * it that the call has not written.  S == 0 returns 0 and writes nothing.
+ * BN_E_SHAPE (nothing written, to out or to ws): D < 1 or D > 64, S < 0, n < 0 (the query returns 0 for these),
+ * ld < D, a workspace smaller than the query's, z or c off a 4-byte, offsets or out off an 8-byte, ws off a 16-byte
+ * boundary.  BN_E_BADARG: z, offsets, out or ws NULL. */
+size_t bn_segment_gram_ws_bytes(int n, int S, int D);
+int bn_segment_gram(const float* z, int ld, const float* c, const long long* offsets, int S, int D, int n,
+                    double* out, void* ws, size_t ws_bytes, bn_stream_t stream);
+
 /* unit-float frames -> stored uint8 grey levels, the inverse of bn_u8_to_unit_float on k / 255:
  *   out[i] = NaN -> 0, else clamp(rint(in[i] * 255), 0, 255)
  * The product is one fp32 multiplication and rint rounds half to even, i.e. numpy's
