@@ -157,6 +157,12 @@ SIGNATURES = {
     'bn_segment_gram_ws_bytes': (_c_size_t, [_c_int] * 3),
     'bn_segment_gram': (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p] + [_c_int] * 3
                         + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    'bn_softmax_cv_lossgrad_ws_bytes': (_c_size_t, [_c_int] * 4),
+    'bn_softmax_cv_lossgrad': (_c_int, [_c_void_p, _c_int] + [_c_void_p] * 4 + [_c_int] * 4
+                               + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
+    'bn_softmax_cv_score_ws_bytes': (_c_size_t, [_c_int] * 4),
+    'bn_softmax_cv_score': (_c_int, [_c_void_p, _c_int] + [_c_void_p] * 4 + [_c_int] * 4
+                            + [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
     'bn_prof_read': (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
@@ -1339,6 +1345,111 @@ def segment_gram(table, offsets, shift=None):
         _check(lib.bn_segment_gram(table.data_ptr(), ld, None if shift is None else shift.data_ptr(),
                                    offsets.data_ptr(), S, D, n, out.data_ptr(),
                                    _arena(table.device, nbytes, 'segment_gram'), nbytes, _stream()), 'bn_segment_gram')
+    return out
+
+
+# csrc/softmax_cv.hip's limits and partition, restated for the callers that check before a launch and for the tests
+# that have to name a row count by the plan (held against the workspace queries in tests/test_classifier_cpu.py):
+# SC_MAX_D, SC_MAX_S, SC_MAX_M, SC_GC, SC_MIN_ROWS, SC_TARGET_BLOCKS, SC_SLAB_BYTES, SC_ROWS
+SOFTMAX_CV_MAX_D, SOFTMAX_CV_MAX_S, SOFTMAX_CV_MAX_M = 64, 8, 64
+_SOFTMAX_CV_GROUP_COLUMNS, _SOFTMAX_CV_MIN_ROWS, _SOFTMAX_CV_TARGET_BLOCKS = 128, 128, 1024
+_SOFTMAX_CV_SLAB_BYTES, SOFTMAX_CV_CHUNK_ROWS = 32 << 20, 32
+
+
+def _softmax_cv_plan(n, D, S, M, score=False):
+    """``(blocks, rows, models_per_group)`` of ``bn_softmax_cv_lossgrad`` (or ``_score``): the row blocks, the rows
+    of a block (the last block takes what is left) and the models a workgroup serves (sc_plan)."""
+    mg = min(_SOFTMAX_CV_GROUP_COLUMNS // S, M)
+    if n < 1:
+        return 0, 1, mg
+    pm = 2 if score else S * (D + 1) + 2
+    cap = min(_SOFTMAX_CV_SLAB_BYTES // (M * pm * 8), _SOFTMAX_CV_TARGET_BLOCKS)
+    want = min(-(-n // _SOFTMAX_CV_MIN_ROWS), cap)
+    rows = -(-n // want)
+    return -(-n // rows), rows, mg
+
+
+def _softmax_cv_operands(who, z, y, fold, W, leave):
+    if not torch.is_tensor(z) or z.dim() != 2:
+        raise TypeError('%s: expected a device table (n, D), got %s'
+                        % (who, tuple(z.shape) if torch.is_tensor(z) else type(z).__name__))
+    if z.dtype != torch.float32:
+        raise TypeError('%s: the table must be float32, got %s' % (who, z.dtype))
+    if not z.is_cuda:
+        raise ValueError('%s: expected the table on the GPU, got device %s (the HIP path has no CPU fallback)'
+                         % (who, z.device))
+    n, D = (int(v) for v in z.shape)
+    if not 1 <= D <= SOFTMAX_CV_MAX_D:
+        raise ValueError('%s: %d columns (1 to %d are served)' % (who, D, SOFTMAX_CV_MAX_D))
+    ld = D if n <= 1 else int(z.stride(0))
+    if (D > 1 and n > 0 and z.stride(1) != 1) or ld < D:
+        raise ValueError('%s: the table\'s rows must be contiguous, got strides %s' % (who, tuple(z.stride())))
+    if not torch.is_tensor(W) or W.dim() != 3:
+        raise TypeError('%s: expected weights (M, S, D + 1), got %s'
+                        % (who, tuple(W.shape) if torch.is_tensor(W) else type(W).__name__))
+    if W.dtype != torch.float64:
+        raise TypeError('%s: the weights must be float64, got %s' % (who, W.dtype))
+    M, S = int(W.shape[0]), int(W.shape[1])
+    if W.shape[2] != D + 1:
+        raise ValueError('%s: weights %s for %d columns and an intercept' % (who, tuple(W.shape), D))
+    if not 2 <= S <= SOFTMAX_CV_MAX_S or not 1 <= M <= SOFTMAX_CV_MAX_M:
+        raise ValueError('%s: %d classes and %d models (2 to %d classes and 1 to %d models are served)'
+                         % (who, S, M, SOFTMAX_CV_MAX_S, SOFTMAX_CV_MAX_M))
+    for name, t, length in (('y', y, n), ('fold', fold, n), ('leave', leave, M)):
+        if t is None and name == 'fold':
+            continue
+        if not torch.is_tensor(t):
+            raise TypeError('%s: expected %s as a device tensor, got %s' % (who, name, type(t).__name__))
+        if t.dtype != torch.int32:
+            raise TypeError('%s: %s must be int32, got %s' % (who, name, t.dtype))
+        if t.shape != (length,):
+            raise ValueError('%s: expected %s (%d,), got %s' % (who, name, length, tuple(t.shape)))
+    for name, t in (('y', y), ('fold', fold), ('W', W), ('leave', leave)):
+        if t is not None and t.device != z.device:
+            raise ValueError('%s: the table is on %s, %s on %s (the HIP path has no CPU fallback)'
+                             % (who, z.device, name, t.device))
+    return (n, D, S, M, ld, y.contiguous(), None if fold is None else fold.contiguous(), W.contiguous(),
+            leave.contiguous())
+
+
+def softmax_cv_lossgrad(z, y, fold, W, leave, packed=False):
+    """Loss, gradient and row count of M multinomial logistic models at once over the fp32 DEVICE table ``z`` (n, D),
+    D <= 64 (``bn_softmax_cv_lossgrad``, csrc/softmax_cv.hip): ``y`` int32 (n) the class of a row, ``fold`` int32 (n)
+    its fold or None, ``W`` float64 (M, S, D + 1) with the intercept in column D, ``leave`` int32 (M) the fold a model
+    leaves out (-1: none), all on the device -> float64 device tensors ``(loss (M,), grad (M, S, D + 1), count (M,))``
+    = the sums of ``logsumexp(l) - l_y`` and ``(softmax(l) - onehot(y)) (x) (z, 1)`` over the rows a model includes,
+    on the current stream.  The table may be a column slice of a wider one.  The same bits on every call.
+    ``packed=True`` returns the ONE buffer the three are views of instead, ``M (S (D + 1) + 2)`` doubles: the losses,
+    the counts, then the gradients -- what a caller sends to the host in one transfer."""
+    n, D, S, M, ld, y, fold, W, leave = _softmax_cv_operands('softmax_cv_lossgrad', z, y, fold, W, leave)
+    lib = load()
+    nbytes = lib.bn_softmax_cv_lossgrad_ws_bytes(n, D, S, M)
+    out = torch.empty(M * (S * (D + 1) + 2), dtype=torch.float64, device=z.device)
+    loss, count, grad = out[:M], out[M:2 * M], out[2 * M:].view(M, S, D + 1)
+    if n == 0:          # (an empty table has no address to hand over: the sums over no rows)
+        out.zero_()
+        return out if packed else (loss, grad, count)
+    _check(lib.bn_softmax_cv_lossgrad(z.data_ptr(), ld, y.data_ptr(), None if fold is None else fold.data_ptr(),
+                                      W.data_ptr(), leave.data_ptr(), n, D, S, M, loss.data_ptr(), grad.data_ptr(),
+                                      count.data_ptr(), _arena(z.device, nbytes, 'softmax_cv'), nbytes, _stream()),
+           'bn_softmax_cv_lossgrad')
+    return out if packed else (loss, grad, count)
+
+
+def softmax_cv_score(z, y, fold, W, leave):
+    """``(hits, rows)`` per model, a float64 device tensor (M, 2) of exact integers: over the rows of model m's held-out
+    fold -- ``fold == leave[m]``, every row for ``leave[m] == -1`` -- with ``y`` in [0, S) the rows whose float64
+    argmax logit is ``y`` (ties to the lowest class) and the rows (``bn_softmax_cv_score``).  Operands as
+    ``softmax_cv_lossgrad``'s."""
+    n, D, S, M, ld, y, fold, W, leave = _softmax_cv_operands('softmax_cv_score', z, y, fold, W, leave)
+    lib = load()
+    nbytes = lib.bn_softmax_cv_score_ws_bytes(n, D, S, M)
+    out = torch.empty((M, 2), dtype=torch.float64, device=z.device)
+    if n == 0:
+        return out.zero_()
+    _check(lib.bn_softmax_cv_score(z.data_ptr(), ld, y.data_ptr(), None if fold is None else fold.data_ptr(),
+                                   W.data_ptr(), leave.data_ptr(), n, D, S, M, out.data_ptr(),
+                                   _arena(z.device, nbytes, 'softmax_cv'), nbytes, _stream()), 'bn_softmax_cv_score')
     return out
 
 

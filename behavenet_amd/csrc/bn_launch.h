@@ -125,6 +125,16 @@ size_t bn_segment_gram_ws_bytes_impl(int n, int S, int D);
 int bn_launch_segment_gram(const float* z, int ld, const float* c, const long long* offsets, int S, int D, int n,
                            double* out, void* ws, hipStream_t st);
 
+// softmax_cv.hip: loss, gradient and held-out score of M multinomial logistic models (S classes, D columns and an
+// intercept each) over the rows of an fp32 table, float64 throughout -- the sums behind the session classifier
+bool bn_softmax_cv_ok(int n, int D, int S, int M);
+size_t bn_softmax_cv_ws_bytes_impl(int n, int D, int S, int M, bool score);
+int bn_launch_softmax_cv_lossgrad(const float* z, int ld, const int* y, const int* fold, const double* W,
+                                  const int* leave, int n, int D, int S, int M, double* loss, double* grad,
+                                  double* count, void* ws, hipStream_t st);
+int bn_launch_softmax_cv_score(const float* z, int ld, const int* y, const int* fold, const double* W,
+                               const int* leave, int n, int D, int S, int M, double* out, void* ws, hipStream_t st);
+
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);
 int bn_launch_bn_stats(const float* x, float* mean, float* var, int N, int C, int HW, void* ws,

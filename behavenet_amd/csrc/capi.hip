@@ -2041,6 +2041,48 @@ extern "C" int bn_segment_gram(const float* z, int ld, const float* c, const lon
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// M multinomial logistic models at once over a table of latents (softmax_cv.hip): the session classifier's sums.
+extern "C" size_t bn_softmax_cv_lossgrad_ws_bytes(int n, int D, int S, int M) {
+    return bn_softmax_cv_ws_bytes_impl(n, D, S, M, false);
+}
+
+extern "C" size_t bn_softmax_cv_score_ws_bytes(int n, int D, int S, int M) {
+    return bn_softmax_cv_ws_bytes_impl(n, D, S, M, true);
+}
+
+static int softmax_cv_args(const float* z, int ld, const int* y, const int* fold, const double* W, const int* leave,
+                           int n, int D, int S, int M, const void* ws, size_t ws_bytes, bool score) {
+    if (!bn_softmax_cv_ok(n, D, S, M) || ld < D) return BN_E_SHAPE;
+    if (!z || !y || !W || !leave || !ws) return BN_E_BADARG;
+    if (((uintptr_t)z & 3) || ((uintptr_t)y & 3) || ((uintptr_t)fold & 3) || ((uintptr_t)leave & 3) ||
+        ((uintptr_t)W & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_softmax_cv_ws_bytes_impl(n, D, S, M, score)) return BN_E_SHAPE;
+    return 0;
+}
+
+extern "C" int bn_softmax_cv_lossgrad(const float* z, int ld, const int* y, const int* fold, const double* W,
+                                      const int* leave, int n, int D, int S, int M, double* loss, double* grad,
+                                      double* count, void* ws, size_t ws_bytes, bn_stream_t stream) {
+    const int rc = softmax_cv_args(z, ld, y, fold, W, leave, n, D, S, M, ws, ws_bytes, false);
+    if (rc) return rc;
+    if (!loss || !grad || !count) return BN_E_BADARG;
+    if (((uintptr_t)loss & 7) || ((uintptr_t)grad & 7) || ((uintptr_t)count & 7)) return BN_E_SHAPE;
+    return bn_launch_softmax_cv_lossgrad(z, ld, y, fold, W, leave, n, D, S, M, loss, grad, count, ws,
+                                         (hipStream_t)stream);
+}
+
+extern "C" int bn_softmax_cv_score(const float* z, int ld, const int* y, const int* fold, const double* W,
+                                   const int* leave, int n, int D, int S, int M, double* out, void* ws,
+                                   size_t ws_bytes, bn_stream_t stream) {
+    const int rc = softmax_cv_args(z, ld, y, fold, W, leave, n, D, S, M, ws, ws_bytes, true);
+    if (rc) return rc;
+    if (!out) return BN_E_BADARG;
+    if ((uintptr_t)out & 7) return BN_E_SHAPE;
+    return bn_launch_softmax_cv_score(z, ld, y, fold, W, leave, n, D, S, M, out, ws, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // fp32 unit-float frames -> stored uint8 grey levels (recon_u8.hip): NaN -> 0, else clamp(rint(x * 255), 0, 255).
 extern "C" int bn_unit_float_to_u8(const float* in, unsigned char* out, size_t n, bn_stream_t stream) {
     if (!in || !out) return BN_E_BADARG;

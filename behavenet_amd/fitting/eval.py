@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from behavenet_amd import _hip
+from behavenet_amd.fitting import classifier as _clf
 from behavenet_amd.fitting import distributed as bdist
 from behavenet_amd.data.utils import label_maps_of
 from behavenet_amd.hip_functions import (DECODE_DTYPES, ENCODE_DTYPES, FrameErrRequest, FrameU8Request,
@@ -35,7 +36,8 @@ __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconst
            'traversal_movie', 'traversal_movie_device', 'reconstruction_movie', 'reconstruction_movie_device',
            'percentile_plan', 'percentile_lerp', 'column_percentiles', 'compute_range', 'latent_ranges',
            'latent_ranges_device', 'summarise_label_sums', 'label_r2', 'export_label_r2', 'summarise_gram',
-           'latent_correlations', 'export_latent_correlations']
+           'latent_correlations', 'export_latent_correlations', 'session_classifier', 'export_session_classifier',
+           'classify_table', 'score_table']
 
 
 def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -1659,3 +1661,139 @@ def export_latent_correlations(data_generator, model, dtype='train', segments=No
     if filename is None:
         filename = os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, 'corr_unsupervised.csv')
     return _write_latent_corr_csv(filename, scores)
+
+
+# ------------------------------------------------------------------------------------------ session classifier
+SESSION_CLASSIFIER_FILE = 'fc_session_classification.npy'
+
+
+def _check_session_classifier(who, data_generator, sess_idx=None):
+    """The sessions to tell apart, ascending; fewer than two, or more than the kernel's eight: ValueError."""
+    wanted = sorted(_wanted_sessions(who, data_generator, sess_idx))
+    if len(wanted) < 2:
+        raise ValueError('%s: %d session (a session classifier needs at least two)' % (who, len(wanted)))
+    if len(wanted) > _hip.SOFTMAX_CV_MAX_S:
+        raise ValueError('%s: %d sessions (2 to %d are served)' % (who, len(wanted), _hip.SOFTMAX_CV_MAX_S))
+    return wanted
+
+
+def session_classifier(data_generator, model, dtype='val', columns=None, Cs=_clf.DEFAULT_CS, n_splits=5, tol=1e-4,
+                       max_iter=100, sess_idx=None):
+    """``fc``, the fraction of the ``dtype`` frames whose session a linear classifier recovers from the latents, and
+    the classifier: the fourth number the reference's MSPS-VAE hyperparameter search reads (``fit_classifier``,
+    plotting/cond_ae_utils.py:1282-1369: ``LogisticRegressionCV(Cs=<8 values>, cv=5, penalty='l2',
+    multi_class='multinomial')`` on the host copy of every training frame, then ``accuracy_score`` on ``dtype``).
+
+    The ``'train'`` trials and the ``dtype`` trials of the sessions ``sess_idx`` (a list, or None for all; at least two)
+    are walked and encoded as ``latent_correlations`` walks and encodes them and put into two device tables in its
+    order; ``columns`` are its columns (default: the unsupervised block of ``ps-vae`` / ``msps-vae``, every latent
+    otherwise).  The class of a row is the index of its session among the selected ones; the folds are sklearn's
+    unshuffled ``StratifiedKFold(n_splits)`` of that order (``fitting.classifier.stratified_folds``).  The
+    ``n_splits x len(Cs)`` models are fitted in lockstep (``fitting.classifier.cross_validate``): an iteration is
+    one ``bn_softmax_cv_lossgrad`` launch over the training table for all models and one transfer of
+    ``M (S (D + 1) + 2)`` doubles; ``bn_softmax_cv_score`` scores them on their held-out folds and the refitted model
+    on the ``dtype`` table.  ``tol`` bounds ``||dF||_inf`` of sklearn's objective; ``max_iter`` the accepted steps.
+
+    -> ``(fc, SessionClassifier)``; under ``torch.distributed`` rank 0 walks every trial and the other ranks return
+    None, as ``label_r2`` does."""
+    who = 'session_classifier'
+    splits = _splits(who, dtype)
+    if len(splits) != 1:
+        raise ValueError("%s: dtype must be 'train', 'val' or 'test', got %r" % (who, dtype))
+    cols = _corr_columns(who, model.hparams, int(model.hparams['n_ae_latents']), columns)
+    wanted = _check_session_classifier(who, data_generator, sess_idx)
+    if n_splits < 2 or n_splits * len(Cs) > _hip.SOFTMAX_CV_MAX_M:
+        raise ValueError('%s: %d folds x %d values of C (2 folds at least, %d models a launch at most)'
+                         % (who, n_splits, len(Cs), _hip.SOFTMAX_CV_MAX_M))
+    _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return None
+    device = next(model.parameters()).device
+    encode = _GraphedTrialEncoder(model)
+    parts = {}
+    wanted_set = set(wanted)
+
+    def on_device(images, sess, data, trial):
+        return encode(images, sess, _batch_fields(model, data)[2]) if sess in wanted_set else None
+
+    def on_host(images, sess, data, trial):
+        if sess not in wanted_set:
+            return None
+        z = encode_trial(model, images, sess, _batch_fields(model, data)[2])
+        return torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(device)
+
+    def sink(sess, trial, result):
+        if result is not None and len(result):
+            parts[(sess, int(trial))] = result
+    dtypes = ['train'] + [d for d in splits if d != 'train']
+    _export_per_trial(who, data_generator, model, on_device, on_host, sink=sink, dtypes=dtypes)
+
+    def table(split):
+        keys = [k for k in _corr_trial_order([ds.batch_idxs for ds in data_generator.datasets], [split], wanted_set)
+                if k in parts]
+        if not keys:
+            raise ValueError('%s: the sessions %s have no %s trial' % (who, wanted, split))
+        z = torch.cat([parts[k] for k in keys], dim=0).to(torch.float32)
+        z = z[:, cols[0]:cols[1]] if isinstance(cols, tuple) else z[:, torch.from_numpy(cols).to(device)]
+        y = np.concatenate([np.full(parts[k].shape[0], wanted.index(k[0]), dtype=np.int32) for k in keys])
+        return z, y
+    z_train, y_train = table('train')
+    z_eval, y_eval = (z_train, y_train) if splits[0] == 'train' else table(splits[0])
+    result = classify_table(z_train, y_train, len(wanted), Cs, n_splits, tol, max_iter, classes=np.asarray(wanted),
+                            columns=cols)
+    hits, rows = score_table(z_eval, y_eval, result.weights_)
+    return hits / rows, result
+
+
+def classify_table(z, y, n_classes, Cs=_clf.DEFAULT_CS, n_splits=5, tol=1e-4, max_iter=100, classes=None, columns=None):
+    """``fitting.classifier.cross_validate`` on a DEVICE table: ``z`` fp32 ``(n, D)``, D <= 64 (a column slice of a
+    wider table is read in place), ``y`` the class of every row, 0 .. ``n_classes`` - 1, as a host array.  Classes and
+    fold ids (``stratified_folds``) are uploaded once; an iteration of the fit is one ``bn_softmax_cv_lossgrad``
+    launch for all ``n_splits x len(Cs)`` models and one transfer of ``M (S (D + 1) + 2)`` doubles; the held-out
+    scores are one ``bn_softmax_cv_score`` launch.  -> ``SessionClassifier``."""
+    clf = _clf
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    S, D = int(n_classes), int(z.shape[1])
+    folds = clf.stratified_folds(y, n_splits)
+    y_d, fold_d = torch.from_numpy(y).to(z.device), torch.from_numpy(folds).to(z.device)
+    leaves = {}
+
+    def on(W, leave):
+        key = leave.tobytes()
+        if key not in leaves:
+            leaves[key] = torch.from_numpy(np.ascontiguousarray(leave, dtype=np.int32)).to(z.device)
+        return torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64)).to(z.device), leaves[key]
+
+    def lossgrad(W, leave):
+        M = len(leave)
+        # (losses, counts and gradients in the one buffer the launch wrote them to: one transfer, no kernel between)
+        host = _hip.softmax_cv_lossgrad(z, y_d, fold_d, *on(W, leave), packed=True).cpu().numpy()
+        return host[:M], host[2 * M:].reshape(M, S, D + 1), host[M:2 * M]
+
+    def score(W, leave):
+        return _hip.softmax_cv_score(z, y_d, fold_d, *on(W, leave)).cpu().numpy()
+    return clf.cross_validate(lossgrad, score, np.bincount(folds, minlength=n_splits), S, D, Cs, tol, max_iter,
+                              classes=classes, columns=columns)
+
+
+def score_table(z, y, weights):
+    """``(hits, rows)`` of ONE model ``weights (S, D + 1)`` on the device table ``z`` with the host classes ``y``: the
+    rows whose argmax logit is their class, and the rows with a class in [0, S) (``bn_softmax_cv_score``)."""
+    W_d = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float64)[None]).to(z.device)
+    y_d = torch.from_numpy(np.ascontiguousarray(y, dtype=np.int32)).to(z.device)
+    none = torch.full((1,), -1, dtype=torch.int32, device=z.device)
+    held = _hip.softmax_cv_score(z, y_d, None, W_d, none).cpu().numpy()
+    return float(held[0, 0]), float(held[0, 1])
+
+
+def export_session_classifier(data_generator, model, dtype='val', columns=None, filename=None, **kwargs):
+    """``session_classifier``'s ``fc`` as the file the reference's ``fit_classifier`` saves and its hyperparameter
+    search reads: ``fc_session_classification.npy`` in the model's version directory (or ``filename``), written with
+    ``np.save(np.array([fc]))``.  -> ``(path, fc, SessionClassifier)`` (None on the ranks other than 0)."""
+    out = session_classifier(data_generator, model, dtype=dtype, columns=columns, **kwargs)
+    if out is None:
+        return None
+    if filename is None:
+        filename = os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, SESSION_CLASSIFIER_FILE)
+    np.save(filename, np.array([out[0]]))
+    return filename, out[0], out[1]

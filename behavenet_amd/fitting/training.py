@@ -591,6 +591,10 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
         # (any class has latents to correlate; a bad batch size is an error now, not after the last epoch)
         from behavenet_amd.fitting.eval import _corr_segments
         _corr_segments("fit: hparams['latent_corr_batch_size']", [], [], hparams.get('latent_corr_batch_size'))
+    if method == 'ae' and hparams.get('export_session_classifier', False):
+        # (one session has nothing to tell apart: an error now, not after the last epoch)
+        from behavenet_amd.fitting.eval import _check_session_classifier
+        _check_session_classifier("fit: hparams['export_session_classifier']", data_generator)
     # hparams['shard_optimizer'] (BN_SHARD_OPTIMIZER=0/1): reduce-scatter -> Adam on this rank's 1/R
     # shard of the arena -> all-gather, instead of all-reduce + R identical steps
     # (fitting/distributed.py sharded_step, default_shard_optimizer: on for frame sharding over >= 4 ranks)
@@ -850,6 +854,11 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
         from behavenet_amd.fitting.eval import export_latent_correlations
         export_latent_correlations(data_generator, best_val_model, dtype='train',
                                    segments=hparams.get('latent_corr_batch_size'))
+    if method == 'ae' and hparams.get('export_session_classifier', False):
+        if is_main:
+            print('exporting the session classifier score of the val trials')
+        from behavenet_amd.fitting.eval import export_session_classifier
+        export_session_classifier(data_generator, best_val_model, dtype='val')
     if resume and is_main:
         if state_writer is not None:
             state_writer.wait()

@@ -1,7 +1,8 @@
 """Latent and label traversals with the reference's signatures (``behavenet/plotting/cond_ae_utils.py``:
 ``interpolate_1d``, ``interpolate_2d``), decoded in ONE batch, the ranges they sweep (``get_input_range``,
 ``compute_range``), selected on the device, the per-trial label scores of the models with supervised latents
-(``get_label_r2``) and the correlations of the unsupervised latents (``get_latent_corr``), reduced on the device.
+(``get_label_r2``) and the correlations of the unsupervised latents (``get_latent_corr``), reduced on the device, and
+the session classifier on the latents (``fit_classifier``), fitted on the device.
 
 The reference calls ``get_reconstruction`` once per point: P launch chains of one frame and P copies to the host.
 Here the points are collected into one table (``fitting.eval.traversal_points``) and ``get_reconstruction`` is called
@@ -19,7 +20,8 @@ from behavenet_amd.fitting import eval as _eval
 from behavenet_amd.fitting.eval import get_reconstruction, traversal_points
 from behavenet_amd.plotting import get_crop
 
-__all__ = ['interpolate_1d', 'interpolate_2d', 'get_input_range', 'compute_range', 'get_label_r2', 'get_latent_corr']
+__all__ = ['interpolate_1d', 'interpolate_2d', 'get_input_range', 'compute_range', 'get_label_r2', 'get_latent_corr',
+           'fit_classifier']
 
 _PLAIN = ('ae', 'vae', 'beta-tcvae', 'ps-vae', 'msps-vae')
 _COND = ('cond-ae', 'cond-vae')
@@ -291,3 +293,52 @@ def get_latent_corr(hparams, model, data_generator, version, batch_size=None, dt
         print('loading results from %s' % save_file)
     # (round_trip: the file holds the shortest decimals that name the float64 values, and they are read back as those)
     return pd.read_csv(save_file, float_precision='round_trip')
+
+
+# ------------------------------------------------------------------------------------------ session classifier
+# the classes the reference's collect_data serves (cond_ae_utils.py:1294-1307); any other: NotImplementedError
+_CLASSIFIER_CLASSES = ('ae', 'vae', 'cond-vae', 'sss-vae', 'ps-vae', 'msps-vae')
+
+
+def fit_classifier(model, data_generator, dtype='val', fit_full=False, overwrite=False):
+    """Fit a classifier from the latent space to the session id -- the reference's ``fit_classifier``
+    (cond_ae_utils.py:1323-1369), its signature, its messages and its file: ``fc_session_classification.npy`` in
+    ``model.hparams['expt_dir']/version_<model.version>`` holds ``np.array([fc])``, the fraction of the ``dtype``
+    frames whose session the classifier fitted on the ``'train'`` frames recovers.  The file is read where it exists
+    and ``overwrite`` is false (neither the model nor the generator is touched then, and the classifier returned is
+    None); otherwise ``fitting.eval.session_classifier`` fits and scores on the device.  ``fit_full=True`` takes every
+    latent of a ``ps-vae`` instead of its unsupervised block; for ``msps-vae`` the reference ignores the flag
+    (``collect_data``: 1304-1305), and so does this.  -> ``(fc, lr)``, ``lr`` a
+    ``fitting.classifier.SessionClassifier`` with sklearn's attribute names."""
+    model_class = model.hparams['model_class']
+    if model_class not in _CLASSIFIER_CLASSES:
+        raise NotImplementedError('fit_classifier: model class %r (served: %s)'
+                                  % (model_class, ', '.join(_CLASSIFIER_CLASSES)))
+    save_file = os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, _eval.SESSION_CLASSIFIER_FILE)
+    if not os.path.exists(save_file) or overwrite:
+        if not os.path.exists(save_file):
+            print('FC metrics do not exist; computing from scratch')
+        else:
+            print('overwriting metrics at %s' % save_file)
+        columns = None          # (the unsupervised block of ps-vae / msps-vae, every latent otherwise)
+        if model_class in ('sss-vae', 'ps-vae') and fit_full:
+            columns = slice(None)
+        elif model_class == 'sss-vae':          # (the ps-vae's earlier name: the same block)
+            columns = slice(int(model.hparams['n_labels']), None)
+        # (the reference's messages; its four stages are one call here, so one 'done' closes them all)
+        print('collecting training labels and latents')
+        print('collecting %s labels and latents' % dtype)
+        print('fitting linear classifier model with training data')
+        print('computing fraction correct on %s data' % dtype)
+        out = _eval.session_classifier(data_generator, model, dtype=dtype, columns=columns)
+        if out is None:
+            return None          # (torch.distributed: rank 0 alone computes and writes)
+        fc, lr = out
+        print('done')
+        print('saving results to %s' % save_file)
+        np.save(save_file, np.array([fc]))
+    else:
+        print('loading results from %s' % save_file)
+        fc = np.load(save_file)[0]
+        lr = None
+    return fc, lr

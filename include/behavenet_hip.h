@@ -702,6 +702,46 @@ size_t bn_segment_gram_ws_bytes(int n, int S, int D);
 int bn_segment_gram(const float* z, int ld, const float* c, const long long* offsets, int S, int D, int n,
                     double* out, void* ws, size_t ws_bytes, bn_stream_t stream);
 
+/* M multinomial logistic models at once over the rows of a table of latents: the sums behind the session classifier
+ * that the MSPS-VAE hyperparameter search scores its models by (plotting/cond_ae_utils.py:1282-1369: sklearn's
+ * LogisticRegressionCV on the host copy of every training frame).  The 5 x 8 (fold, C) models of a cross-validated
+ * fit differ only in their weights and in the fold they leave out, so ONE pass over the table serves all of them.
+ * z: fp32 table of n rows and D columns, 1 <= D <= 64, row-major with leading dimension ld >= D, on any 4-byte
+ * boundary.  y: int32 (n), the class of a row; a row whose y is outside [0, S) belongs to no model.  fold: int32 (n),
+ * the fold of a row, or NULL (a row belongs to no fold).  W: float64 (M, S, D + 1), one weight row a class and
+ * model, column D the intercept.  leave: int32 (M), the fold model m leaves out, -1 for none.  2 <= S <= 8,
+ * 1 <= M <= 64, n >= 0.  None of these is ever written.
+ *
+ * bn_softmax_cv_lossgrad: with l = W[m] (z, 1), formed in float64 from the fp32 row, over the rows with y in [0, S)
+ * and fold != leave[m],
+ *   loss[m]  = sum (logsumexp_k l_k - l_y)                              float64 (M)
+ *   grad[m]  = sum (softmax(l) - onehot(y)) (x) (z, 1)                  float64 (M, S, D + 1)
+ *   count[m] = the number of those rows (an exact integer)              float64 (M)
+ * logsumexp is taken with the row maximum subtracted (logits of +-800 give finite sums) and every sum is float64.
+ * Regularisation and the 1 / n scaling are the caller's.  A row with a NaN or Inf among its D values gives NaN as
+ * loss[m] and all of grad[m] for the models that include it and nothing to the others.
+ *
+ * bn_softmax_cv_score: out float64 (M, 2); over the rows with y in [0, S) and, where leave[m] >= 0,
+ * fold == leave[m]: out[m][0] = the rows whose float64 argmax_k l_k is y (a tie goes to the lowest class; a row with
+ * a NaN or Inf among its values reads as class 0, as np.argmax of NaNs does), out[m][1] = the rows.  Exact integers.
+ *
+ * Every output element is written exactly once (zeros for n == 0).  The rows are cut into row blocks and the models
+ * into groups of at most 128 / S; every (block, model) leaves one partial in the workspace and the partials are added
+ * in block order: no global atomics, and the order of every sum is fixed by (n, D, S, M): the same bits on every
+ * call.  The inner products run on v_mfma_f64_16x16x4_f64.
+ * ws: bn_softmax_cv_{lossgrad,score}_ws_bytes(n, D, S, M) bytes (32 MiB at most) on a 16-byte boundary; nothing is
+ * read from it that the call has not written.
+ * BN_E_SHAPE (nothing written, to the outputs or to ws): D, S, M or n outside the limits above (the queries return 0
+ * for these), ld < D, a workspace smaller than the query's, z, y, fold or leave off a 4-byte, W or an output off an
+ * 8-byte, ws off a 16-byte boundary.  BN_E_BADARG: z, y, W, leave, an output or ws NULL. */
+size_t bn_softmax_cv_lossgrad_ws_bytes(int n, int D, int S, int M);
+int bn_softmax_cv_lossgrad(const float* z, int ld, const int* y, const int* fold, const double* W, const int* leave,
+                           int n, int D, int S, int M, double* loss, double* grad, double* count, void* ws,
+                           size_t ws_bytes, bn_stream_t stream);
+size_t bn_softmax_cv_score_ws_bytes(int n, int D, int S, int M);
+int bn_softmax_cv_score(const float* z, int ld, const int* y, const int* fold, const double* W, const int* leave,
+                        int n, int D, int S, int M, double* out, void* ws, size_t ws_bytes, bn_stream_t stream);
+
 /* unit-float frames -> stored uint8 grey levels, the inverse of bn_u8_to_unit_float on k / 255:
  *   out[i] = NaN -> 0, else clamp(rint(in[i] * 255), 0, 255)
  * The product is one fp32 multiplication and rint rounds half to even, i.e. numpy's
