@@ -724,7 +724,9 @@ __global__ __launch_bounds__(PD_THREADS) void k_col2im(const float* __restrict__
 static int col_frames(const BnGeom& g) {
     const size_t per = (size_t)g.Hs * g.Ws * g.Cb * g.R * g.S * 4;
     size_t nb = COL_MAX_BYTES / (per ? per : 1);
-    const size_t rows_cap = ((size_t)1 << 21) / ((size_t)g.Hs * g.Ws);     // GEMM grid: rows / 32 < 65536
+    // GEMM grid: rows / 32 <= 65536 row tiles in grid.y (a pass of exactly 2^21 rows launches 65536 of them, which the
+    // runtime accepts: tests/test_gpu_column_matrix.py, k1_c3_c5_256x256_n33)
+    const size_t rows_cap = ((size_t)1 << 21) / ((size_t)g.Hs * g.Ws);
     if (nb > rows_cap) nb = rows_cap;
     if (nb > (size_t)g.N) nb = g.N;
     return (int)nb;
