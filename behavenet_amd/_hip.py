@@ -145,6 +145,8 @@ SIGNATURES = {
     'bn_unit_float_to_u8': (_c_int, [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
     'bn_cond_encoder_input': (_c_int, [_c_void_p, _c_int, _c_void_p] + [_c_int] * 6 + [_c_void_p, _c_void_p]),
     'bn_frame_mosaic_u8': (_c_int, [_c_void_p] + [_c_int] * 10 + [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_void_p]),
+    'bn_frame_mosaic_ch_u8': (_c_int, [_c_void_p] + [_c_int] * 11 + [_c_void_p] + [_c_int] * 3
+                              + [_c_void_p, _c_void_p]),
     'bn_recon_panels_u8': (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p] + [_c_int] * 6
                            + [_c_void_p, _c_size_t, _c_void_p]),
     'bn_column_select_ws_bytes': (_c_size_t, [_c_int] * 3),
@@ -1101,15 +1103,34 @@ def cond_encoder_input(x, coords, n_maps=None):
     return out
 
 
+def mosaic_channels(ch, n_channels):
+    """``(ch0, n_ch)``, the channels a mosaic's panel shows side by side, of ``ch``: an int (that channel alone),
+    None (all ``n_channels``) or a pair ``(ch0, n_ch)``; ``ValueError`` for anything else and for channels outside
+    [0, n_channels)."""
+    C = int(n_channels)
+    if isinstance(ch, (int, np.integer)):
+        ch0, n_ch = int(ch), 1
+        if not 0 <= ch0 < C:
+            raise ValueError('frame_mosaic_u8: channel %d of frames with %d channels' % (ch0, C))
+        return ch0, n_ch
+    if ch is None:
+        return 0, C
+    if isinstance(ch, (tuple, list)) and len(ch) == 2 and all(isinstance(v, (int, np.integer)) for v in ch):
+        ch0, n_ch = int(ch[0]), int(ch[1])
+        if n_ch < 1 or ch0 < 0 or ch0 + n_ch > C:
+            raise ValueError('frame_mosaic_u8: channels [%d, %d) of frames with %d channels' % (ch0, ch0 + n_ch, C))
+        return ch0, n_ch
+    raise ValueError('frame_mosaic_u8: ch must be an int, None (all channels) or a pair (ch0, n_ch), got %r' % (ch,))
+
+
 def check_mosaic_args(shape, ch=0, crop=None):
     """The crop window ``(y_min, x_min, Hc, Wc)`` of a mosaic of frames of ``shape`` (P, C, H, W) -- ``crop`` or the
-    whole frame -- after the checks that need no device: ``ValueError`` for a channel outside [0, C), a negative
-    origin (a numpy slice would wrap there) or an empty window."""
+    whole frame -- after the checks that need no device: ``ValueError`` for a channel outside [0, C) (``ch`` as
+    ``mosaic_channels`` reads it), a negative origin (a numpy slice would wrap there) or an empty window."""
     if len(shape) != 4:
         raise ValueError('frame_mosaic_u8: expected frames (P, C, H, W), got %s' % (tuple(shape),))
     P, C, H, W = (int(v) for v in shape)
-    if not 0 <= int(ch) < C:
-        raise ValueError('frame_mosaic_u8: channel %d of frames with %d channels' % (ch, C))
+    mosaic_channels(ch, C)
     y_min, x_min, Hc, Wc = (0, 0, H, W) if crop is None else (int(v) for v in crop)
     if y_min < 0 or x_min < 0:
         raise ValueError('frame_mosaic_u8: the crop window starts at (%d, %d); a negative origin is not served '
@@ -1136,9 +1157,12 @@ def frame_mosaic_u8(frames, src, ch=0, crop=None):
     """Frames (P, C, H, W), fp32 unit floats or uint8 grey levels, -> the uint8 DEVICE mosaic (T, R * Hc, Cc * Wc)
     whose panel (t, r, c) shows channel ``ch`` of frame ``src[t, r, c]`` inside the window ``crop = (y_min, x_min, Hc,
     Wc)`` (default: the whole frame), zero where the window passes the bottom or right edge and where ``src`` is
-    negative.  fp32 frames are quantised by ``unit_float_to_u8``'s rule.  ``src``: a host array (T, R, Cc) or (R, Cc),
-    checked against P here and uploaded, or an int32 device tensor (T, R, Cc) the caller has checked
-    (``check_mosaic_src``).  One pass on the current stream (csrc/frame_mosaic.hip)."""
+    negative.  fp32 frames are quantised by ``unit_float_to_u8``'s rule.  ``ch=None`` shows all C channels of the
+    frame side by side in its panel, as the reference's ``concat`` does, and a pair ``ch=(ch0, n_ch)`` the channels
+    ``ch0 .. ch0 + n_ch - 1``: the mosaic is then (T, R * Hc, Cc * n_ch * Wc) and sub-panel q of panel (t, r, c) shows
+    channel ``ch0 + q`` (``bn_frame_mosaic_ch_u8``; an int ``ch`` is ``bn_frame_mosaic_u8``).  ``src``: a host array
+    (T, R, Cc) or (R, Cc), checked against P here and uploaded, or an int32 device tensor (T, R, Cc) the caller has
+    checked (``check_mosaic_src``).  One pass on the current stream (csrc/frame_mosaic.hip)."""
     if not torch.is_tensor(frames) or frames.dim() != 4:
         raise ValueError('frame_mosaic_u8: expected frames (P, C, H, W), got %s'
                          % (tuple(frames.shape) if torch.is_tensor(frames) else type(frames).__name__,))
@@ -1153,11 +1177,18 @@ def frame_mosaic_u8(frames, src, ch=0, crop=None):
     frames, src = frames.contiguous(), src.contiguous()
     P, C, H, W = frames.shape
     T, R, Cc = src.shape
-    out = torch.empty((T, R * Hc, Cc * Wc), dtype=torch.uint8, device=frames.device)
-    _check(load().bn_frame_mosaic_u8(
-        _ptr(frames, 'frames', dtype=frames.dtype), int(frames.dtype == torch.uint8), P, C, H, W, int(ch), y_min,
-        x_min, Hc, Wc, _ptr(src, 'src', dtype=torch.int32), T, R, Cc, _ptr(out, 'out', dtype=torch.uint8), _stream()),
-        'bn_frame_mosaic_u8')
+    ch0, n_ch = mosaic_channels(ch, C)
+    out = torch.empty((T, R * Hc, Cc * n_ch * Wc), dtype=torch.uint8, device=frames.device)
+    if isinstance(ch, (int, np.integer)):
+        _check(load().bn_frame_mosaic_u8(
+            _ptr(frames, 'frames', dtype=frames.dtype), int(frames.dtype == torch.uint8), P, C, H, W, ch0, y_min,
+            x_min, Hc, Wc, _ptr(src, 'src', dtype=torch.int32), T, R, Cc, _ptr(out, 'out', dtype=torch.uint8),
+            _stream()), 'bn_frame_mosaic_u8')
+    else:
+        _check(load().bn_frame_mosaic_ch_u8(
+            _ptr(frames, 'frames', dtype=frames.dtype), int(frames.dtype == torch.uint8), P, C, H, W, ch0, n_ch, y_min,
+            x_min, Hc, Wc, _ptr(src, 'src', dtype=torch.int32), T, R, Cc, _ptr(out, 'out', dtype=torch.uint8),
+            _stream()), 'bn_frame_mosaic_ch_u8')
     return out
 
 

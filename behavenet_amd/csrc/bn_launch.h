@@ -87,11 +87,14 @@ bool bn_cond_input_ok(int N, int C, int H, int W, int L);
 int bn_launch_cond_input(const void* frames, int frames_is_u8, const float* coords, int ld, int N, int C, int H, int W,
                          int L, float* out, hipStream_t st);
 
-// frame_mosaic.hip: one channel of frames (fp32 unit floats or uint8 grey levels), cropped, quantised and tiled into
-// a (T, R Hc, Cc Wc) uint8 mosaic by a device table of source frames (-1: a blank panel)
-bool bn_frame_mosaic_ok(int P, int C, int H, int W, int ch, int y_min, int x_min, int Hc, int Wc, int T, int R, int Cc);
-int bn_launch_frame_mosaic(const void* frames, int frames_u8, int P, int C, int H, int W, int ch, int y_min, int x_min,
-                           int Hc, int Wc, const int* src, int T, int R, int Cc, unsigned char* out, hipStream_t st);
+// frame_mosaic.hip: the channels [ch0, ch0 + n_ch) of frames (fp32 unit floats or uint8 grey levels), cropped,
+// quantised and tiled side by side into a (T, R Hc, Cc n_ch Wc) uint8 mosaic by a device table of source frames
+// (-1: a blank panel)
+bool bn_frame_mosaic_ok(int P, int C, int H, int W, int ch0, int n_ch, int y_min, int x_min, int Hc, int Wc, int T,
+                        int R, int Cc);
+int bn_launch_frame_mosaic(const void* frames, int frames_u8, int P, int C, int H, int W, int ch0, int n_ch, int y_min,
+                           int x_min, int Hc, int Wc, const int* src, int T, int R, int Cc, unsigned char* out,
+                           hipStream_t st);
 
 // recon_panels.hip: frames, their reconstruction and the residual 0.5 + (orig * mask - recon) as three uint8 panels
 // per row, channels side by side, into frames of out_frame_stride >= 3 C H W bytes (one row of a movie)

@@ -1954,18 +1954,27 @@ extern "C" int bn_cond_encoder_input(const void* frames, int frames_is_u8, const
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// Frames -> a uint8 mosaic of cropped panels (frame_mosaic.hip): latent traversals as grids and movies.
-extern "C" int bn_frame_mosaic_u8(const void* frames, int frames_u8, int p, int c, int h, int w, int ch, int y_min,
-                                  int x_min, int hc, int wc, const int* src, int t, int r, int cc, unsigned char* out,
-                                  bn_stream_t stream) {
-    if (!bn_frame_mosaic_ok(p, c, h, w, ch, y_min, x_min, hc, wc, t, r, cc)) return BN_E_SHAPE;
+// Frames -> a uint8 mosaic of cropped panels (frame_mosaic.hip): latent traversals, point paths and session swaps as
+// grids and movies.  A panel shows the channels [ch0, ch0 + n_ch) of its frame side by side.
+extern "C" int bn_frame_mosaic_ch_u8(const void* frames, int frames_u8, int p, int c, int h, int w, int ch0, int n_ch,
+                                     int y_min, int x_min, int hc, int wc, const int* src, int t, int r, int cc,
+                                     unsigned char* out, bn_stream_t stream) {
+    if (!bn_frame_mosaic_ok(p, c, h, w, ch0, n_ch, y_min, x_min, hc, wc, t, r, cc)) return BN_E_SHAPE;
     if ((size_t)t * (size_t)r * (size_t)cc == 0) return 0;
     // (without frames every panel is blank and `frames` is not read)
     if (!src || !out || (p > 0 && !frames)) return BN_E_BADARG;
     // (operands that are not even 4-byte aligned cannot be read at all)
     if (((uintptr_t)src & 3) || (!frames_u8 && ((uintptr_t)frames & 3))) return BN_E_SHAPE;
-    return bn_launch_frame_mosaic(frames, frames_u8, p, c, h, w, ch, y_min, x_min, hc, wc, src, t, r, cc, out,
+    return bn_launch_frame_mosaic(frames, frames_u8, p, c, h, w, ch0, n_ch, y_min, x_min, hc, wc, src, t, r, cc, out,
                                   (hipStream_t)stream);
+}
+
+// (one channel: a sub-panel is the panel)
+extern "C" int bn_frame_mosaic_u8(const void* frames, int frames_u8, int p, int c, int h, int w, int ch, int y_min,
+                                  int x_min, int hc, int wc, const int* src, int t, int r, int cc, unsigned char* out,
+                                  bn_stream_t stream) {
+    return bn_frame_mosaic_ch_u8(frames, frames_u8, p, c, h, w, ch, 1, y_min, x_min, hc, wc, src, t, r, cc, out,
+                                 stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------

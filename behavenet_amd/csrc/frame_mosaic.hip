@@ -1,19 +1,22 @@
 // Frames -> a uint8 mosaic of cropped panels in one pass ("traversals"):
 //
-//   out[t, r Hc + y, c Wc + x] = 0                                                    blank panel or outside the frame
-//                              = bn_quantise_u8(frames[s, ch, y_min + y, x_min + x])   fp32 frames (unit floats)
-//                              = frames[s, ch, y_min + y, x_min + x]                   uint8 frames (grey levels)
+//   out[t, r Hc + y, (c n_ch + q) Wc + x] = 0                                         blank panel or outside the frame
+//                              = bn_quantise_u8(frames[s, ch0 + q, y_min + y, x_min + x])   fp32 frames (unit floats)
+//                              = frames[s, ch0 + q, y_min + y, x_min + x]                   uint8 frames (grey levels)
 //
 // with s = src[t, r, c]; a panel is blank for s < 0 (and for s >= P, which the Python wrapper refuses before any
-// call), a pixel is outside for y_min + y >= H or x_min + x >= W -- the zero fill of the reference's get_crop.  One
-// channel is picked, cropped, quantised and tiled; every output byte is written once, no memset is relied on.
+// call), a pixel is outside for y_min + y >= H or x_min + x >= W -- the zero fill of the reference's get_crop.  A
+// panel is n_ch sub-panels of Wc columns, the channels ch0 .. ch0 + n_ch - 1 of ONE frame side by side (the
+// reference's concat(ims[i])): one index read per panel, whatever n_ch is.  bn_frame_mosaic_u8 is n_ch = 1, where a
+// sub-panel is the panel.  Channels are picked, cropped, quantised and tiled; every output byte is written once, no
+// memset is relied on.
 //
-// HBM-bound: Hc Wc (4 or 1) bytes read per panel shown, Hc Wc written.  A thread owns 16 consecutive bytes of one
-// output row.  With `out` and the row length Cc Wc on 16-byte boundaries it writes them with one 16-byte store;
-// where the 16 bytes lie inside one panel, inside the frame and their source sits on a 16-byte boundary they come
-// from four 16-byte loads (uint8 frames: one), otherwise -- a segment that straddles two panels, the frame's edge,
-// a window or a pointer off alignment -- byte by byte.  Without that alignment of the output the bytes are stored one
-// by one.  mo_byte is the only arithmetic, so every route gives the same bytes.
+// HBM-bound: Hc Wc (4 or 1) bytes read per sub-panel shown, Hc Wc written.  A thread owns 16 consecutive bytes of one
+// output row.  With `out` and the row length Cc n_ch Wc on 16-byte boundaries it writes them with one 16-byte store;
+// where the 16 bytes lie inside one sub-panel, inside the frame and their source sits on a 16-byte boundary they come
+// from four 16-byte loads (uint8 frames: one), otherwise -- a segment that straddles two sub-panels, the frame's
+// edge, a window or a pointer off alignment -- byte by byte.  Without that alignment of the output the bytes are
+// stored one by one.  mo_byte is the only arithmetic, so every route gives the same bytes.
 //
 // The block is (bx, 256 / bx): bx threads walk the 16-byte segments of a row, 256 / bx rows share a block, and
 // blockIdx.x counts row groups -- a movie has far more than 65,535 rows, which grid.y could not hold.  No 64-bit
@@ -28,31 +31,34 @@ struct MoArgs {
     const void* frames;
     const int* src;
     unsigned char* out;
-    int P, C, H, W, ch, y_min, x_min, Hc, Wc, R, Cc;
-    unsigned rows, OH, OW, segs;          // rows = T R Hc, OH = R Hc, OW = Cc Wc, segs = ceil(OW / 16)
+    int P, C, H, W, ch0, n_ch, y_min, x_min, Hc, Wc, R, Cc;
+    unsigned rows, OH, OW, segs;          // rows = T R Hc, OH = R Hc, OW = Cc n_ch Wc, segs = ceil(OW / 16)
 };
 
-// the frame plane of panel (t, r, c), or nullptr for a blank one
-template <bool U8>
-__device__ __forceinline__ const void* mo_plane(const MoArgs& a, size_t panel_row, unsigned c) {
+// the frame plane of sub-panel u = c n_ch + q of panel row (t, r) -- channel ch0 + q of frame src[t, r, c] -- or
+// nullptr for a blank one (u < Cc n_ch, so c < Cc and ch0 + q < C).  ONE: n_ch == 1, where u is the panel and the
+// division is not paid (measured: 18.8 against 17.1 us on the uint8 route of the traversal movie with it)
+template <bool U8, bool ONE>
+__device__ __forceinline__ const void* mo_plane(const MoArgs& a, size_t panel_row, unsigned u) {
+    const unsigned c = ONE ? u : u / (unsigned)a.n_ch, q = ONE ? 0u : u - c * (unsigned)a.n_ch;
     const int s = a.src[panel_row * (size_t)a.Cc + c];
     if (s < 0 || s >= a.P) return nullptr;
-    const size_t at = ((size_t)s * (size_t)a.C + (size_t)a.ch) * (size_t)a.H * (size_t)a.W;
+    const size_t at = ((size_t)s * (size_t)a.C + (size_t)a.ch0 + q) * (size_t)a.H * (size_t)a.W;
     return U8 ? (const void*)((const unsigned char*)a.frames + at) : (const void*)((const float*)a.frames + at);
 }
 
 // one output byte: column ox of the output row whose source row is ys (ys < H checked by the caller)
-template <bool U8>
+template <bool U8, bool ONE>
 __device__ __forceinline__ unsigned mo_byte(const MoArgs& a, size_t panel_row, size_t row_at, unsigned ox) {
-    const unsigned c = ox / (unsigned)a.Wc;
-    const unsigned xs = (unsigned)a.x_min + (ox - c * (unsigned)a.Wc);
+    const unsigned u = ox / (unsigned)a.Wc;
+    const unsigned xs = (unsigned)a.x_min + (ox - u * (unsigned)a.Wc);
     if (xs >= (unsigned)a.W) return 0u;
-    const void* p = mo_plane<U8>(a, panel_row, c);
+    const void* p = mo_plane<U8, ONE>(a, panel_row, u);
     if (!p) return 0u;
     return U8 ? (unsigned)((const unsigned char*)p)[row_at + xs] : bn_quantise_u8(((const float*)p)[row_at + xs]);
 }
 
-template <bool U8, bool VEC>
+template <bool U8, bool VEC, bool ONE>
 __global__ __launch_bounds__(MO_THREADS) void k_frame_mosaic(const MoArgs a) {
     const unsigned row = blockIdx.x * blockDim.y + threadIdx.y;
     if (row >= a.rows) return;
@@ -68,11 +74,11 @@ __global__ __launch_bounds__(MO_THREADS) void k_frame_mosaic(const MoArgs a) {
             // (OW is a multiple of 16: the segment is whole)
             unsigned w[4] = {0u, 0u, 0u, 0u};
             if (ys < (unsigned)a.H) {
-                const unsigned c = x0 / (unsigned)a.Wc, x = x0 - c * (unsigned)a.Wc;
+                const unsigned u = x0 / (unsigned)a.Wc, x = x0 - u * (unsigned)a.Wc;
                 const unsigned xs = (unsigned)a.x_min + x;
                 bool done = false;
                 if (x + MO_SEG <= (unsigned)a.Wc && xs + MO_SEG <= (unsigned)a.W) {
-                    const void* p = mo_plane<U8>(a, panel_row, c);
+                    const void* p = mo_plane<U8, ONE>(a, panel_row, u);
                     if (!p) {
                         done = true;          // a blank panel: zeros
                     } else if (U8) {
@@ -99,14 +105,14 @@ __global__ __launch_bounds__(MO_THREADS) void k_frame_mosaic(const MoArgs a) {
                 if (!done) {
 #pragma unroll
                     for (int k = 0; k < MO_SEG; ++k)
-                        w[k >> 2] |= mo_byte<U8>(a, panel_row, row_at, x0 + k) << (8 * (k & 3));
+                        w[k >> 2] |= mo_byte<U8, ONE>(a, panel_row, row_at, x0 + k) << (8 * (k & 3));
                 }
             }
             *reinterpret_cast<uint4*>(o + x0) = make_uint4(w[0], w[1], w[2], w[3]);
         } else {
             const unsigned x1 = x0 + MO_SEG < a.OW ? x0 + MO_SEG : a.OW;
             for (unsigned ox = x0; ox < x1; ++ox)
-                o[ox] = (unsigned char)(ys < (unsigned)a.H ? mo_byte<U8>(a, panel_row, row_at, ox) : 0u);
+                o[ox] = (unsigned char)(ys < (unsigned)a.H ? mo_byte<U8, ONE>(a, panel_row, row_at, ox) : 0u);
         }
     }
 }
@@ -119,31 +125,35 @@ static inline unsigned mo_block_x(size_t OW) {
     return bx;
 }
 
-bool bn_frame_mosaic_ok(int P, int C, int H, int W, int ch, int y_min, int x_min, int Hc, int Wc, int T, int R,
-                        int Cc) {
+bool bn_frame_mosaic_ok(int P, int C, int H, int W, int ch0, int n_ch, int y_min, int x_min, int Hc, int Wc, int T,
+                        int R, int Cc) {
     if (P < 0 || C <= 0 || H <= 0 || W <= 0 || T < 0 || R < 0 || Cc < 0) return false;
-    if (ch < 0 || ch >= C || y_min < 0 || x_min < 0 || Hc <= 0 || Wc <= 0) return false;
+    if (n_ch < 1 || ch0 < 0 || (long long)ch0 + (long long)n_ch > (long long)C) return false;
+    if (y_min < 0 || x_min < 0 || Hc <= 0 || Wc <= 0) return false;
     // the launch counts output rows and columns in 32 bits (and y_min + y, x_min + x with them)
     const size_t lim = (size_t)1 << 31;
     const size_t TR = (size_t)T * (size_t)R;
     if (TR >= lim || TR * (size_t)Hc >= lim || (size_t)Cc * (size_t)Wc >= lim) return false;
+    const size_t OW = (size_t)Cc * (size_t)Wc * (size_t)n_ch;          // (n_ch <= C < 2^31: below 2^62)
+    if (OW >= lim) return false;
     if ((size_t)y_min + (size_t)Hc >= lim || (size_t)x_min + (size_t)Wc >= lim) return false;
     // ... and a grid holds fewer than 2^32 threads
-    const size_t by = MO_THREADS / mo_block_x((size_t)Cc * (size_t)Wc);
+    const size_t by = MO_THREADS / mo_block_x(OW);
     if ((TR * (size_t)Hc + by - 1) / by * MO_THREADS >= ((size_t)1 << 32)) return false;
     // (frame and output offsets stay far inside 64 bits)
     const size_t HW = (size_t)H * (size_t)W, big = (size_t)1 << 44;
     return (size_t)C <= big / HW && (size_t)P <= big / ((size_t)C * HW);
 }
 
-int bn_launch_frame_mosaic(const void* frames, int frames_u8, int P, int C, int H, int W, int ch, int y_min, int x_min,
-                           int Hc, int Wc, const int* src, int T, int R, int Cc, unsigned char* out, hipStream_t st) {
-    if (!bn_frame_mosaic_ok(P, C, H, W, ch, y_min, x_min, Hc, Wc, T, R, Cc)) return BN_E_SHAPE;
+int bn_launch_frame_mosaic(const void* frames, int frames_u8, int P, int C, int H, int W, int ch0, int n_ch, int y_min,
+                           int x_min, int Hc, int Wc, const int* src, int T, int R, int Cc, unsigned char* out,
+                           hipStream_t st) {
+    if (!bn_frame_mosaic_ok(P, C, H, W, ch0, n_ch, y_min, x_min, Hc, Wc, T, R, Cc)) return BN_E_SHAPE;
     MoArgs a;
     a.frames = frames, a.src = src, a.out = out;
-    a.P = P, a.C = C, a.H = H, a.W = W, a.ch = ch, a.y_min = y_min, a.x_min = x_min, a.Hc = Hc, a.Wc = Wc;
-    a.R = R, a.Cc = Cc;
-    a.OH = (unsigned)R * (unsigned)Hc, a.OW = (unsigned)Cc * (unsigned)Wc;
+    a.P = P, a.C = C, a.H = H, a.W = W, a.ch0 = ch0, a.n_ch = n_ch, a.y_min = y_min, a.x_min = x_min;
+    a.Hc = Hc, a.Wc = Wc, a.R = R, a.Cc = Cc;
+    a.OH = (unsigned)R * (unsigned)Hc, a.OW = (unsigned)Cc * (unsigned)n_ch * (unsigned)Wc;
     a.rows = (unsigned)T * a.OH;
     a.segs = (a.OW + MO_SEG - 1) / MO_SEG;
     if (a.rows == 0 || a.OW == 0) return 0;
@@ -151,13 +161,15 @@ int bn_launch_frame_mosaic(const void* frames, int frames_u8, int P, int C, int 
     const dim3 block(bx, MO_THREADS / bx);
     const dim3 grid((a.rows + block.y - 1) / block.y);
     const bool vec = a.OW % MO_SEG == 0 && (((uintptr_t)out) & 15u) == 0;
-#define MO_GO(U8, VEC) hipLaunchKernelGGL((k_frame_mosaic<U8, VEC>), grid, block, 0, st, a)
+#define MO_ONE(U8, VEC, ONE) hipLaunchKernelGGL((k_frame_mosaic<U8, VEC, ONE>), grid, block, 0, st, a)
+#define MO_GO(U8, VEC) do { if (n_ch == 1) MO_ONE(U8, VEC, true); else MO_ONE(U8, VEC, false); } while (0)
     if (frames_u8) {
         if (vec) MO_GO(true, true); else MO_GO(true, false);
     } else {
         if (vec) MO_GO(false, true); else MO_GO(false, false);
     }
 #undef MO_GO
+#undef MO_ONE
     BN_LAUNCH_CHECK();
     return 0;
 }

@@ -1,7 +1,8 @@
 """Inference-only passes over every trial: latents -> ``*_latents.pkl`` (BASELINE config 5), per-frame
 reconstruction errors -> ``*_frame_errors.pkl``, uint8 reconstructions -> ``*_reconstructions.npz`` and per-pixel
 error / moment maps -> ``*_pixel_stats.pkl``; latent traversals as uint8 mosaics and movies, decoded in one batch
-and tiled on the device; reconstruction movies (original, reconstruction, residual) as uint8 strips; the
+and tiled on the device, point-path traversal movies and session-swap movies among them; reconstruction movies
+(original, reconstruction, residual) as uint8 strips; the
 percentile ranges of latents and labels, selected on the device; the per-trial label R^2 and MSE of the models
 with supervised latents -> ``r2_supervised.csv``, reduced on the device; and the correlation matrices of the latents
 per batch, trial or session -> ``corr_unsupervised.csv``, from second moments reduced on the device.
@@ -33,7 +34,9 @@ __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconst
            'frame_errors', 'frame_errors_device', 'export_reconstructions', 'reconstruct_trial',
            'reconstruct_trial_device', 'export_pixel_stats', 'pixel_stats', 'pixel_stats_device',
            'summarise_pixel_stats', 'traversal_points', 'traverse_latents', 'traverse_latents_device',
-           'traversal_movie', 'traversal_movie_device', 'reconstruction_movie', 'reconstruction_movie_device',
+           'traversal_movie', 'traversal_movie_device', 'path_points', 'path_movie_src', 'point_path_movie',
+           'point_path_movie_device', 'swap_points', 'swap_layout', 'session_swap_movie', 'session_swap_movie_device',
+           'background_medians', 'reconstruction_movie', 'reconstruction_movie_device',
            'percentile_plan', 'percentile_lerp', 'column_percentiles', 'compute_range', 'latent_ranges',
            'latent_ranges_device', 'summarise_label_sums', 'label_r2', 'export_label_r2', 'summarise_gram',
            'latent_correlations', 'export_latent_correlations', 'session_classifier', 'export_session_classifier',
@@ -1032,6 +1035,236 @@ def traversal_movie(model, base_latents, mins, maxes, input_idxs, n_frames, n_co
     """``traversal_movie_device`` as a numpy array ``(B * n_frames, n_rows * Hc, n_cols * Wc)`` of uint8."""
     return traversal_movie_device(model, base_latents, mins, maxes, input_idxs, n_frames, n_cols, labels_0,
                                   apply_inverse_transform, crop_kwargs, ch, chunk_size).cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------ point paths
+def path_points(points, n_frames):
+    """Every step of the path through ``points`` (n_points, D), as the reference's ``interpolate_point_path`` walks
+    it (plotting/cond_ae_utils.py:786-802): leg ``p`` from ``points[p]`` to ``points[p + 1]`` has ``n_frames[p] + 1``
+    steps ``p0 + pn * ((p1 - p0) / n_frames[p])``, ``pn = 0 .. n_frames[p]`` -- both ends, so the end of one leg and
+    the start of the next both appear.  ``n_frames``: an int for every leg, or one per leg (another length is the
+    reference's AssertionError).  The arithmetic is numpy's in the dtype of ``points``.  -> ``(sum(n_frames + 1),
+    D)``."""
+    points = np.asarray(points)
+    if points.ndim != 2:
+        raise ValueError('path_points: expected points (n_points, D), got %s' % (points.shape,))
+    n_points = points.shape[0]
+    if isinstance(n_frames, (int, np.integer)):
+        n_frames = [n_frames] * (n_points - 1)
+    assert len(n_frames) == (n_points - 1)
+    n_frames = [int(n) for n in n_frames]
+    if any(n < 1 for n in n_frames):
+        raise ValueError('path_points: a leg needs at least one frame, got n_frames %s' % (n_frames,))
+    legs = []
+    for p, n in enumerate(n_frames):
+        p0, p1 = points[None, p], points[None, p + 1]
+        p_vec = (p1 - p0) / n
+        # (a Python int times the vector, for every pn at once: the step number in the vector's own dtype)
+        legs.append(p0 + np.arange(n + 1).astype(p_vec.dtype)[:, None] * p_vec)
+    if not legs:
+        return np.zeros((0, points.shape[1]), dtype=points.dtype)
+    return np.concatenate(legs, axis=0)
+
+
+def path_movie_src(n_base, n_panels, n_steps, n_buffer_frames, n_cols, order_idxs=None, beg=0, end=None):
+    """The source table ``(end - beg, n_rows, n_cols)`` of frames ``[beg, end)`` of a point-path movie.  A base point
+    takes ``n_steps`` movie frames and, where there are several base points, ``n_buffer_frames`` blank ones after
+    them (every panel -1), the last base point included.  At step ``i`` of base ``b`` position ``j`` of the grid --
+    row ``j // n_cols``, column ``j % n_cols`` -- shows panel ``k = order_idxs[j]`` (default: ``j``), which is point
+    ``(b * n_panels + k) * n_steps + i`` of the movie's table; positions past ``len(order_idxs)`` are blank."""
+    order = np.arange(n_panels) if order_idxs is None else np.asarray(order_idxs, dtype=np.int64).reshape(-1)
+    per_base = n_steps + (n_buffer_frames if n_base > 1 else 0)
+    end = n_base * per_base if end is None else end
+    n_rows = -(-len(order) // n_cols)
+    t = np.arange(beg, end)
+    b, i = t // per_base, t % per_base
+    src = np.full((end - beg, n_rows * n_cols), -1, dtype=np.int32)
+    shown = (b[:, None] * n_panels + order[None, :]) * n_steps + i[:, None]
+    src[:, :len(order)] = np.where(i[:, None] < n_steps, shown, -1)
+    return src.reshape(end - beg, n_rows, n_cols)
+
+
+def _mosaic_in_chunks(frames, src_of, n_t, ch, crop, chunk_size):
+    """One mosaic launch per ``chunk_size`` movie frames, ``src_of(beg, end)`` naming their sources."""
+    parts = [_hip.frame_mosaic_u8(frames, src_of(beg, min(beg + chunk_size, n_t)), ch, crop)
+             for beg in range(0, n_t, chunk_size)]
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+
+def point_path_movie_device(model, base_latents, panels, n_frames=10, n_buffer_frames=5, n_cols=3, order_idxs=None,
+                            labels_0=None, apply_inverse_transform=True, crop_kwargs=None, ch=0, chunk_size=200):
+    """The frames the reference's ``make_latent_traversal_movie`` plays (plotting/cond_ae_utils.py:2400-2511, through
+    ``interpolate_point_path``) as a uint8 DEVICE tensor ``(T, n_rows * Hc, n_cols * n_ch * Wc)``.
+
+    ``panels`` is a list of ``(dim, lo, hi)``; the caller lists the label dimensions first and the latent dimensions
+    after them, as the reference does.  For base point ``b`` of ``base_latents`` (B, D) and panel ``k`` the path runs
+    through three points, the base row with ``dim`` set to ``lo``, ``hi`` and ``lo`` again: min -> max -> min in two
+    legs of ``n_frames + 1`` steps (``path_points``; the turning point appears twice).  Panel ``k`` sits at row ``k //
+    n_cols``, column ``k % n_cols`` after ``order_idxs`` (a list of panel numbers, default all in order) is applied;
+    trailing positions are blank.  With B > 1, ``n_buffer_frames`` all-zero frames follow every base point, the last
+    one included, as in the reference; so ``T = B * (2 * (n_frames + 1) + n_buffer_frames)``, or ``2 * (n_frames +
+    1)`` for one base point.
+
+    All ``B * K * 2 * (n_frames + 1)`` points are decoded in one batched pass (``decode_points_device``, which honours
+    ``hparams['hip_decode_dtype']`` as ``traversal_movie_device`` does) and tiled by one mosaic launch per
+    ``chunk_size`` movie frames; only the movie crosses to the host.  ``ch``: one channel, None for all channels side
+    by side in every panel, or ``(ch0, n_ch)`` (``_hip.frame_mosaic_u8``).  ``labels_0``: (1, L) or (B, L) labels of a
+    cond-AE / cond-VAE, whose panels sweep latents here (a label path of those classes goes through the whole model:
+    ``plotting.cond_ae_utils.interpolate_point_path``).
+
+    Departure: the reference crops its label panels alone, so its figure has panels of two sizes; a mosaic has one
+    window, ``crop_kwargs``, for every panel."""
+    base = np.asarray(base_latents)
+    if base.ndim == 1:
+        base = base[None]
+    if base.ndim != 2 or base.shape[0] < 1:
+        raise ValueError('point_path_movie: expected base points (B, D), got %s' % (base.shape,))
+    n_base, n_lat = base.shape
+    panels = [(int(d), lo, hi) for d, lo, hi in panels]
+    n_frames, n_buffer_frames, n_cols, chunk_size = int(n_frames), int(n_buffer_frames), int(n_cols), int(chunk_size)
+    if not panels or n_cols < 1 or n_frames < 1 or n_buffer_frames < 0 or chunk_size < 1:
+        raise ValueError('point_path_movie: %d panels in %d columns, n_frames %d, n_buffer_frames %d, chunk_size %d'
+                         % (len(panels), n_cols, n_frames, n_buffer_frames, chunk_size))
+    for d, _, _ in panels:
+        if not 0 <= d < n_lat:
+            raise ValueError('point_path_movie: dimension %d of a base point with %d' % (d, n_lat))
+    if order_idxs is not None:
+        order_idxs = [int(k) for k in order_idxs]
+        if not order_idxs or min(order_idxs) < 0 or max(order_idxs) >= len(panels):
+            raise ValueError('point_path_movie: order_idxs %s of %d panels' % (order_idxs, len(panels)))
+    n_steps = 2 * (n_frames + 1)
+    legs = []
+    for row in base:
+        for d, lo, hi in panels:
+            points = np.array([row] * 3)
+            points[0, d], points[1, d], points[2, d] = lo, hi, lo
+            legs.append(path_points(points, n_frames))
+    table = np.ascontiguousarray(np.concatenate(legs, axis=0).astype(np.float32))
+    crop = _checked_crop(model, table.shape[0], ch, crop_kwargs)
+    labels = _point_labels(model, labels_0, n_base)
+    if labels is not None:
+        labels = labels.repeat_interleave(len(panels) * n_steps, dim=0)
+    frames = decode_points_device(model, table, labels, apply_inverse_transform, chunk_size)
+    n_t = n_base * (n_steps + (n_buffer_frames if n_base > 1 else 0))
+    return _mosaic_in_chunks(
+        frames, lambda beg, end: path_movie_src(n_base, len(panels), n_steps, n_buffer_frames, n_cols, order_idxs,
+                                                beg, end), n_t, ch, crop, chunk_size)
+
+
+def point_path_movie(model, base_latents, panels, n_frames=10, n_buffer_frames=5, n_cols=3, order_idxs=None,
+                     labels_0=None, apply_inverse_transform=True, crop_kwargs=None, ch=0, chunk_size=200):
+    """``point_path_movie_device`` as a numpy array ``(T, n_rows * Hc, n_cols * n_ch * Wc)`` of uint8."""
+    return point_path_movie_device(model, base_latents, panels, n_frames, n_buffer_frames, n_cols, order_idxs,
+                                   labels_0, apply_inverse_transform, crop_kwargs, ch, chunk_size).cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------ session swaps
+def swap_points(latents, background_idxs, medians):
+    """The latents ``(T, D)`` of a trial once per session, ``(S * T, D)``: block ``s`` is the trial with the columns
+    ``background_idxs`` set to row ``s`` of ``medians`` (S, n_background) -- the reference's ``latents_np[:,
+    background_idxs] = background_medians[s]`` (plotting/cond_ae_utils.py:3111), all sessions in one table."""
+    latents = np.asarray(latents)
+    idxs = np.asarray(background_idxs, dtype=np.int64).reshape(-1)
+    medians = np.asarray(medians)
+    if latents.ndim != 2:
+        raise ValueError('swap_points: expected latents (T, D), got %s' % (latents.shape,))
+    if medians.ndim != 2 or medians.shape[1] != len(idxs):
+        raise ValueError('swap_points: expected medians (S, %d), got %s' % (len(idxs), medians.shape))
+    if len(idxs) and (idxs.min() < 0 or idxs.max() >= latents.shape[1]):
+        raise ValueError('swap_points: background columns %s of latents with %d' % (idxs.tolist(), latents.shape[1]))
+    out = np.tile(latents[None], (medians.shape[0], 1, 1))
+    out[:, :, idxs] = medians[:, None, :]
+    return out.reshape(medians.shape[0] * latents.shape[0], latents.shape[1])
+
+
+def swap_layout(n_sessions, sess_idx=0, layout_pattern=None):
+    """Where the panels of a session-swap movie go: an int array ``(n_rows, n_cols)`` naming the session every
+    position shows, -1 for a blank one (plotting/cond_ae_utils.py:3130-3152).  Session ``sess_idx``, the trial's own,
+    swaps places with session 0 and so comes first.  Without a pattern fewer than four sessions stand in one row,
+    four in 2 x 2, five or six in 2 x 3; a boolean ``layout_pattern`` (n_rows, n_cols) whose sum is the number of
+    sessions places them at its true positions, row by row.  More than six sessions without a pattern, a pattern of
+    another sum and a session outside [0, n_sessions) are ValueErrors."""
+    n_sessions, sess_idx = int(n_sessions), int(sess_idx)
+    if n_sessions < 1 or not 0 <= sess_idx < n_sessions:
+        raise ValueError('session_swap_movie: session %d of %d' % (sess_idx, n_sessions))
+    order = list(range(n_sessions))
+    order[0], order[sess_idx] = order[sess_idx], order[0]
+    if layout_pattern is None:
+        if n_sessions > 6:
+            raise ValueError('session_swap_movie: %d sessions need a layout_pattern (at most six are laid out '
+                             'without one)' % n_sessions)
+        n_rows, n_cols = (1, n_sessions) if n_sessions < 4 else (2, 2) if n_sessions == 4 else (2, 3)
+        pattern = np.arange(n_rows * n_cols).reshape(n_rows, n_cols) < n_sessions
+    else:
+        pattern = np.asarray(layout_pattern).astype(bool)
+        if pattern.ndim != 2 or int(pattern.sum()) != n_sessions:
+            raise ValueError('session_swap_movie: layout_pattern must be a 2-d boolean array with %d true entries, '
+                             'got %s with %d' % (n_sessions, pattern.shape, int(pattern.sum())))
+    grid = np.full(pattern.shape, -1, dtype=np.int64)
+    grid[pattern] = order
+    return grid
+
+
+def session_swap_movie_device(model, trials_latents, background_idxs, medians, sess_idx=0, n_buffer_frames=5,
+                              layout_pattern=None, apply_inverse_transform=False, chunk_size=200):
+    """The frames of the reference's ``make_session_swap_movie`` (plotting/cond_ae_utils.py:3030-3156), the MSPS-VAE's
+    own picture, as a uint8 DEVICE tensor ``(sum T_i + (n_trials - 1) * n_buffer_frames, n_rows * H, n_cols * C *
+    W)``: every trial of ``trials_latents`` (a list of (T_i, D) tables) re-rendered once per session with that session's
+    median background latents (row ``s`` of ``medians`` (S, n_background) in the columns ``background_idxs``:
+    ``swap_points``), one panel per session laid out by ``swap_layout``, every panel showing all channels of its
+    frame side by side; ``n_buffer_frames`` all-zero frames separate the trials.
+
+    A trial's ``S * T_i`` points are decoded by ``decode_points_device`` and tiled by one mosaic launch
+    (``bn_frame_mosaic_ch_u8``) per ``chunk_size`` movie frames; only the movie crosses to the host.
+
+    ``apply_inverse_transform=False`` is the reference's call: it hands the output of ``get_transformed_latents``,
+    whose supervised block lies in label space, to the decoder without mapping it back.  ``True`` maps it back first,
+    which is the consistent alternative."""
+    medians = np.asarray(medians)
+    if medians.ndim != 2:
+        raise ValueError('session_swap_movie: expected medians (S, n_background), got %s' % (medians.shape,))
+    grid = swap_layout(medians.shape[0], sess_idx, layout_pattern)
+    n_buffer_frames, chunk_size = int(n_buffer_frames), int(chunk_size)
+    if n_buffer_frames < 0 or chunk_size < 1 or len(trials_latents) < 1:
+        raise ValueError('session_swap_movie: %d trials, n_buffer_frames %d, chunk_size %d'
+                         % (len(trials_latents), n_buffer_frames, chunk_size))
+    tables = [swap_points(z, background_idxs, medians) for z in trials_latents]
+    lengths = [len(z) for z in trials_latents]
+    if min(lengths) < 1:
+        raise ValueError('session_swap_movie: a trial without frames (lengths %s)' % (lengths,))
+    _checked_crop(model, sum(len(t) for t in tables), None, None)
+    parts = []
+    for i, (table, n) in enumerate(zip(tables, lengths)):
+        frames = decode_points_device(model, np.ascontiguousarray(table, dtype=np.float32), None,
+                                      apply_inverse_transform, chunk_size)
+        n_t = n + (n_buffer_frames if i + 1 < len(tables) else 0)
+
+        def src_of(beg, end, n=n):
+            tau = np.arange(beg, end)[:, None, None]
+            return np.where((grid[None] >= 0) & (tau < n), grid[None] * n + tau, -1).astype(np.int32)
+        parts.append(_mosaic_in_chunks(frames, src_of, n_t, None, None, chunk_size))
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+
+def session_swap_movie(model, trials_latents, background_idxs, medians, sess_idx=0, n_buffer_frames=5,
+                       layout_pattern=None, apply_inverse_transform=False, chunk_size=200):
+    """``session_swap_movie_device`` as a numpy array of uint8."""
+    return session_swap_movie_device(model, trials_latents, background_idxs, medians, sess_idx, n_buffer_frames,
+                                     layout_pattern, apply_inverse_transform, chunk_size).cpu().numpy()
+
+
+def background_medians(data_generator, model, background_idxs, min_p=15, max_p=85):
+    """The median background latents of every session of ``data_generator``, ``(S, n_background)`` float32: per
+    session ``latent_ranges(..., sess_idx=s, min_p, max_p)['med']`` at the columns ``background_idxs`` -- the first
+    user of ``'med'``, with the reference's percentiles (plotting/cond_ae_utils.py:3079-3084).  None off rank 0."""
+    idxs = np.asarray(background_idxs, dtype=np.int64).reshape(-1)
+    rows = []
+    for s in range(len(data_generator.datasets)):
+        got = latent_ranges(data_generator, model, sess_idx=s, min_p=min_p, max_p=max_p)
+        if got is None:
+            return None
+        rows.append(got['med'][idxs])
+    return np.stack(rows)
 
 
 # ------------------------------------------------------------------------------------------ reconstruction movies

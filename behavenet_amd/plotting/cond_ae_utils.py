@@ -1,5 +1,6 @@
 """Latent and label traversals with the reference's signatures (``behavenet/plotting/cond_ae_utils.py``:
-``interpolate_1d``, ``interpolate_2d``), decoded in ONE batch, the ranges they sweep (``get_input_range``,
+``interpolate_1d``, ``interpolate_2d``, ``interpolate_point_path``), decoded in ONE batch, the frames of the
+session-swap movie (``make_session_swap_movie``), tiled on the device, the ranges they sweep (``get_input_range``,
 ``compute_range``), selected on the device, the per-trial label scores of the models with supervised latents
 (``get_label_r2``) and the correlations of the unsupervised latents (``get_latent_corr``), reduced on the device, and
 the session classifier on the latents (``fit_classifier``), fitted on the device.
@@ -8,7 +9,8 @@ The reference calls ``get_reconstruction`` once per point: P launch chains of on
 Here the points are collected into one table (``fitting.eval.traversal_points``) and ``get_reconstruction`` is called
 once on it; the lists that come back have the reference's nesting and dtypes.  For an image instead of lists --
 cropped, quantised and tiled on the device, with only the uint8 result crossing to the host -- see
-``fitting.eval.traverse_latents`` and ``traversal_movie``.  Nothing here imports matplotlib."""
+``fitting.eval.traverse_latents``, ``traversal_movie`` and ``point_path_movie``.  Nothing here imports
+matplotlib."""
 
 import os
 import pickle
@@ -16,12 +18,13 @@ import pickle
 import numpy as np
 import torch
 
+from behavenet_amd.fitting import distributed as _bdist
 from behavenet_amd.fitting import eval as _eval
-from behavenet_amd.fitting.eval import get_reconstruction, traversal_points
+from behavenet_amd.fitting.eval import get_reconstruction, path_points, traversal_points
 from behavenet_amd.plotting import get_crop
 
-__all__ = ['interpolate_1d', 'interpolate_2d', 'get_input_range', 'compute_range', 'get_label_r2', 'get_latent_corr',
-           'fit_classifier']
+__all__ = ['interpolate_1d', 'interpolate_2d', 'interpolate_point_path', 'make_session_swap_movie', 'get_input_range',
+           'compute_range', 'get_label_r2', 'get_latent_corr', 'fit_classifier']
 
 _PLAIN = ('ae', 'vae', 'beta-tcvae', 'ps-vae', 'msps-vae')
 _COND = ('cond-ae', 'cond-vae')
@@ -148,6 +151,116 @@ def interpolate_1d(
     ``input_idxs[0]`` and ``input_idxs[1]``, as there."""
     return _interpolate('1d', interp_type, model, ims_0, latents_0, labels_0, labels_sc_0, mins, maxes, input_idxs,
                         n_frames, crop_type, mins_sc, maxes_sc, crop_kwargs, marker_idxs, ch)
+
+
+def interpolate_point_path(
+        interp_type, model, ims_0, labels_0, points, n_frames=10, ch=0, crop_kwargs=None,
+        apply_inverse_transform=True):
+    """Reconstructions along the path through ``points`` (n_points, D): the reference's ``interpolate_point_path``
+    (cond_ae_utils.py:733-844), what its traversal movies play, with its parameters in its order.  Every leg has
+    ``n_frames + 1`` steps, both ends included (``n_frames``: an int, or one per leg; another length is its
+    AssertionError; ``fitting.eval.path_points``).  Returns ``(ims_list, inputs_list)``: per step a float32 frame
+    ``(y_pix, x_pix)`` of channel ``ch`` -- with a non-int ``ch`` all channels next to each other, ``(y_pix, C *
+    x_pix)``; with ``crop_kwargs`` the float64 zero-filled ``get_crop`` of channel ``ch``, where a non-int ``ch`` is
+    the reference's ValueError -- and the step's point ``(1, D)`` in the dtype of ``points``.
+
+    ``'latents'``: the points are latents (``labels_0`` (1, L) goes with them for a cond-ae / cond-vae;
+    ``apply_inverse_transform`` as in ``get_reconstruction``).  ``'labels'``: the points are the transformed latents of
+    a cond-ae-msp / ps-vae / msps-vae, mapped back, or the labels of a cond-ae / cond-vae, which go with ``ims_0``,
+    repeated, through the whole model.  Where the reference calls ``get_reconstruction`` once per step, this makes ONE
+    batched call on the table.  ``hparams['conditional_encoder']`` is a NotImplementedError, as there."""
+    if model.hparams.get('conditional_encoder', False):
+        raise NotImplementedError
+    if interp_type not in ('latents', 'labels'):
+        raise NotImplementedError
+    if crop_kwargs is not None and not isinstance(ch, int):
+        raise ValueError('"ch" must be an integer to use crop_kwargs')
+    cls = model.hparams['model_class']
+    table = path_points(points, n_frames)
+    ims_list, inputs_list = [], []
+    if len(table) == 0:
+        return ims_list, inputs_list
+    if interp_type == 'latents':
+        labels = None
+        if cls in _COND:
+            labels = torch.from_numpy(np.asarray(labels_0)).float().to(_device_of(model)).expand(table.shape[0], -1)
+        ims = get_reconstruction(model, table, labels=labels, apply_inverse_transform=apply_inverse_transform)
+    elif cls in _MSP:
+        ims = get_reconstruction(model, table, apply_inverse_transform=True)
+    else:
+        ims_0 = ims_0 if torch.is_tensor(ims_0) else torch.from_numpy(np.asarray(ims_0))
+        ims_rep = ims_0.float().to(_device_of(model)).expand(table.shape[0], -1, -1, -1).contiguous()
+        ims = get_reconstruction(model, ims_rep, labels=torch.from_numpy(table).float().to(_device_of(model)))
+    for im, vec in zip(ims, table):
+        if crop_kwargs is not None:
+            ims_list.append(get_crop(
+                im[ch], crop_kwargs['y_0'], crop_kwargs['y_ext'], crop_kwargs['x_0'], crop_kwargs['x_ext']))
+        elif isinstance(ch, int):
+            ims_list.append(np.copy(im[ch]))
+        else:
+            ims_list.append(np.concatenate(list(im), axis=1))
+        inputs_list.append(np.copy(vec[None]))
+    return ims_list, inputs_list
+
+
+def make_session_swap_movie(
+        model, data_generator, n_labels, n_background, sess_idx, trials, trial_idxs=None, n_buffer_frames=5,
+        layout_pattern=None, save_file=None, max_frames=400):
+    """The frames of the reference's ``make_session_swap_movie`` (cond_ae_utils.py:3030-3156): trials of session
+    ``sess_idx`` re-rendered with every session's median background latents, one panel per session (the trial's own
+    session first), all channels side by side, ``n_buffer_frames`` black frames between trials -- a uint8 array
+    ``(T, n_rows * H, n_cols * C * W)`` (``fitting.eval.session_swap_movie``: decoded and tiled on the device).
+
+    The model and the generator are taken as they are (as ``fit_classifier`` and ``get_label_r2`` take them) instead
+    of being rebuilt from ``hparams`` and ``version``; the figure, titles and ffmpeg are not served.  The background
+    columns are ``n_labels .. n_labels + n_background - 1`` and every session's median comes from
+    ``fitting.eval.latent_ranges(..., sess_idx=s, min_p=15, max_p=85)['med']``, the reference's percentiles.
+    ``trials`` are trial numbers of the session; an entry of ``trial_idxs`` indexes its test trials
+    (``batch_idxs['test'][trial_idx]``) and is used where the entry of ``trials`` is None; one of the two lists may be
+    None.  Of every trial the first ``max_frames`` frames are taken; their latents come from
+    ``get_transformed_latents`` for a cond-ae-msp / ps-vae / msps-vae and from ``get_reconstruction(...,
+    return_latents=True)`` otherwise, and are decoded without the inverse transform, as the reference decodes them.
+    ``save_file``: the array is also written there with ``np.save``.  Under ``torch.distributed`` rank 0 alone
+    works; the other ranks return None."""
+    if _bdist.world_size() > 1 and _bdist.rank() != 0:
+        return None
+    if trial_idxs is None:
+        trial_idxs = [None] * len(trials)
+    if trials is None:
+        trials = [None] * len(trial_idxs)
+    if len(trials) != len(trial_idxs) or not len(trials):
+        raise ValueError('make_session_swap_movie: %d trials and %d trial_idxs' % (len(trials), len(trial_idxs)))
+    for trial, trial_idx in zip(trials, trial_idxs):
+        if (trial is None) == (trial_idx is None):
+            raise ValueError('make_session_swap_movie: exactly one of a trial and its trial_idx must be given, '
+                             'got %r and %r' % (trial, trial_idx))
+    n_sessions = len(data_generator.datasets)
+    _eval.swap_layout(n_sessions, sess_idx, layout_pattern)          # (a layout error before anything is encoded)
+    dataset = data_generator.datasets[sess_idx]
+    numbers = [int(dataset.batch_idxs['test'][trial_idx]) if trial is None else int(trial)
+               for trial, trial_idx in zip(trials, trial_idxs)]
+    background_idxs = np.arange(n_labels, n_labels + n_background)
+    medians = _eval.background_medians(data_generator, model, background_idxs, min_p=15, max_p=85)
+    cls = model.hparams['model_class']
+    latents = []
+    model.eval()
+    for trial in numbers:
+        batch = data_generator._sample(sess_idx, trial, 'test')          # (the trial as the generator serves it)
+        ims = batch['images'][0][:max_frames]
+        ims = ims if torch.is_tensor(ims) else torch.from_numpy(np.asarray(ims))
+        ims = (ims.float() / 255 if ims.dtype == torch.uint8 else ims).to(_device_of(model))
+        if cls in _MSP:
+            with torch.no_grad():
+                latents.append(model.get_transformed_latents(ims, dataset=sess_idx, as_numpy=True))
+        else:
+            labels = batch['labels'][0][:max_frames] if cls in _COND else None
+            latents.append(get_reconstruction(model, ims, dataset=sess_idx, labels=labels, return_latents=True)[1])
+    movie = _eval.session_swap_movie(model, latents, background_idxs, medians, sess_idx=sess_idx,
+                                     n_buffer_frames=n_buffer_frames, layout_pattern=layout_pattern,
+                                     apply_inverse_transform=False)
+    if save_file is not None:
+        np.save(save_file, movie)
+    return movie
 
 
 # ------------------------------------------------------------------------------------------ ranges

@@ -591,6 +591,26 @@ int bn_frame_mosaic_u8(const void* frames, int frames_u8, int p, int c, int h, i
                        int y_min, int x_min, int hc, int wc, const int* src, int t, int r, int cc,
                        unsigned char* out, bn_stream_t stream);
 
+/* bn_frame_mosaic_u8 with a range of channels per panel (the panels of make_session_swap_movie and
+ * make_reconstruction_movie, plotting/cond_ae_utils.py and ae_utils.py, which show concat(ims[i]): all channels
+ * of a frame side by side): out uint8 (t, r * hc, cc * n_ch * wc); panel (i, j, k) is n_ch sub-panels of wc
+ * columns, and sub-panel q shows channel ch0 + q of frame s = src[(i * r + j) * cc + k],
+ *   out[i, j * hc + y, (k * n_ch + q) * wc + x] = 0          s < 0, s >= p, y_min + y >= h or x_min + x >= w
+ *                                  = quantise(frames[s, ch0 + q, y_min + y, x_min + x])     fp32 frames
+ *                                  = frames[s, ch0 + q, y_min + y, x_min + x]               frames_u8
+ * src keeps naming frames: one index is read per panel, whatever n_ch is.  Everything else is the contract
+ * of bn_frame_mosaic_u8 -- the crop window and its zero fill, blank panels, quantise, every output byte written
+ * once by plain stores, no memset, no atomics -- and bn_frame_mosaic_u8 is this call with n_ch == 1, byte for
+ * byte.  16-byte stores where `out` and cc * n_ch * wc are multiples of 16, with four 16-byte loads
+ * (frames_u8: one) where the 16 bytes lie in one sub-panel, inside the frame and on a 16-byte boundary of the
+ * source; byte by byte otherwise, with the same values.
+ * t * r * cc == 0 returns 0 and launches nothing.  BN_E_SHAPE (nothing written): n_ch < 1, ch0 < 0,
+ * ch0 + n_ch > c, cc * n_ch * wc at 2^31 or beyond, and every refusal of bn_frame_mosaic_u8.  BN_E_BADARG: a
+ * NULL pointer (frames may be NULL when p == 0). */
+int bn_frame_mosaic_ch_u8(const void* frames, int frames_u8, int p, int c, int h, int w, int ch0, int n_ch,
+                          int y_min, int x_min, int hc, int wc, const int* src, int t, int r, int cc,
+                          unsigned char* out, bn_stream_t stream);
+
 /* The strips of a reconstruction movie in one pass (replaces the three fp32 arrays ims_orig, ims_recon and
  * 0.5 + (ims_orig - ims_recon) of make_ae_reconstruction_movie_wrapper, plotting/ae_utils.py:147-186, their
  * concat per frame and matplotlib's vmin=0, vmax=1 clip): for frame i and row y three panels of c * w bytes,
