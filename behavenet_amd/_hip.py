@@ -165,6 +165,17 @@ SIGNATURES = {
     'bn_softmax_cv_score_ws_bytes': (_c_size_t, [_c_int] * 4),
     'bn_softmax_cv_score': (_c_int, [_c_void_p, _c_int] + [_c_void_p] * 4 + [_c_int] * 4
                             + [_c_void_p] * 2 + [_c_size_t, _c_void_p]),
+    'bn_arhmm_loglik_ws_bytes': (_c_size_t, [_c_int] * 5),
+    'bn_arhmm_loglik': (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p] + [_c_int] * 5
+                        + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
+    'bn_hmm_forward_backward_ws_bytes': (_c_size_t, [_c_int] * 3),
+    'bn_hmm_forward_backward': (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 3 + [_c_void_p, _c_void_p, _c_int]
+                                + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
+    'bn_arhmm_moments_ws_bytes': (_c_size_t, [_c_int] * 5),
+    'bn_arhmm_moments': (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p] + [_c_int] * 5
+                         + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
+    'bn_hmm_viterbi_ws_bytes': (_c_size_t, [_c_int] * 3),
+    'bn_hmm_viterbi': (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 3 + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
     'bn_prof_read': (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
@@ -1482,6 +1493,200 @@ def softmax_cv_score(z, y, fold, W, leave):
                                    W.data_ptr(), leave.data_ptr(), n, D, S, M, out.data_ptr(),
                                    _arena(z.device, nbytes, 'softmax_cv'), nbytes, _stream()), 'bn_softmax_cv_score')
     return out
+
+
+# csrc/arhmm.hip's limits and the partition of bn_arhmm_moments, restated for the callers that check before a launch
+# and for the tests that have to name a row count by the plan (held against the workspace query in
+# tests/test_arhmm_cpu.py): AR_MAX_K, AR_MAX_L, AR_MAX_LD, AR_MO_MIN_ROWS, AR_MO_TARGET_BLOCKS, AR_MO_SLAB_BYTES
+ARHMM_MAX_K, ARHMM_MAX_LAGS, ARHMM_MAX_LAGGED_COLUMNS = 32, 8, 64
+_ARHMM_MIN_ROWS, _ARHMM_TARGET_BLOCKS, _ARHMM_SLAB_BYTES = 512, 1024, 60 << 20
+
+
+def _arhmm_moments_plan(n, D, L, K):
+    """``(blocks, rows)`` of ``bn_arhmm_moments``: the row blocks and the rows of a block, the last block taking what
+    is left (ar_plan); K partial matrices (P, P) a block fit into 60 MiB."""
+    if n < 1:
+        return 0, 1
+    P = 1 + (L + 1) * D
+    cap = min(_ARHMM_SLAB_BYTES // (K * P * P * 8), _ARHMM_TARGET_BLOCKS)
+    want = min(-(-n // _ARHMM_MIN_ROWS), cap)
+    rows = -(-n // want)
+    return -(-n // rows), rows
+
+
+def _arhmm_moments_group(D, L):
+    """The states a workgroup of ``bn_arhmm_moments`` takes with one staging of its rows (ar_mo_group): 4 up to 32
+    columns of ``a_t``, 2 up to 64, 1 beyond."""
+    P = 1 + (L + 1) * D
+    return 4 if P <= 32 else (2 if P <= 64 else 1)
+
+
+def check_arhmm_dims(who, D, L, K):
+    """ValueError unless (D, L, K) are dimensions the ARHMM kernels serve."""
+    if not 1 <= K <= ARHMM_MAX_K:
+        raise ValueError('%s: %d states (1 to %d are served)' % (who, K, ARHMM_MAX_K))
+    if not 0 <= L <= ARHMM_MAX_LAGS:
+        raise ValueError('%s: %d lags (0 to %d are served)' % (who, L, ARHMM_MAX_LAGS))
+    if D < 1 or (L + 1) * D > ARHMM_MAX_LAGGED_COLUMNS:
+        raise ValueError('%s: %d columns at %d lags, (lags + 1) * columns = %d (1 to %d are served)'
+                         % (who, D, L, (L + 1) * D, ARHMM_MAX_LAGGED_COLUMNS))
+
+
+def _f64_operand(who, name, x, shape, device, allow_none=False):
+    """``x`` as a contiguous float64 tensor of ``shape`` on ``device``: a host array is uploaded, a tensor must be
+    float64 and on the device already."""
+    if x is None:
+        if allow_none:
+            return None
+        raise ValueError('%s: %s is None' % (who, name))
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float64)).to(device)
+    if x.dtype != torch.float64 or tuple(x.shape) != tuple(shape):
+        raise ValueError('%s: expected %s float64 %s, got %s %s' % (who, name, tuple(shape), x.dtype, tuple(x.shape)))
+    if x.device != device:
+        raise ValueError('%s: the table is on %s, %s on %s (the HIP path has no CPU fallback)'
+                         % (who, device, name, x.device))
+    return x.contiguous()
+
+
+def _trial_offsets(who, offsets, device):
+    if not torch.is_tensor(offsets):
+        offsets = torch.from_numpy(np.ascontiguousarray(np.asarray(offsets), dtype=np.int64)).to(device)
+    if offsets.dim() != 1 or offsets.dtype != torch.int64 or offsets.numel() < 1:
+        raise ValueError('%s: expected offsets int64 (S + 1,), got %s %s' % (who, offsets.dtype, tuple(offsets.shape)))
+    if offsets.device != device:
+        raise ValueError('%s: the table is on %s, offsets on %s (the HIP path has no CPU fallback)'
+                         % (who, device, offsets.device))
+    return offsets.contiguous()
+
+
+def _ll_table(who, ll):
+    """(n, K) of a table of log-likelihoods: float64, contiguous, on the GPU, 1 <= K <= 32."""
+    if not torch.is_tensor(ll) or ll.dim() != 2 or ll.dtype != torch.float64:
+        raise ValueError('%s: expected ll float64 (n, K), got %s'
+                         % (who, (ll.dtype, tuple(ll.shape)) if torch.is_tensor(ll) else type(ll).__name__))
+    n, K = (int(v) for v in ll.shape)
+    if not 1 <= K <= ARHMM_MAX_K:
+        raise ValueError('%s: %d states (1 to %d are served)' % (who, K, ARHMM_MAX_K))
+    if not ll.is_cuda:
+        raise ValueError('%s: expected ll on the GPU, got device %s (the HIP path has no CPU fallback)'
+                         % (who, ll.device))
+    if not ll.is_contiguous():
+        raise ValueError('%s: ll must be contiguous, got strides %s' % (who, tuple(ll.stride())))
+    return n, K
+
+
+def arhmm_loglik(table, offsets, G, cst, lags, shift=None, out=None):
+    """Emission log-likelihoods of an ARHMM on the fp32 DEVICE ``table`` (n, D): a float64 device tensor (n, K)
+    (``bn_arhmm_loglik``, csrc/arhmm.hip).  ``offsets``: int64 (S + 1), the trials; ``G`` float64 (K, D, P) and ``cst``
+    (K), the folded parameters (``models.arhmm.ARHMM.fold``), P = 1 + (lags + 1) D; ``shift``: None or D float64 values.
+    Host arrays are uploaded.  Row t of a trial with t < lags gets the standard normal density of the row for every
+    state.  Rows outside the trials are left as they are (zeros in a fresh ``out``)."""
+    n, D, ld = _column_table('arhmm_loglik', table)
+    L = int(lags)
+    if not torch.is_tensor(G) and np.ndim(G) != 3 or torch.is_tensor(G) and G.dim() != 3:
+        raise ValueError('arhmm_loglik: expected G float64 (K, D, P)')
+    K = int(G.shape[0])
+    check_arhmm_dims('arhmm_loglik', D, L, K)
+    P = 1 + (L + 1) * D
+    dev = table.device
+    G = _f64_operand('arhmm_loglik', 'G', G, (K, D, P), dev)
+    cst = _f64_operand('arhmm_loglik', 'cst', cst, (K,), dev)
+    shift = _f64_operand('arhmm_loglik', 'shift', shift, (D,), dev, allow_none=True)
+    offsets = _trial_offsets('arhmm_loglik', offsets, dev)
+    S = int(offsets.numel()) - 1
+    if out is None:
+        out = torch.zeros((n, K), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (n, K) or out.device != dev or not out.is_contiguous():
+        raise ValueError('arhmm_loglik: expected out float64 (%d, %d) on %s' % (n, K, dev))
+    lib = load()
+    nbytes = lib.bn_arhmm_loglik_ws_bytes(n, S, D, L, K)
+    if S:
+        _check(lib.bn_arhmm_loglik(table.data_ptr(), ld, None if shift is None else shift.data_ptr(),
+                                   offsets.data_ptr(), S, D, L, K, n, G.data_ptr(), cst.data_ptr(), out.data_ptr(),
+                                   _arena(dev, nbytes, 'arhmm'), nbytes, _stream()), 'bn_arhmm_loglik')
+    return out
+
+
+def hmm_forward_backward(ll, offsets, log_Ps, log_pi0, want_posteriors=True, gamma=None, xi=None):
+    """Forward-backward per trial over the float64 DEVICE table ``ll`` (n, K) of log-likelihoods
+    (``bn_hmm_forward_backward``): ``(gamma, xi, loglik)`` -- the state marginals (n, K), per trial the summed pairwise
+    posteriors (S, K, K) and the log-likelihood (S,), float64 device tensors.  ``want_posteriors=False`` runs the
+    forward sweep alone and returns ``(None, None, loglik)``; a ``gamma`` / ``xi`` given then is not touched.
+    ``log_Ps`` (K, K) and ``log_pi0`` (K): float64, host arrays are uploaded."""
+    n, K = _ll_table('hmm_forward_backward', ll)
+    dev = ll.device
+    log_Ps = _f64_operand('hmm_forward_backward', 'log_Ps', log_Ps, (K, K), dev)
+    log_pi0 = _f64_operand('hmm_forward_backward', 'log_pi0', log_pi0, (K,), dev)
+    offsets = _trial_offsets('hmm_forward_backward', offsets, dev)
+    S = int(offsets.numel()) - 1
+    loglik = torch.empty((S,), dtype=torch.float64, device=dev)
+    want = 1 if want_posteriors else 0
+    if want:
+        if gamma is None:
+            gamma = torch.zeros((n, K), dtype=torch.float64, device=dev)
+        if xi is None:
+            xi = torch.empty((S, K, K), dtype=torch.float64, device=dev)
+        for name, t, shape in (('gamma', gamma, (n, K)), ('xi', xi, (S, K, K))):
+            if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+                raise ValueError('hmm_forward_backward: expected %s float64 %s on %s' % (name, shape, dev))
+    lib = load()
+    nbytes = lib.bn_hmm_forward_backward_ws_bytes(n, S, K)
+    if S:
+        _check(lib.bn_hmm_forward_backward(ll.data_ptr(), offsets.data_ptr(), S, K, n, log_Ps.data_ptr(),
+                                           log_pi0.data_ptr(), want, gamma.data_ptr() if want else None,
+                                           xi.data_ptr() if want else None, loglik.data_ptr(),
+                                           _arena(dev, nbytes, 'arhmm'), nbytes, _stream()),
+               'bn_hmm_forward_backward')
+    return (gamma, xi, loglik) if want else (None, None, loglik)
+
+
+def arhmm_moments(table, offsets, gamma, lags, shift=None):
+    """Weighted lagged moments of the fp32 DEVICE ``table`` (n, D): ``(out, gamma0)``, float64 device tensors
+    (K, P, P) and (K,) (``bn_arhmm_moments``).  ``out[k]`` is the sum over the AR rows of ``gamma[t, k] a_t^T a_t`` with
+    ``a_t = (1, x_t - shift, ..., x_{t-lags} - shift)``, ``gamma0[k]`` the sum of ``gamma[t, k]`` over the first
+    ``lags`` rows of every trial.  ``gamma``: float64 DEVICE (n, K)."""
+    n, D, ld = _column_table('arhmm_moments', table)
+    L = int(lags)
+    if not torch.is_tensor(gamma) or gamma.dim() != 2:
+        raise ValueError('arhmm_moments: expected gamma float64 (n, K) on the device')
+    K = int(gamma.shape[1])
+    check_arhmm_dims('arhmm_moments', D, L, K)
+    dev = table.device
+    gamma = _f64_operand('arhmm_moments', 'gamma', gamma, (n, K), dev)
+    shift = _f64_operand('arhmm_moments', 'shift', shift, (D,), dev, allow_none=True)
+    offsets = _trial_offsets('arhmm_moments', offsets, dev)
+    S = int(offsets.numel()) - 1
+    P = 1 + (L + 1) * D
+    out = torch.empty((K, P, P), dtype=torch.float64, device=dev)
+    gamma0 = torch.empty((K,), dtype=torch.float64, device=dev)
+    if not S:
+        return out.zero_(), gamma0.zero_()
+    lib = load()
+    nbytes = lib.bn_arhmm_moments_ws_bytes(n, S, D, L, K)
+    _check(lib.bn_arhmm_moments(table.data_ptr(), ld, None if shift is None else shift.data_ptr(), offsets.data_ptr(),
+                                S, D, L, K, n, gamma.data_ptr(), out.data_ptr(), gamma0.data_ptr(),
+                                _arena(dev, nbytes, 'arhmm'), nbytes, _stream()), 'bn_arhmm_moments')
+    return out, gamma0
+
+
+def hmm_viterbi(ll, offsets, log_Ps, log_pi0):
+    """The most likely state path of every trial over the float64 DEVICE table ``ll`` (n, K): an int32 device tensor
+    (n,) (``bn_hmm_viterbi``); a tie goes to the lowest state.  Rows outside the trials read 0."""
+    n, K = _ll_table('hmm_viterbi', ll)
+    dev = ll.device
+    log_Ps = _f64_operand('hmm_viterbi', 'log_Ps', log_Ps, (K, K), dev)
+    log_pi0 = _f64_operand('hmm_viterbi', 'log_pi0', log_pi0, (K,), dev)
+    offsets = _trial_offsets('hmm_viterbi', offsets, dev)
+    S = int(offsets.numel()) - 1
+    states = torch.zeros((n,), dtype=torch.int32, device=dev)
+    lib = load()
+    nbytes = lib.bn_hmm_viterbi_ws_bytes(n, S, K)
+    if S:
+        _check(lib.bn_hmm_viterbi(ll.data_ptr(), offsets.data_ptr(), S, K, n, log_Ps.data_ptr(), log_pi0.data_ptr(),
+                                  states.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes, _stream()),
+               'bn_hmm_viterbi')
+    return states
 
 
 def recon_panels_u8(orig, recon, mask=None, show_orig=True, out=None, row=0, n_rows=1):

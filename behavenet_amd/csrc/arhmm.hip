@@ -1,0 +1,671 @@
+// EM for autoregressive hidden Markov models on a table of latents ("ARHMM"): the four launches
+// of one EM iteration and of the state export.  The table z is fp32 (n, D); everything else is float64.  The rows are
+// cut into trials by offsets made safe as segment_sums.hip makes them (bn_launch_segment_offsets: clamped into [0, n]
+// and non-decreasing); rows outside [e[0], e[S]) belong to no trial and are neither read nor written by any launch.
+// Row t of a trial (counted from the trial's first row) is an INITIAL row if t < L and an AR row otherwise; for an AR
+// row
+//
+//   a_t = (1, x_t - c, x_{t-1} - c, ..., x_{t-L} - c)        float64, P = 1 + (L + 1) D entries, c the shift or zeros
+//
+// k_ar_kind      one byte a row: 0 outside the trials, 1 initial, 2 AR (a binary search in the offsets a row; the
+//                staging loops of the two table kernels read the byte, not the offsets)
+// k_ar_loglik    ll[t][k] = cst[k] - 1/2 |G_k a_t|^2 for AR rows: the (n x P) (P x K D) product on
+//                v_mfma_f64_16x16x4_f64.  A wave takes 32 rows (two row tiles of 16, staged in LDS as float64 rows
+//                a_t, zeros for the rows that are not AR rows and for the padding of P to a multiple of four).  The
+//                tile COLUMNS are states (16 a tile) and the D output dimensions are taken one after the other: the
+//                MFMA chain over P for dimension d leaves (G_k a_t)[d] for 16 rows x 16 states, which is squared and
+//                added into the lane's own four sums -- the squared norm over D needs no cross-lane step.  B comes
+//                straight from G (at most 1 MiB, resident in L2).  Initial rows: -D/2 log 2 pi - 1/2 |x_t|^2 for
+//                every state, one lane a row.  A NaN in row t is in the staged rows a_t .. a_{t+L} of its trial and
+//                nowhere else, and a row of A reaches its own row of the product only.
+// k_hmm_fb       forward-backward, one wave (one workgroup of 64) a trial.  Lane j is state j; it keeps column j of
+//                P = exp(logP) in registers for the forward sweep and row j for the backward sweep.  The K values of
+//                the step before reach every lane through LDS: one write, one barrier, K broadcast reads (double
+//                buffered, so one barrier a step).  Scaled recursion: b_t = exp(ll_t - max_k ll_t), u_t[j] =
+//                sum_i ahat_{t-1}[i] P[i][j] b_t[j], s_t = sum_j u_t[j], ahat_t = u_t / s_t and
+//                loglik = sum_t (log s_t + max_t); the division by s_t is done by the readers of the next step (they
+//                sum the K values they read anyway), and log s_t is taken once per 64 steps: lane (t & 63) keeps s_t
+//                and all lanes take one log when the 64 are full.  Row maximum and exp of row t + 1 are formed
+//                during step t and row t + 2 is asked for then, in both sweeps.  gamma's storage holds ahat between the sweeps; the
+//                workspace holds (s_t, max_t) a row.  Backward: v_t[j] = b_t[j] bhat_t[j] / s_t, bhat_t[i] =
+//                sum_j P[i][j] v_{t+1}[j], xi += ahat_t[i] P[i][j] v_{t+1}[j] and gamma_t = ahat_t bhat_t, divided
+//                by its own sum over the states (read from LDS with v).  The sums over states run in state order in
+//                four interleaved accumulators: the same bits on every call.
+// k_ar_moments   out[k] = sum_t gamma[t][k] a_t^T a_t over the AR rows: segment_gram.hip's scheme (32 staged rows,
+//                four waves taking the k-steps in turn, tiles with ti <= tj only and mirrored on the way out) with
+//                the weight folded into the A fragment.  The grid is (row blocks, state groups): a workgroup stages
+//                its rows ONCE for a group of 4, 2 or 1 states (by the registers 2 TB (TB + 1) accumulators a state
+//                leave) and leaves one (P, P) partial a state, k_ar_combine adds the partials in block order.  The 1
+//                of a_t is a column of the product like the others, so out[k][0][0] is the sum of the weights.
+// k_ar_gamma0    the sum of gamma over the initial rows, one workgroup a state, in (thread, trial) order.
+// k_hmm_viterbi  max-sum, one wave a trial, the lane layout of k_hmm_fb; uint8 back-pointers (n, K) in the workspace;
+//                a tie goes to the lowest state (strict > in ascending order).  The walk back runs on lane 0 over
+//                64 rows of back-pointers at a time, copied into LDS by the whole wave.
+// No global atomics; every output element is written exactly once.
+#include <math.h>
+#include "bn_common.h"
+#include "bn_launch.h"
+
+#define AR_MAX_K 32
+#define AR_MAX_L 8
+#define AR_MAX_LD 64                        // (L + 1) D at most
+#define AR_LL_THREADS 128                   // k_ar_loglik: two waves ...
+#define AR_LL_WAVES (AR_LL_THREADS / BN_WAVE)
+#define AR_LL_ROWS 32                       // ... of 32 rows (two row tiles) each
+#define AR_LL_LW 72                         // doubles a staged row at most: P <= 65 padded to 68, plus 4
+#define AR_MO_THREADS 256
+#define AR_MO_WAVES (AR_MO_THREADS / BN_WAVE)
+#define AR_MO_ROWS 32                       // rows of a staged chunk: eight k-steps of four rows, two a wave
+#define AR_MO_MIN_ROWS 512                  // rows a row block holds at least (but for the last)
+#define AR_MO_TARGET_BLOCKS 1024            // row blocks at most ...
+#define AR_MO_SLAB_BYTES (60u << 20)        // ... and no more than fit K partials each into 60 MiB
+#define AR_BT_ROWS 64                       // rows of back-pointers the walk back holds in LDS
+
+typedef double ar_d4 __attribute__((ext_vector_type(4)));
+
+struct ArPlan {
+    int blocks;       // row blocks
+    int rows;         // rows per block (the last block takes what is left)
+};
+
+static bool ar_dims_ok(int D, int L, int K) {
+    return K >= 1 && K <= AR_MAX_K && L >= 0 && L <= AR_MAX_L && D >= 1 && (L + 1) * (long)D <= AR_MAX_LD;
+}
+
+// the ONE partition of k_ar_moments the workspace query, the launch and the combine go by
+static ArPlan ar_plan(int n, int D, int L, int K) {
+    ArPlan p;
+    if (n < 1) {
+        p.blocks = 0;
+        p.rows = 1;
+        return p;
+    }
+    const long P = 1 + (long)(L + 1) * D;
+    const long by_bytes = AR_MO_SLAB_BYTES / ((long)K * P * P * (long)sizeof(double));       // 58 at K = 32, P = 65
+    const long cap = by_bytes < AR_MO_TARGET_BLOCKS ? by_bytes : AR_MO_TARGET_BLOCKS;
+    const long by_rows = ((long)n + AR_MO_MIN_ROWS - 1) / AR_MO_MIN_ROWS;
+    const long want = by_rows < cap ? by_rows : cap;
+    p.rows = (int)(((long)n + want - 1) / want);
+    p.blocks = (int)(((long)n + p.rows - 1) / p.rows);
+    return p;
+}
+
+static size_t ar_pad16(size_t b) { return (b + 15) & ~(size_t)15; }
+static size_t ar_offsets_bytes(int S) { return ar_pad16(((size_t)S + 1) * sizeof(int)); }
+
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ar_kind(const int* __restrict__ e, int S, int L, int n,
+                                                 unsigned char* __restrict__ kind) {
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    unsigned char v = 0;
+    if (r >= e[0] && r < e[S]) {
+        int lo = 0, hi = S - 1;                            // the first trial that ends after r
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (e[mid + 1] > r) hi = mid; else lo = mid + 1;
+        }
+        v = r - e[lo] < L ? 1 : 2;
+    }
+    kind[r] = v;
+}
+
+// the staged entry p of a_t for the AR row `row` (p < P)
+__device__ __forceinline__ double ar_entry(const float* __restrict__ z, int ld, const double* shift, int D, long row,
+                                           int p) {
+    if (p == 0) return 1.0;
+    const int q = p - 1, lag = q / D, j = q - lag * D;
+    return (double)z[(size_t)(row - lag) * ld + j] - shift[j];
+}
+
+__global__ __launch_bounds__(AR_LL_THREADS) void k_ar_loglik(const float* __restrict__ z, int ld,
+                                                             const double* __restrict__ c,
+                                                             const unsigned char* __restrict__ kind, int D, int L,
+                                                             int K, int n, const double* __restrict__ G,
+                                                             const double* __restrict__ cst, double* __restrict__ ll) {
+    __shared__ double stage[AR_LL_WAVES][AR_LL_ROWS * AR_LL_LW];
+    __shared__ double shift[AR_MAX_LD];
+    const int tid = threadIdx.x, lane = tid & (BN_WAVE - 1), wave = tid / BN_WAVE;
+    const int kk = lane >> 4, col = lane & 15;
+    const int P = 1 + (L + 1) * D, PP = (P + 3) & ~3, LW = PP + 4, KS = PP >> 2;
+    const long row0 = ((long)blockIdx.x * AR_LL_WAVES + wave) * AR_LL_ROWS;
+    double* st = stage[wave];
+
+    if (tid < D) shift[tid] = c ? c[tid] : 0.0;
+    __syncthreads();
+    for (int idx = lane; idx < AR_LL_ROWS * PP; idx += BN_WAVE) {
+        const int r = idx / PP, p = idx - r * PP;
+        const long row = row0 + r;
+        double v = 0.0;
+        if (row < n && p < P && kind[row] == 2) v = ar_entry(z, ld, shift, D, row, p);
+        st[r * LW + p] = v;
+    }
+    __syncthreads();
+
+    for (int kt = 0; kt * 16 < K; ++kt) {
+        const int state = kt * 16 + col;
+        const bool live = state < K;
+        ar_d4 q0 = {0.0, 0.0, 0.0, 0.0}, q1 = {0.0, 0.0, 0.0, 0.0};
+        for (int d = 0; d < D; ++d) {
+            const double* g = G + ((size_t)(live ? state : 0) * D + d) * P;
+            ar_d4 c0 = {0.0, 0.0, 0.0, 0.0}, c1 = {0.0, 0.0, 0.0, 0.0};
+            for (int ks = 0; ks < KS; ++ks) {
+                const int p = 4 * ks + kk;
+                // A: row `col` of the tile, entry p; B: entry p of row d of G_state
+                const double b = live && p < P ? g[p] : 0.0;
+                const double a0 = st[col * LW + p], a1 = st[(16 + col) * LW + p];
+                c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, c0, 0, 0, 0);
+                c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, c1, 0, 0, 0);
+            }
+            q0 += c0 * c0;
+            q1 += c1 * c1;
+        }
+        // C/D of the f64 MFMA: column lane & 15 (the state), row (lane >> 4) + 4 * reg
+        if (live) {
+            const double cs = cst[state];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long ra = row0 + kk + 4 * r, rb = ra + 16;
+                if (ra < n && kind[ra] == 2) ll[(size_t)ra * K + state] = cs - 0.5 * q0[r];
+                if (rb < n && kind[rb] == 2) ll[(size_t)rb * K + state] = cs - 0.5 * q1[r];
+            }
+        }
+    }
+    // the initial rows: the standard normal density of the row, the same for every state
+    if (lane < AR_LL_ROWS) {
+        const long row = row0 + lane;
+        if (row < n && kind[row] == 1) {
+            double s = 0.0;
+            for (int j = 0; j < D; ++j) {
+                const double x = (double)z[(size_t)row * ld + j];
+                s += x * x;
+            }
+            const double v = -0.5 * D * 1.8378770664093453 - 0.5 * s;          // log 2 pi
+            for (int k = 0; k < K; ++k) ll[(size_t)row * K + k] = v;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double ar_wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+
+__device__ __forceinline__ double ar_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+template <int KP>
+__global__ __launch_bounds__(BN_WAVE) void k_hmm_fb(const double* __restrict__ ll, const int* __restrict__ e, int K,
+                                                    const double* __restrict__ logP,
+                                                    const double* __restrict__ logpi0, int want,
+                                                    double* __restrict__ gamma, double* __restrict__ xi,
+                                                    double* __restrict__ loglik, double* __restrict__ cm) {
+    __shared__ __attribute__((aligned(16))) double buf[2][2][KP];              // [parity][v or g][state]
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int beg = e[s], T = e[s + 1] - beg;
+    const bool active = lane < K, writer = lane < KP;
+    if (T <= 0) {
+        if (lane == 0) loglik[s] = 0.0;
+        if (want)
+            for (int o = lane; o < K * K; o += BN_WAVE) xi[(size_t)s * K * K + o] = 0.0;
+        return;
+    }
+    const double* l = ll + (size_t)beg * K;
+    double* gam = gamma + (size_t)beg * K;
+    double* cmt = cm + (size_t)beg * 2;
+    const double ninf = -INFINITY;
+
+    double Pc[KP];
+#pragma unroll
+    for (int i = 0; i < KP; ++i) Pc[i] = active && i < K ? exp(logP[i * K + lane]) : 0.0;
+    const double pi = active ? exp(logpi0[lane]) : 0.0;
+
+    double lsum = 0.0, msum = 0.0, pend = 1.0, dot = 0.0;
+    // the row maximum and exp of row t + 1 are formed during step t and the row t + 2 is asked for then: only
+    // u -> LDS -> sums -> division is on the chain from step to step
+    double m, b;
+    {
+        const double lv = active ? l[lane] : ninf;
+        m = ar_wave_max(lv);
+        b = active ? exp(lv - m) : 0.0;
+    }
+    double l1 = active && T > 1 ? l[(size_t)K + lane] : ninf;
+    for (int t = 0; t < T; ++t) {
+        const double l2 = active && t + 2 < T ? l[(size_t)(t + 2) * K + lane] : ninf;
+        const double u = t == 0 ? pi * b : dot * b;
+        const int par = t & 1;
+        if (writer) buf[par][0][lane] = u;
+        __syncthreads();
+        const double mn = ar_wave_max(l1);
+        const double bn = active ? exp(l1 - mn) : 0.0;     // (row T: -inf - -inf, a NaN nobody reads)
+        double s4[4] = {0.0, 0.0, 0.0, 0.0}, d4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int i = 0; i < KP; ++i) {
+            const double ui = buf[par][0][i];
+            s4[i & 3] += ui;
+            d4[i & 3] += ui * Pc[i];
+        }
+        const double st = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+        const double inv = 1.0 / st;
+        dot = ((d4[0] + d4[1]) + (d4[2] + d4[3])) * inv;
+        if (want) {
+            if (active) gam[(size_t)t * K + lane] = u * inv;
+            if (lane == 0) {
+                cmt[2 * (size_t)t] = st;
+                cmt[2 * (size_t)t + 1] = m;
+            }
+        }
+        msum += m;
+        pend = lane == (t & 63) ? st : pend;
+        if ((t & 63) == 63) {
+            lsum += log(pend);
+            pend = 1.0;
+        }
+        m = mn;
+        b = bn;
+        l1 = l2;
+    }
+    lsum += log(pend);
+    const double total = ar_wave_sum(lsum) + msum;
+    if (lane == 0) loglik[s] = total;
+    if (!want) return;
+
+    // ---- backward: gamma holds ahat, cm holds (s_t, max_t); lane i is the SOURCE state now
+    __syncthreads();                                       // (cm, written by lane 0, is read by every lane)
+    double Pr[KP], acc[KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        Pr[j] = active && j < K ? exp(logP[lane * K + j]) : 0.0;
+        acc[j] = 0.0;
+    }
+    int par = 0;
+    {
+        const int t = T - 1;
+        const double b = active ? exp(l[(size_t)t * K + lane] - cmt[2 * (size_t)t + 1]) : 0.0;
+        if (writer) buf[par][0][lane] = b / cmt[2 * (size_t)t];
+        __syncthreads();
+    }
+    // row t's ahat and b_t / s_t are ready when step t begins: b_{t-1} / s_{t-1} is formed during step t from the
+    // values asked for during step t + 1, and row t - 2 is asked for
+    double a = 0.0, bq = 0.0, a1 = 0.0, q1 = ninf, s1 = 1.0, m1 = 0.0;
+    if (T >= 2) {
+        const size_t t = T - 2;
+        a = active ? gam[t * K + lane] : 0.0;
+        bq = active ? exp(l[t * K + lane] - cmt[2 * t + 1]) / cmt[2 * t] : 0.0;
+    }
+    if (T >= 3) {
+        const size_t t = T - 3;
+        a1 = active ? gam[t * K + lane] : 0.0;
+        q1 = active ? l[t * K + lane] : ninf;
+        s1 = cmt[2 * t];
+        m1 = cmt[2 * t + 1];
+    }
+    for (int t = T - 2; t >= 0; --t) {
+        double a2 = 0.0, q2 = ninf, s2 = 1.0, m2 = 0.0;
+        if (t > 1) {
+            const size_t r = t - 2;
+            a2 = active ? gam[r * K + lane] : 0.0;
+            q2 = active ? l[r * K + lane] : ninf;
+            s2 = cmt[2 * r];
+            m2 = cmt[2 * r + 1];
+        }
+        const double bq1 = active ? exp(q1 - m1) / s1 : 0.0;
+        double b4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            const double pv = Pr[j] * buf[par][0][j];
+            b4[j & 3] += pv;
+            acc[j] += a * pv;
+        }
+        const double beta = (b4[0] + b4[1]) + (b4[2] + b4[3]);
+        const double g = a * beta;
+        par ^= 1;
+        if (writer) {
+            buf[par][0][lane] = bq * beta;
+            buf[par][1][lane] = g;
+        }
+        __syncthreads();
+        double z4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int i = 0; i < KP; ++i) z4[i & 3] += buf[par][1][i];
+        const double Z = (z4[0] + z4[1]) + (z4[2] + z4[3]);
+        if (active) gam[(size_t)t * K + lane] = g / Z;
+        a = a1;
+        bq = bq1;
+        a1 = a2;
+        q1 = q2;
+        s1 = s2;
+        m1 = m2;
+    }
+    if (active) {
+#pragma unroll
+        for (int j = 0; j < KP; ++j)
+            if (j < K) xi[((size_t)s * K + lane) * K + j] = acc[j];
+    }
+}
+
+template <int KP>
+__global__ __launch_bounds__(BN_WAVE) void k_hmm_viterbi(const double* __restrict__ ll, const int* __restrict__ e,
+                                                         int K, const double* __restrict__ logP,
+                                                         const double* __restrict__ logpi0, int* __restrict__ states,
+                                                         unsigned char* __restrict__ bp) {
+    __shared__ __attribute__((aligned(16))) double buf[2][KP];
+    __shared__ unsigned char chunk[AR_BT_ROWS * AR_MAX_K];
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int beg = e[s], T = e[s + 1] - beg;
+    if (T <= 0) return;
+    const bool active = lane < K, writer = lane < KP;
+    const double ninf = -INFINITY;
+    const double* l = ll + (size_t)beg * K;
+    unsigned char* back = bp + (size_t)beg * K;
+    int* out = states + beg;
+
+    double Pc[KP];
+#pragma unroll
+    for (int i = 0; i < KP; ++i) Pc[i] = active && i < K ? logP[i * K + lane] : ninf;
+    double delta = active ? logpi0[lane] + l[lane] : ninf;
+    double lv = active && T > 1 ? l[(size_t)K + lane] : ninf;
+    for (int t = 1; t < T; ++t) {
+        const double lnext = active && t + 1 < T ? l[(size_t)(t + 1) * K + lane] : ninf;
+        const int par = t & 1;
+        if (writer) buf[par][lane] = delta;
+        __syncthreads();
+        double best = buf[par][0] + Pc[0];
+        int arg = 0;
+#pragma unroll
+        for (int i = 1; i < KP; ++i) {
+            const double v = buf[par][i] + Pc[i];
+            if (v > best) {
+                best = v;
+                arg = i;
+            }
+        }
+        if (active) back[(size_t)t * K + lane] = (unsigned char)arg;
+        delta = best + lv;
+        lv = lnext;
+    }
+    const int par = T & 1;
+    if (writer) buf[par][lane] = delta;
+    __syncthreads();                                       // (and the back-pointers are visible to the wave)
+    int cur = 0;
+    {
+        double best = buf[par][0];
+        for (int j = 1; j < K; ++j)
+            if (buf[par][j] > best) {
+                best = buf[par][j];
+                cur = j;
+            }
+    }
+    for (int hi = T; hi > 0; hi -= AR_BT_ROWS) {
+        const int lo = hi > AR_BT_ROWS ? hi - AR_BT_ROWS : 0;
+        __syncthreads();                                   // (the chunk before this one has been walked)
+        for (int idx = lane; idx < (hi - lo) * K; idx += BN_WAVE) {
+            const size_t o = (size_t)lo * K + idx;
+            chunk[idx] = o >= (size_t)K ? back[o] : 0;     // (row 0 has no back-pointers)
+        }
+        __syncthreads();
+        if (lane == 0) {
+            for (int t = hi - 1; t >= lo; --t) {
+                out[t] = cur;
+                if (t > 0) cur = chunk[(t - lo) * K + cur];
+            }
+        }
+        cur = __shfl(cur, 0);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// states a workgroup of k_ar_moments takes with ONE staging of its rows (the accumulators of a state are
+// 2 TB (TB + 1) registers a lane; at TB = 3 four states measured slower than two: one wave a SIMD)
+__host__ __device__ constexpr int ar_mo_group(int TB) { return TB <= 2 ? 4 : (TB <= 4 ? 2 : 1); }
+
+template <int TB>
+__global__ __launch_bounds__(AR_MO_THREADS) void k_ar_moments(const float* __restrict__ z, int ld,
+                                                              const double* __restrict__ c,
+                                                              const unsigned char* __restrict__ kind,
+                                                              const double* __restrict__ gamma, int D, int L, int K,
+                                                              int n, int rows, double* __restrict__ slabs) {
+    constexpr int PT = 16 * TB, LW = PT + 4, NT = TB * (TB + 1) / 2, SG = ar_mo_group(TB);
+    __shared__ double stage[AR_MO_ROWS * LW];
+    __shared__ double wgt[SG][AR_MO_ROWS];
+    __shared__ double red[AR_MO_WAVES - 1][4 * BN_WAVE];
+    __shared__ double shift[AR_MAX_LD];
+    const int tid = threadIdx.x, lane = tid & (BN_WAVE - 1), wave = tid / BN_WAVE;
+    const int kk = lane >> 4, col = lane & 15;
+    const int P = 1 + (L + 1) * D, k0 = blockIdx.y * SG;
+    const long row0 = (long)blockIdx.x * rows;
+    const long row1 = n - row0 > rows ? row0 + rows : n;
+
+    if (tid < D) shift[tid] = c ? c[tid] : 0.0;
+    ar_d4 acc[SG][NT];
+#pragma unroll
+    for (int g = 0; g < SG; ++g)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[g][t] = ar_d4{0.0, 0.0, 0.0, 0.0};
+    for (long r0 = row0; r0 < row1; r0 += AR_MO_ROWS) {
+        __syncthreads();                                   // (the chunk before this one has been read; shift is there)
+        for (int idx = tid; idx < AR_MO_ROWS * PT; idx += AR_MO_THREADS) {
+            const int r = idx / PT, p = idx - r * PT;
+            const long row = r0 + r;
+            double v = 0.0;
+            if (row < row1 && p < P && kind[row] == 2) v = ar_entry(z, ld, shift, D, row, p);
+            stage[r * LW + p] = v;
+        }
+        if (tid < AR_MO_ROWS * SG) {
+            const int g = tid / AR_MO_ROWS, r = tid - g * AR_MO_ROWS;
+            const long row = r0 + r;
+            wgt[g][r] = k0 + g < K && row < row1 && kind[row] == 2 ? gamma[(size_t)row * K + k0 + g] : 0.0;
+        }
+        __syncthreads();
+        for (int ks = wave; ks < AR_MO_ROWS / 4; ks += AR_MO_WAVES) {
+            double frag[TB];
+#pragma unroll
+            for (int q = 0; q < TB; ++q) frag[q] = stage[(4 * ks + kk) * LW + 16 * q + col];
+#pragma unroll
+            for (int g = 0; g < SG; ++g) {
+                const double w = wgt[g][4 * ks + kk];
+                double wf[TB];
+#pragma unroll
+                for (int q = 0; q < TB; ++q) wf[q] = w * frag[q];
+                int t = 0;
+#pragma unroll
+                for (int ti = 0; ti < TB; ++ti)
+#pragma unroll
+                    for (int tj = ti; tj < TB; ++tj, ++t)
+                        acc[g][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wf[ti], frag[tj], acc[g][t], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < SG; ++g) {
+        if (k0 + g >= K) break;                            // (the same for the whole workgroup)
+        double* dst = slabs + ((size_t)blockIdx.x * K + k0 + g) * P * P;
+        int t = 0;
+#pragma unroll
+        for (int ti = 0; ti < TB; ++ti)
+#pragma unroll
+            for (int tj = ti; tj < TB; ++tj, ++t) {
+                __syncthreads();                           // (red has been read)
+                if (wave) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) red[wave - 1][r * BN_WAVE + lane] = acc[g][t][r];
+                }
+                __syncthreads();
+                if (!wave) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        double v = acc[g][t][r];
+#pragma unroll
+                        for (int w = 0; w < AR_MO_WAVES - 1; ++w) v += red[w][r * BN_WAVE + lane];
+                        const int i = 16 * ti + kk + 4 * r, j = 16 * tj + col;
+                        if (i <= j && j < P) {             // (the upper triangle, mirrored)
+                            dst[(size_t)i * P + j] = v;
+                            if (i != j) dst[(size_t)j * P + i] = v;
+                        }
+                    }
+                }
+            }
+    }
+}
+
+// out[k][o] = the partials of the row blocks added in block order; one thread an element
+__global__ __launch_bounds__(256) void k_ar_combine(const double* __restrict__ slabs, int blocks, size_t total,
+                                                    double* __restrict__ out) {
+    const size_t o = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= total) return;
+    double sum = 0.0;
+    for (int b = 0; b < blocks; ++b) sum += slabs[(size_t)b * total + o];
+    out[o] = sum;
+}
+
+// gamma0[k] = the sum of gamma[t][k] over the initial rows; thread i takes the trials i, i + 256, ... in order and
+// thread 0 adds the 256 sums in thread order
+__global__ __launch_bounds__(256) void k_ar_gamma0(const double* __restrict__ gamma, const int* __restrict__ e, int S,
+                                                   int L, int K, double* __restrict__ gamma0) {
+    __shared__ double part[256];
+    const int k = blockIdx.x;
+    double sum = 0.0;
+    for (int s = threadIdx.x; s < S; s += 256) {
+        const int beg = e[s], end = e[s + 1];
+        const int stop = end - beg > L ? beg + L : end;
+        for (int t = beg; t < stop; ++t) sum += gamma[(size_t)t * K + k];
+    }
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double total = 0.0;
+        for (int i = 0; i < 256; ++i) total += part[i];
+        gamma0[k] = total;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+bool bn_arhmm_ok(int n, int S, int D, int L, int K) {
+    return n >= 0 && S >= 0 && S < INT32_MAX && ar_dims_ok(D, L, K);
+}
+
+bool bn_hmm_ok(int n, int S, int K) { return n >= 0 && S >= 0 && S < INT32_MAX && K >= 1 && K <= AR_MAX_K; }
+
+size_t bn_arhmm_loglik_ws_bytes_impl(int n, int S, int D, int L, int K) {
+    if (!bn_arhmm_ok(n, S, D, L, K)) return 0;
+    return ar_offsets_bytes(S) + ar_pad16((size_t)n);
+}
+
+size_t bn_arhmm_moments_ws_bytes_impl(int n, int S, int D, int L, int K) {
+    if (!bn_arhmm_ok(n, S, D, L, K)) return 0;
+    const size_t P = 1 + (size_t)(L + 1) * D;
+    return ar_offsets_bytes(S) + ar_pad16((size_t)n) + (size_t)ar_plan(n, D, L, K).blocks * K * P * P * sizeof(double);
+}
+
+size_t bn_hmm_forward_backward_ws_bytes_impl(int n, int S, int K) {
+    if (!bn_hmm_ok(n, S, K)) return 0;
+    return ar_offsets_bytes(S) + (size_t)n * 2 * sizeof(double);
+}
+
+size_t bn_hmm_viterbi_ws_bytes_impl(int n, int S, int K) {
+    if (!bn_hmm_ok(n, S, K)) return 0;
+    return ar_offsets_bytes(S) + ar_pad16((size_t)n * K);
+}
+
+static int ar_launch_kind(const long long* offsets, int S, int L, int n, void* ws, hipStream_t st) {
+    int* e = reinterpret_cast<int*>(ws);
+    unsigned char* kind = reinterpret_cast<unsigned char*>(ws) + ar_offsets_bytes(S);
+    const int rc = bn_launch_segment_offsets(offsets, S + 1, n, e, st);
+    if (rc) return rc;
+    if (n) {
+        hipLaunchKernelGGL(k_ar_kind, dim3((unsigned)(((long)n + 255) / 256)), dim3(256), 0, st, (const int*)e, S, L,
+                           n, kind);
+        BN_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+int bn_launch_arhmm_loglik(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L,
+                           int K, int n, const double* G, const double* cst, double* ll, void* ws, hipStream_t st) {
+    if (!bn_arhmm_ok(n, S, D, L, K)) return BN_E_SHAPE;
+    if (S == 0) return 0;
+    const int rc = ar_launch_kind(offsets, S, L, n, ws, st);
+    if (rc) return rc;
+    if (!n) return 0;
+    const unsigned char* kind = reinterpret_cast<const unsigned char*>(ws) + ar_offsets_bytes(S);
+    const long per = AR_LL_WAVES * AR_LL_ROWS;
+    hipLaunchKernelGGL(k_ar_loglik, dim3((unsigned)(((long)n + per - 1) / per)), dim3(AR_LL_THREADS), 0, st, z, ld, c,
+                       kind, D, L, K, n, G, cst, ll);
+    BN_LAUNCH_CHECK();
+    return 0;
+}
+
+int bn_launch_arhmm_moments(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L,
+                            int K, int n, const double* gamma, double* out, double* gamma0, void* ws,
+                            hipStream_t st) {
+    if (!bn_arhmm_ok(n, S, D, L, K)) return BN_E_SHAPE;
+    if (S == 0) return 0;
+    const int rc = ar_launch_kind(offsets, S, L, n, ws, st);
+    if (rc) return rc;
+    const int* e = reinterpret_cast<const int*>(ws);
+    const unsigned char* kind = reinterpret_cast<const unsigned char*>(ws) + ar_offsets_bytes(S);
+    double* slabs = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + ar_offsets_bytes(S) + ar_pad16((size_t)n));
+    const ArPlan p = ar_plan(n, D, L, K);
+    const int P = 1 + (L + 1) * D;
+    if (p.blocks) {
+        const int TB = (P + 15) / 16, SG = ar_mo_group(TB);        // column blocks of 16; states a workgroup
+        const dim3 grid((unsigned)p.blocks, (unsigned)((K + SG - 1) / SG)), block(AR_MO_THREADS);
+        switch (TB) {
+            case 1: hipLaunchKernelGGL(k_ar_moments<1>, grid, block, 0, st, z, ld, c, kind, gamma, D, L, K, n, p.rows, slabs); break;
+            case 2: hipLaunchKernelGGL(k_ar_moments<2>, grid, block, 0, st, z, ld, c, kind, gamma, D, L, K, n, p.rows, slabs); break;
+            case 3: hipLaunchKernelGGL(k_ar_moments<3>, grid, block, 0, st, z, ld, c, kind, gamma, D, L, K, n, p.rows, slabs); break;
+            case 4: hipLaunchKernelGGL(k_ar_moments<4>, grid, block, 0, st, z, ld, c, kind, gamma, D, L, K, n, p.rows, slabs); break;
+            default: hipLaunchKernelGGL(k_ar_moments<5>, grid, block, 0, st, z, ld, c, kind, gamma, D, L, K, n, p.rows, slabs); break;
+        }
+        BN_LAUNCH_CHECK();
+    }
+    const size_t total = (size_t)K * P * P;
+    hipLaunchKernelGGL(k_ar_combine, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)slabs,
+                       p.blocks, total, out);
+    BN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_ar_gamma0, dim3((unsigned)K), dim3(256), 0, st, gamma, e, S, L, K, gamma0);
+    BN_LAUNCH_CHECK();
+    return 0;
+}
+
+int bn_launch_hmm_forward_backward(const double* ll, const long long* offsets, int S, int K, int n,
+                                   const double* logP, const double* logpi0, int want, double* gamma, double* xi,
+                                   double* loglik, void* ws, hipStream_t st) {
+    if (!bn_hmm_ok(n, S, K)) return BN_E_SHAPE;
+    if (S == 0) return 0;
+    int* e = reinterpret_cast<int*>(ws);
+    double* cm = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + ar_offsets_bytes(S));
+    const int rc = bn_launch_segment_offsets(offsets, S + 1, n, e, st);
+    if (rc) return rc;
+    const dim3 grid((unsigned)S), block(BN_WAVE);
+    const int* ce = e;
+    if (K <= 4) hipLaunchKernelGGL(k_hmm_fb<4>, grid, block, 0, st, ll, ce, K, logP, logpi0, want, gamma, xi, loglik, cm);
+    else if (K <= 8) hipLaunchKernelGGL(k_hmm_fb<8>, grid, block, 0, st, ll, ce, K, logP, logpi0, want, gamma, xi, loglik, cm);
+    else if (K <= 16) hipLaunchKernelGGL(k_hmm_fb<16>, grid, block, 0, st, ll, ce, K, logP, logpi0, want, gamma, xi, loglik, cm);
+    else hipLaunchKernelGGL(k_hmm_fb<32>, grid, block, 0, st, ll, ce, K, logP, logpi0, want, gamma, xi, loglik, cm);
+    BN_LAUNCH_CHECK();
+    return 0;
+}
+
+int bn_launch_hmm_viterbi(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
+                          const double* logpi0, int* states, void* ws, hipStream_t st) {
+    if (!bn_hmm_ok(n, S, K)) return BN_E_SHAPE;
+    if (S == 0) return 0;
+    int* e = reinterpret_cast<int*>(ws);
+    unsigned char* bp = reinterpret_cast<unsigned char*>(ws) + ar_offsets_bytes(S);
+    const int rc = bn_launch_segment_offsets(offsets, S + 1, n, e, st);
+    if (rc) return rc;
+    const dim3 grid((unsigned)S), block(BN_WAVE);
+    const int* ce = e;
+    if (K <= 4) hipLaunchKernelGGL(k_hmm_viterbi<4>, grid, block, 0, st, ll, ce, K, logP, logpi0, states, bp);
+    else if (K <= 8) hipLaunchKernelGGL(k_hmm_viterbi<8>, grid, block, 0, st, ll, ce, K, logP, logpi0, states, bp);
+    else if (K <= 16) hipLaunchKernelGGL(k_hmm_viterbi<16>, grid, block, 0, st, ll, ce, K, logP, logpi0, states, bp);
+    else hipLaunchKernelGGL(k_hmm_viterbi<32>, grid, block, 0, st, ll, ce, K, logP, logpi0, states, bp);
+    BN_LAUNCH_CHECK();
+    return 0;
+}

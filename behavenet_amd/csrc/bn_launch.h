@@ -138,6 +138,24 @@ int bn_launch_softmax_cv_lossgrad(const float* z, int ld, const int* y, const in
 int bn_launch_softmax_cv_score(const float* z, int ld, const int* y, const int* fold, const double* W,
                                const int* leave, int n, int D, int S, int M, double* out, void* ws, hipStream_t st);
 
+// arhmm.hip: the launches of one EM iteration of an autoregressive HMM on an fp32 table (n, D) cut into trials --
+// emission log-likelihoods, forward-backward, weighted lagged moments -- and Viterbi, float64 throughout
+bool bn_arhmm_ok(int n, int S, int D, int L, int K);
+bool bn_hmm_ok(int n, int S, int K);
+size_t bn_arhmm_loglik_ws_bytes_impl(int n, int S, int D, int L, int K);
+size_t bn_arhmm_moments_ws_bytes_impl(int n, int S, int D, int L, int K);
+size_t bn_hmm_forward_backward_ws_bytes_impl(int n, int S, int K);
+size_t bn_hmm_viterbi_ws_bytes_impl(int n, int S, int K);
+int bn_launch_arhmm_loglik(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L,
+                           int K, int n, const double* G, const double* cst, double* ll, void* ws, hipStream_t st);
+int bn_launch_arhmm_moments(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L,
+                            int K, int n, const double* gamma, double* out, double* gamma0, void* ws, hipStream_t st);
+int bn_launch_hmm_forward_backward(const double* ll, const long long* offsets, int S, int K, int n,
+                                   const double* logP, const double* logpi0, int want, double* gamma, double* xi,
+                                   double* loglik, void* ws, hipStream_t st);
+int bn_launch_hmm_viterbi(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
+                          const double* logpi0, int* states, void* ws, hipStream_t st);
+
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);
 int bn_launch_bn_stats(const float* x, float* mean, float* var, int N, int C, int HW, void* ws,

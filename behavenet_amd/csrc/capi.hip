@@ -2092,6 +2092,70 @@ extern "C" int bn_softmax_cv_score(const float* z, int ld, const int* y, const i
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// EM for autoregressive HMMs on a table of latents (arhmm.hip).
+extern "C" size_t bn_arhmm_loglik_ws_bytes(int n, int S, int D, int L, int K) {
+    return bn_arhmm_loglik_ws_bytes_impl(n, S, D, L, K);
+}
+
+extern "C" size_t bn_arhmm_moments_ws_bytes(int n, int S, int D, int L, int K) {
+    return bn_arhmm_moments_ws_bytes_impl(n, S, D, L, K);
+}
+
+extern "C" size_t bn_hmm_forward_backward_ws_bytes(int n, int S, int K) {
+    return bn_hmm_forward_backward_ws_bytes_impl(n, S, K);
+}
+
+extern "C" size_t bn_hmm_viterbi_ws_bytes(int n, int S, int K) { return bn_hmm_viterbi_ws_bytes_impl(n, S, K); }
+
+extern "C" int bn_arhmm_loglik(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L,
+                               int K, int n, const double* G, const double* cst, double* ll, void* ws,
+                               size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_arhmm_ok(n, S, D, L, K) || ld < D) return BN_E_SHAPE;
+    if (!z || !offsets || !G || !cst || !ll || !ws) return BN_E_BADARG;
+    if (((uintptr_t)z & 3) || ((uintptr_t)c & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)G & 7) ||
+        ((uintptr_t)cst & 7) || ((uintptr_t)ll & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_arhmm_loglik_ws_bytes_impl(n, S, D, L, K)) return BN_E_SHAPE;
+    return bn_launch_arhmm_loglik(z, ld, c, offsets, S, D, L, K, n, G, cst, ll, ws, (hipStream_t)stream);
+}
+
+extern "C" int bn_arhmm_moments(const float* z, int ld, const double* c, const long long* offsets, int S, int D,
+                                int L, int K, int n, const double* gamma, double* out, double* gamma0, void* ws,
+                                size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_arhmm_ok(n, S, D, L, K) || ld < D) return BN_E_SHAPE;
+    if (!z || !offsets || !gamma || !out || !gamma0 || !ws) return BN_E_BADARG;
+    if (((uintptr_t)z & 3) || ((uintptr_t)c & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)gamma & 7) ||
+        ((uintptr_t)out & 7) || ((uintptr_t)gamma0 & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_arhmm_moments_ws_bytes_impl(n, S, D, L, K)) return BN_E_SHAPE;
+    return bn_launch_arhmm_moments(z, ld, c, offsets, S, D, L, K, n, gamma, out, gamma0, ws, (hipStream_t)stream);
+}
+
+extern "C" int bn_hmm_forward_backward(const double* ll, const long long* offsets, int S, int K, int n,
+                                       const double* logP, const double* logpi0, int want, double* gamma, double* xi,
+                                       double* loglik, void* ws, size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_hmm_ok(n, S, K) || want < 0 || want > 1) return BN_E_SHAPE;
+    if (!ll || !offsets || !logP || !logpi0 || !loglik || !ws || (want && (!gamma || !xi))) return BN_E_BADARG;
+    if (((uintptr_t)ll & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)logP & 7) || ((uintptr_t)logpi0 & 7) ||
+        ((uintptr_t)gamma & 7) || ((uintptr_t)xi & 7) || ((uintptr_t)loglik & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_hmm_forward_backward_ws_bytes_impl(n, S, K)) return BN_E_SHAPE;
+    return bn_launch_hmm_forward_backward(ll, offsets, S, K, n, logP, logpi0, want, gamma, xi, loglik, ws,
+                                          (hipStream_t)stream);
+}
+
+extern "C" int bn_hmm_viterbi(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
+                              const double* logpi0, int* states, void* ws, size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_hmm_ok(n, S, K)) return BN_E_SHAPE;
+    if (!ll || !offsets || !logP || !logpi0 || !states || !ws) return BN_E_BADARG;
+    if (((uintptr_t)ll & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)logP & 7) || ((uintptr_t)logpi0 & 7) ||
+        ((uintptr_t)states & 3) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_hmm_viterbi_ws_bytes_impl(n, S, K)) return BN_E_SHAPE;
+    return bn_launch_hmm_viterbi(ll, offsets, S, K, n, logP, logpi0, states, ws, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // fp32 unit-float frames -> stored uint8 grey levels (recon_u8.hip): NaN -> 0, else clamp(rint(x * 255), 0, 255).
 extern "C" int bn_unit_float_to_u8(const float* in, unsigned char* out, size_t n, bn_stream_t stream) {
     if (!in || !out) return BN_E_BADARG;

@@ -40,7 +40,7 @@ __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconst
            'percentile_plan', 'percentile_lerp', 'column_percentiles', 'compute_range', 'latent_ranges',
            'latent_ranges_device', 'summarise_label_sums', 'label_r2', 'export_label_r2', 'summarise_gram',
            'latent_correlations', 'export_latent_correlations', 'session_classifier', 'export_session_classifier',
-           'classify_table', 'score_table']
+           'classify_table', 'score_table', 'fit_arhmm', 'fit_arhmm_tables', 'export_states', 'export_arhmm']
 
 
 def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -2030,3 +2030,225 @@ def export_session_classifier(data_generator, model, dtype='val', columns=None, 
         filename = os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, SESSION_CLASSIFIER_FILE)
     np.save(filename, np.array([out[0]]))
     return filename, out[0], out[1]
+
+
+# ------------------------------------------------------------------------------------------ ARHMM (second stage)
+ARHMM_MODEL_FILE = 'arhmm_best_val_model.pt'
+_ARHMM_NOISE = {'gaussian': 'ar'}            # noise_type -> the model's observations ('gaussian' at zero lags)
+
+
+def _arhmm_trials(who, data_generator, model, data_key, dtypes, wanted):
+    """``{(session, trial): fp32 device tensor (T, D)}`` of the trials of the splits ``dtypes`` of the sessions
+    ``wanted``: the latents, walked and encoded as ``latent_correlations`` walks and encodes them, or, for
+    ``data_key='labels'``, the labels the generator serves (no model is needed for those)."""
+    parts = {}
+    if data_key == 'labels':
+        device = torch.device('cuda', torch.cuda.current_device()) if model is None \
+            else next(model.parameters()).device
+        for dtype in dtypes:
+            data_generator.reset_iterators(dtype)
+            for _ in range(sum(len(ds.batch_idxs[dtype]) for ds in data_generator.datasets)):
+                single = {'return_multiple': False} if getattr(data_generator, 'n_sessions_per_batch', 1) > 1 else {}
+                data, sess = data_generator.next_batch(dtype, **single)
+                if 'labels' not in data:
+                    raise ValueError('%s: the generator serves no labels (session %d)' % (who, sess))
+                if sess not in wanted:
+                    continue
+                idx = data['batch_idx']
+                y = data['labels'][0]
+                y = y if torch.is_tensor(y) else torch.from_numpy(np.asarray(y))
+                parts[(sess, idx.item() if hasattr(idx, 'item') else int(idx))] = y.to(device, torch.float32)
+        return parts
+    if data_key != 'ae_latents':
+        raise ValueError("%s: data_key must be 'ae_latents' or 'labels', got %r" % (who, data_key))
+    if model is None:
+        raise ValueError('%s: latents need the model that encodes them' % who)
+    device = next(model.parameters()).device
+    encode = _GraphedTrialEncoder(model)
+
+    def on_device(images, sess, data, trial):
+        return encode(images, sess, _batch_fields(model, data)[2]) if sess in wanted else None
+
+    def on_host(images, sess, data, trial):
+        if sess not in wanted:
+            return None
+        z = encode_trial(model, images, sess, _batch_fields(model, data)[2])
+        return torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(device)
+
+    def sink(sess, trial, result):
+        if result is not None and len(result):
+            parts[(sess, int(trial))] = result.to(torch.float32)
+    _export_per_trial(who, data_generator, model, on_device, on_host, sink=sink, dtypes=dtypes)
+    return parts
+
+
+def _arhmm_split(parts, keys):
+    """``(table, offsets, sessions, trials)`` of the trials ``keys`` in that order; the table is None without rows."""
+    keys = [k for k in keys if k in parts]
+    offsets = np.concatenate(([0], np.cumsum([parts[k].shape[0] for k in keys]))).astype(np.int64)
+    table = torch.cat([parts[k] for k in keys], dim=0).contiguous() if keys and offsets[-1] else None
+    return (table, offsets, np.asarray([k[0] for k in keys], dtype=np.int64),
+            np.asarray([k[1] for k in keys], dtype=np.int64))
+
+
+def _arhmm_loss(lls, offsets, sel, D):
+    """``-loglik / (frames D)`` over the trials ``sel`` (a mask); NaN without frames."""
+    frames = float(np.sum(np.diff(offsets)[sel]))
+    return float(-np.sum(lls[sel]) / (frames * D)) if frames else float('nan')
+
+
+def _fit_arhmm_splits(splits, n_datasets, n_states, n_lags, transitions, kappa, n_iters, tol, rng_seed_model,
+                      noise_type):
+    from behavenet_amd.models.arhmm import ARHMM
+    if noise_type not in _ARHMM_NOISE:
+        raise NotImplementedError('fit_arhmm: noise_type %r is not served (gaussian is)' % (noise_type,))
+    train, t_off, t_sess, _ = splits['train']
+    if train is None:
+        raise ValueError('fit_arhmm: no train frames')
+    val, v_off, v_sess, _ = splits['val']
+    D = int(train.shape[1])
+    arhmm = ARHMM(n_states, D, lags=n_lags, transitions='stationary' if transitions == 'standard' else transitions,
+                  kappa=kappa)
+    arhmm.initialize(train, t_off, seed=rng_seed_model)
+    rows, stats, val_prev, epoch = [], None, np.inf, 0
+    for epoch in range(int(n_iters) + 1):
+        # the 0th epoch has no training: the initialised model is evaluated.  The E-step that scores the training
+        # trials of an epoch is the one the next epoch's M-step needs
+        if epoch > 0:
+            arhmm.m_step(*stats)
+        mom, _, xi_sum, g0, tr_lls = arhmm.e_step(train, t_off)
+        stats = (mom, xi_sum, g0)
+        val_lls = arhmm.trial_logliks(val, v_off) if val is not None else np.zeros((0,))
+        every_t, every_v = np.ones(len(t_sess), dtype=bool), np.ones(len(v_sess), dtype=bool)
+        val_ll = _arhmm_loss(val_lls, v_off, every_v, D)
+        rows.append({'epoch': epoch, 'dataset': -1, 'tr_loss': _arhmm_loss(tr_lls, t_off, every_t, D),
+                     'val_loss': val_ll, 'trial': -1})
+        for d in n_datasets:
+            val_ll = _arhmm_loss(val_lls, v_off, v_sess == d, D)
+            rows.append({'epoch': epoch, 'dataset': d, 'tr_loss': _arhmm_loss(tr_lls, t_off, t_sess == d, D),
+                         'val_loss': val_ll, 'trial': -1})
+        # (the reference compares the val_loss it computed last: the last session's)
+        if epoch > 10 and np.abs((val_ll - val_prev) / val_ll) < tol:
+            print('relative change less than tolerance=%1.2f; training terminating!' % tol)
+            break
+        val_prev = val_ll
+    test, s_off, s_sess, s_trial = splits['test']
+    if test is not None:
+        test_lls = arhmm.trial_logliks(test, s_off)
+        for i in np.argsort(s_sess, kind='stable'):
+            frames = int(s_off[i + 1] - s_off[i])
+            rows.append({'epoch': epoch, 'dataset': int(s_sess[i]),
+                         'test_loss': float(-test_lls[i] / (frames * D)) if frames else float('nan'),
+                         'trial': int(s_trial[i])})
+    # states relabelled by usage on the training trials
+    usage = np.bincount(arhmm.table_states(train, t_off), minlength=arhmm.K)
+    arhmm.permute(np.argsort(usage)[::-1])
+    return arhmm, rows
+
+
+def fit_arhmm(data_generator, model, n_states, n_lags=1, transitions='stationary', kappa=0, n_iters=150, tol=0,
+              rng_seed_model=0, sess_idx=None, data_key='ae_latents', noise_type='gaussian'):
+    """Fit an ARHMM on a model's latents by EM with the E-step on the device: the second stage of the BehaveNet
+    pipeline, with the bookkeeping of the reference's driver (fitting/arhmm_grid_search.py:132-209).
+
+    The train / val / test trials of the sessions ``sess_idx`` are walked and encoded as ``latent_correlations`` walks
+    and encodes them (``hparams['hip_encode_dtype']`` is honoured) and kept as one device table per split, in the
+    reference's order.  ``data_key='labels'`` takes the generator's labels in place of latents (``arhmm-labels``;
+    ``model`` may be None).  Epochs ``0 .. n_iters``: epoch 0 is evaluated and not trained; ``tr_loss`` and
+    ``val_loss`` are ``-loglik / (frames D)``, pooled (``dataset = -1``) and per session; the fit stops after epoch 10
+    on a relative ``val_loss`` change below ``tol``; a ``test_loss`` per test trial follows; then the states are
+    relabelled by their usage in the Viterbi paths of the training trials.
+    -> ``(arhmm, rows)``: the ``models.arhmm.ARHMM`` and the list of dicts the reference hands to ``exp.log``.
+    Under ``torch.distributed`` rank 0 fits and the other ranks return None."""
+    who = 'fit_arhmm'
+    if data_key == 'ae_latents':
+        _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return None
+    wanted = _wanted_sessions(who, data_generator, sess_idx)
+    parts = _arhmm_trials(who, data_generator, model, data_key, ('train', 'val', 'test'), wanted)
+    idxs = [ds.batch_idxs for ds in data_generator.datasets]
+    splits = {dt: _arhmm_split(parts, _corr_trial_order(idxs, [dt], wanted)) for dt in ('train', 'val', 'test')}
+    return _fit_arhmm_splits(splits, sorted(wanted), n_states, n_lags, transitions, kappa, n_iters, tol,
+                             rng_seed_model, noise_type)
+
+
+def fit_arhmm_tables(train, val=None, test=None, n_states=2, n_lags=1, transitions='stationary', kappa=0, n_iters=150,
+                     tol=0, rng_seed_model=0, noise_type='gaussian'):
+    """``fit_arhmm`` for lists of (T, D) arrays or device tensors, with no generator and no model: one session
+    (``dataset = 0``), the trials numbered by their position in their list."""
+    from behavenet_amd.models.arhmm import ARHMM
+    splits = {}
+    for name, datas in (('train', train), ('val', val), ('test', test)):
+        datas = list(datas) if datas is not None else []
+        if datas:
+            table, offsets = ARHMM.as_table(datas)
+            table = table if offsets[-1] else None
+        else:
+            table, offsets = None, np.zeros((1,), dtype=np.int64)
+        splits[name] = (table, offsets, np.zeros(len(datas), dtype=np.int64), np.arange(len(datas), dtype=np.int64))
+    return _fit_arhmm_splits(splits, [0], n_states, n_lags, transitions, kappa, n_iters, tol, rng_seed_model,
+                             noise_type)
+
+
+def export_states(hparams, data_generator, arhmm, model=None, filename=None):
+    """The most likely states of every train / val / test trial, per session
+    ``{'states': [per-trial int arrays, empty for gap trials], 'trials': batch_idxs}`` in
+    ``<lab>_<expt>_<animal>_<session>_states.pkl`` under ``hparams['expt_dir']/version_<hparams['version']>`` (or
+    ``filename``): the reference's ``export_states`` (fitting/eval.py:121-188).  The trials' latents (encoded by
+    ``model``) or, for a ``model_class`` with ``label`` in it, their labels go into ONE device table and ONE Viterbi
+    launch.  -> the file names (an empty list on the ranks other than 0)."""
+    who = 'export_states'
+    data_key = 'labels' if str(hparams.get('model_class', 'arhmm')).find('label') > -1 else 'ae_latents'
+    if data_key == 'ae_latents' and model is not None:
+        _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return []
+    wanted = set(range(len(data_generator.datasets)))
+    parts = _arhmm_trials(who, data_generator, model, data_key, ('train', 'val', 'test'), wanted)
+    keys = sorted(parts)
+    table, offsets, _, _ = _arhmm_split(parts, keys)
+    states = [[np.array([]) for _ in range(ds.n_trials)] for ds in data_generator.datasets]
+    if table is not None:
+        path = arhmm.table_states(table, offsets)
+        for i, (sess, trial) in enumerate(keys):
+            states[sess][trial] = path[offsets[i]:offsets[i + 1]].copy()
+    filenames = []
+    for sess, dataset in enumerate(data_generator.datasets):
+        out = filename
+        if out is None:
+            sess_id = '%s_%s_%s_%s_states.pkl' % (dataset.lab, dataset.expt, dataset.animal, dataset.session)
+            out = os.path.join(hparams['expt_dir'], 'version_%i' % hparams['version'], sess_id)
+        print('saving states %i of %i:\n%s' % (sess + 1, data_generator.n_datasets, out))
+        with open(out, 'wb') as f:
+            pickle.dump({'states': states[sess], 'trials': dataset.batch_idxs}, f)
+        filenames.append(out)
+    return filenames
+
+
+def check_export_arhmm(who, kwargs):
+    """``hparams['export_arhmm']``: a dict of ``fit_arhmm``'s keyword arguments with ``n_states`` among them."""
+    import inspect
+    known = set(inspect.signature(fit_arhmm).parameters) - {'data_generator', 'model'}
+    if not isinstance(kwargs, dict) or 'n_states' not in kwargs or not set(kwargs) <= known:
+        raise ValueError('%s: expected a dict with n_states and any of %s, got %r' % (who, sorted(known), kwargs))
+    from behavenet_amd.models.arhmm import ARHMM
+    ARHMM(kwargs['n_states'], 1, lags=kwargs.get('n_lags', 1),                         # (limits and served types)
+          transitions={'standard': 'stationary'}.get(kwargs.get('transitions'), kwargs.get('transitions', 'stationary')))
+
+
+def export_arhmm(data_generator, model, **kwargs):
+    """``fit_arhmm`` + ``export_states`` for a trained model: the ARHMM pickled as ``arhmm_best_val_model.pt`` and the
+    states files next to the model's latents.  -> ``(arhmm, rows, model file, states files)``, None on the ranks
+    other than 0."""
+    out = fit_arhmm(data_generator, model, **kwargs)
+    if out is None:
+        return None
+    arhmm, rows = out
+    labels = kwargs.get('data_key', 'ae_latents') == 'labels'
+    hparams = {'expt_dir': model.hparams['expt_dir'], 'version': model.version,
+               'model_class': ('arhmm' if kwargs.get('n_lags', 1) > 0 else 'hmm') + ('-labels' if labels else '')}
+    path = os.path.join(hparams['expt_dir'], 'version_%i' % hparams['version'], ARHMM_MODEL_FILE)
+    with open(path, 'wb') as f:
+        pickle.dump(arhmm, f)
+    return arhmm, rows, path, export_states(hparams, data_generator, arhmm, model=model)

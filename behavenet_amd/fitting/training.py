@@ -595,6 +595,10 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
         # (one session has nothing to tell apart: an error now, not after the last epoch)
         from behavenet_amd.fitting.eval import _check_session_classifier
         _check_session_classifier("fit: hparams['export_session_classifier']", data_generator)
+    if method == 'ae' and hparams.get('export_arhmm'):
+        # (a state count or a transition type that is not served: an error now, not after the last epoch)
+        from behavenet_amd.fitting.eval import check_export_arhmm
+        check_export_arhmm("fit: hparams['export_arhmm']", hparams['export_arhmm'])
     # hparams['shard_optimizer'] (BN_SHARD_OPTIMIZER=0/1): reduce-scatter -> Adam on this rank's 1/R
     # shard of the arena -> all-gather, instead of all-reduce + R identical steps
     # (fitting/distributed.py sharded_step, default_shard_optimizer: on for frame sharding over >= 4 ranks)
@@ -859,6 +863,11 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
             print('exporting the session classifier score of the val trials')
         from behavenet_amd.fitting.eval import export_session_classifier
         export_session_classifier(data_generator, best_val_model, dtype='val')
+    if method == 'ae' and hparams.get('export_arhmm'):
+        if is_main:
+            print('fitting an ARHMM on the latents and exporting its states')
+        from behavenet_amd.fitting.eval import export_arhmm
+        export_arhmm(data_generator, best_val_model, **hparams['export_arhmm'])
     if resume and is_main:
         if state_writer is not None:
             state_writer.wait()

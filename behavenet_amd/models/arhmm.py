@@ -1,0 +1,320 @@
+"""Autoregressive hidden Markov models on autoencoder latents, fitted by EM with the E-step on the device
+("ARHMM"; csrc/arhmm.hip).
+
+The class has the duck type the reference's ARHMM driver (fitting/arhmm_grid_search.py:132-209) and ``export_states``
+use of the ``ssm`` library's ``HMM``: ``initialize``, ``fit(method='em', num_iters=1, initialize=False)`` in a loop,
+``log_likelihood``, ``expected_states``, ``most_likely_states``, ``permute``.  Served: Gaussian AR observations with
+full covariance, ``lags >= 0`` (0 is the reference's ``hmm`` class), ``stationary`` and ``sticky`` transitions, EM.
+Everything else is a ``NotImplementedError`` that names the type.
+
+Host side: numpy float64 only -- the M-step, the fold of the parameters for the kernel, the priors.  Device side (per EM
+iteration): ``bn_arhmm_loglik`` -> ``bn_hmm_forward_backward`` -> ``bn_arhmm_moments`` on one fp32 table that holds
+every trial, one transfer of ``K (P^2 + K + 1)`` doubles.
+
+Model, with ``x_t`` the row, ``L = lags`` and state ``k`` at time ``t``:
+
+    x_t | z_t = k  ~  N(b_k + sum_l A_k[l] x_{t-1-l}, Sigma_k)           t >= L   (``As[k][:, l D:(l + 1) D] = A_k[l]``)
+    x_t            ~  N(0, I)                                            t <  L   (the same for every state)
+
+The priors and their defaults (``l2_penalty_A``, ``l2_penalty_b``, ``nu0``, ``Psi0``, ``alpha``, ``kappa``) and the
+standard-normal initial rows are THIS project's definitions.  They follow what the ``ssm`` library does as far as its
+authors' papers describe it, but that library is not installed where this was written and no parity with it has been
+checked.
+"""
+
+import numpy as np
+
+_LOG_2PI = float(np.log(2.0 * np.pi))
+_SERVED_TRANSITIONS = ('stationary', 'sticky')
+_SERVED_OBSERVATIONS = ('ar', 'gaussian')
+
+
+class ARHMM(object):
+
+    def __init__(self, K, D, lags=1, transitions='stationary', kappa=0, alpha=1, l2_penalty_A=1e-8, l2_penalty_b=1e-8,
+                 nu0=1e-4, Psi0=1e-4, observations='ar'):
+        if observations not in _SERVED_OBSERVATIONS:
+            raise NotImplementedError('ARHMM: observations %r are not served (%s are)'
+                                      % (observations, ', '.join(_SERVED_OBSERVATIONS)))
+        if transitions not in _SERVED_TRANSITIONS:
+            raise NotImplementedError('ARHMM: transitions %r are not served (%s are)'
+                                      % (transitions, ', '.join(_SERVED_TRANSITIONS)))
+        if observations == 'gaussian':
+            lags = 0
+        from behavenet_amd import _hip
+        _hip.check_arhmm_dims('ARHMM', int(D), int(lags), int(K))
+        self.K, self.D, self.lags = int(K), int(D), int(lags)
+        self.transitions = transitions
+        self.kappa = float(kappa) if transitions == 'sticky' else 0.0
+        self.alpha = float(alpha)
+        self.l2_penalty_A, self.l2_penalty_b = float(l2_penalty_A), float(l2_penalty_b)
+        self.nu0, self.Psi0 = float(nu0), float(Psi0)
+        K, D, L = self.K, self.D, self.lags
+        self.As = np.zeros((K, D, L * D))
+        self.bs = np.zeros((K, D))
+        self.Sigmas = np.tile(np.eye(D), (K, 1, 1))
+        self.log_pi0 = np.full((K,), -np.log(K))
+        self.log_Ps = self._initial_log_Ps()
+        self.shift = np.zeros((D,))          # the kernels' column shift c: a property of the fit, not of the model
+
+    @property
+    def P(self):
+        return 1 + (self.lags + 1) * self.D
+
+    def _initial_log_Ps(self):
+        Ps = np.ones((self.K, self.K)) + self.kappa * np.eye(self.K)
+        return np.log(Ps / Ps.sum(axis=1, keepdims=True))
+
+    # ------------------------------------------------------------------------------------------------------
+    # host side
+    # ------------------------------------------------------------------------------------------------------
+    def fold(self):
+        """``(G, cst)`` for ``bn_arhmm_loglik``: ``G[k] = R_k [-(b_k - c + sum_l A_k[l] c) | I | -A_k]`` with
+        ``R_k = C_k^-1``, ``Sigma_k = C_k C_k^T`` (Cholesky), so ``|G_k a_t|^2`` is the Mahalanobis distance of the
+        residual, and ``cst[k] = -D/2 log 2 pi + log det R_k``."""
+        K, D, L, P = self.K, self.D, self.lags, self.P
+        G = np.zeros((K, D, P))
+        cst = np.zeros((K,))
+        c = self.shift
+        for k in range(K):
+            try:
+                C = np.linalg.cholesky(self.Sigmas[k])
+            except np.linalg.LinAlgError:
+                raise ValueError('ARHMM.fold: Sigmas[%d] is not positive definite' % k)
+            if not np.all(np.isfinite(C)):
+                raise ValueError('ARHMM.fold: Sigmas[%d] is not finite' % k)
+            M = np.zeros((D, P))
+            Ac = np.zeros((D,))
+            for l in range(L):
+                Ac += self.As[k][:, l * D:(l + 1) * D] @ c
+            M[:, 0] = -(self.bs[k] - c + Ac)
+            M[:, 1:1 + D] = np.eye(D)
+            M[:, 1 + D:] = -self.As[k]
+            G[k] = np.linalg.solve(C, M)
+            cst[k] = -0.5 * D * _LOG_2PI - np.sum(np.log(np.diag(C)))
+        return G, cst
+
+    def _ridge(self):
+        lam = np.full((1 + self.lags * self.D,), self.l2_penalty_A)
+        lam[0] = self.l2_penalty_b
+        return lam
+
+    def _shifted_weights(self, k):
+        """``W = [b' | A]`` of state k in the shifted coordinates of the moments: ``x_t - c = b' + A (u - c)``."""
+        c, D = self.shift, self.D
+        Ac = np.zeros((D,))
+        for l in range(self.lags):
+            Ac += self.As[k][:, l * D:(l + 1) * D] @ c
+        return np.concatenate([(self.bs[k] - c + Ac)[:, None], self.As[k]], axis=1)
+
+    def m_step_observations(self, moments):
+        """Per state the ridge-regularised weighted least squares for ``[b | A]`` and the MAP covariance from the
+        moment matrices ``moments`` (K, P, P) of ``a_t = (1, x_t - c, x_{t-1} - c, ...)``.  A state whose expected
+        count is below ``D + 1`` keeps its parameters."""
+        K, D, L = self.K, self.D, self.lags
+        moments = np.asarray(moments, dtype=np.float64)
+        assert moments.shape == (K, self.P, self.P), moments.shape
+        c = self.shift
+        phi = np.concatenate([[0], np.arange(1 + D, self.P)]).astype(int)       # (1, lagged columns)
+        y = np.arange(1, 1 + D)
+        lam = np.diag(self._ridge())
+        for k in range(K):
+            M = moments[k]
+            N = M[0, 0]
+            if not np.isfinite(N) or N < D + 1:
+                continue
+            Sxx = M[np.ix_(phi, phi)] + lam
+            Sxy = M[np.ix_(phi, y)]
+            Syy = M[np.ix_(y, y)]
+            W = np.linalg.solve(Sxx, Sxy).T                                     # (D, 1 + L D), shifted coordinates
+            scatter = Syy - W @ Sxy - Sxy.T @ W.T + W @ Sxx @ W.T               # (residuals and the ridge term)
+            Sigma = (scatter + self.Psi0 * np.eye(D)) / (N + self.nu0 + D + 1)
+            A = W[:, 1:]
+            Ac = np.zeros((D,))
+            for l in range(L):
+                Ac += A[:, l * D:(l + 1) * D] @ c
+            self.As[k] = A
+            self.bs[k] = W[:, 0] + c - Ac
+            self.Sigmas[k] = 0.5 * (Sigma + Sigma.T)
+
+    def m_step_transitions(self, xi_sum, gamma0_sum):
+        """Transition rows ``~ xi_sum + kappa I + (alpha - 1)`` and ``pi0 ~ gamma0_sum + 1e-8`` (the summed pairwise
+        posteriors (K, K) and the summed first-row marginals (K)).  A row without mass keeps its values."""
+        xi_sum = np.asarray(xi_sum, dtype=np.float64)
+        Ps = np.maximum(xi_sum + self.kappa * np.eye(self.K) + (self.alpha - 1.0), 0.0)
+        tot = Ps.sum(axis=1)
+        with np.errstate(divide='ignore'):
+            for k in range(self.K):
+                if np.isfinite(tot[k]) and tot[k] > 0:
+                    self.log_Ps[k] = np.log(Ps[k] / tot[k])
+            p0 = np.asarray(gamma0_sum, dtype=np.float64) + 1e-8
+            if np.all(np.isfinite(p0)):
+                self.log_pi0 = np.log(p0 / p0.sum())
+
+    def m_step(self, moments, xi_sum, gamma0_sum):
+        self.m_step_observations(moments)
+        self.m_step_transitions(xi_sum, gamma0_sum)
+
+    def log_prior(self):
+        """The log prior the M-step maximises with the expected log-likelihood (up to constants): per state
+        ``-1/2 (nu0 + D + 1) log det Sigma - 1/2 tr(Sigma^-1 (Psi0 I + W Lambda W^T))`` with ``W`` in the shifted
+        coordinates and ``Lambda`` the ridge; ``sum (kappa I + alpha - 1) log Ps``; ``1e-8 sum log pi0``."""
+        lp = 0.0
+        lam = np.diag(self._ridge())
+        for k in range(self.K):
+            W = self._shifted_weights(k)
+            _, logdet = np.linalg.slogdet(self.Sigmas[k])
+            B = self.Psi0 * np.eye(self.D) + W @ lam @ W.T
+            lp += -0.5 * (self.nu0 + self.D + 1) * logdet - 0.5 * np.trace(np.linalg.solve(self.Sigmas[k], B))
+        w = self.kappa * np.eye(self.K) + (self.alpha - 1.0)
+        nz = w != 0
+        lp += float(np.sum(w[nz] * self.log_Ps[nz]))
+        lp += 1e-8 * float(np.sum(self.log_pi0))
+        return float(lp)
+
+    def permute(self, perm):
+        """State ``k`` becomes the old state ``perm[k]`` (the reference relabels by usage with it)."""
+        perm = np.asarray(perm, dtype=int)
+        assert sorted(perm.tolist()) == list(range(self.K)), perm
+        self.As, self.bs, self.Sigmas = self.As[perm].copy(), self.bs[perm].copy(), self.Sigmas[perm].copy()
+        self.log_pi0 = self.log_pi0[perm].copy()
+        self.log_Ps = self.log_Ps[np.ix_(perm, perm)].copy()
+
+    # ------------------------------------------------------------------------------------------------------
+    # device side
+    # ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def as_table(datas, device=None):
+        """``(table, offsets)``: the trials ``datas`` -- one (T, D) array or tensor, or a list of them -- as ONE fp32
+        device table and the int64 host offsets of its trials."""
+        import torch
+        if not isinstance(datas, (list, tuple)):
+            datas = [datas]
+        device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        parts, offsets = [], [0]
+        for x in datas:
+            t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32))
+            if t.dim() != 2:
+                raise ValueError('ARHMM: a trial must be (T, D), got %s' % (tuple(t.shape),))
+            parts.append(t.to(device=device, dtype=torch.float32))
+            offsets.append(offsets[-1] + int(t.shape[0]))
+        if not parts:
+            raise ValueError('ARHMM: no trials')
+        return torch.cat(parts, dim=0).contiguous(), np.asarray(offsets, dtype=np.int64)
+
+    def _check_table(self, table):
+        if table.dim() != 2 or int(table.shape[1]) != self.D:
+            raise ValueError('ARHMM: the model has D = %d, the data %s' % (self.D, tuple(table.shape)))
+
+    def set_shift(self, table):
+        """The kernels' shift: the column means of the table (from ``bn_segment_gram``'s sums), rounded to fp32 values.
+        The moments lose no digits to a mean far from zero; the model's parameters do not depend on it."""
+        from behavenet_amd import _hip
+        n = int(table.shape[0])
+        g = _hip.segment_gram(table, np.asarray([0, n], dtype=np.int64))[0].cpu().numpy()
+        self.shift = (g[0, 1:] / max(g[0, 0], 1.0)).astype(np.float32).astype(np.float64)
+        return self.shift
+
+    def _loglik_table(self, table, offsets_d):
+        from behavenet_amd import _hip
+        G, cst = self.fold()
+        return _hip.arhmm_loglik(table, offsets_d, G, cst, self.lags, shift=self.shift)
+
+    def _offsets_d(self, table, offsets):
+        import torch
+        if torch.is_tensor(offsets):
+            return offsets
+        return torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(table.device)
+
+    def trial_logliks(self, table, offsets):
+        """The log-likelihood of every trial of the table, a float64 host array (S,) (forward sweep only)."""
+        from behavenet_amd import _hip
+        self._check_table(table)
+        offsets_d = self._offsets_d(table, offsets)
+        ll = self._loglik_table(table, offsets_d)
+        return _hip.hmm_forward_backward(ll, offsets_d, self.log_Ps, self.log_pi0,
+                                         want_posteriors=False)[2].cpu().numpy()
+
+    def e_step(self, table, offsets):
+        """``(moments, gamma_init, xi_sum, gamma0_sum, logliks)`` of the current parameters, host arrays: the three
+        launches of an EM iteration and ONE transfer."""
+        import torch
+        from behavenet_amd import _hip
+        self._check_table(table)
+        offsets_d = self._offsets_d(table, offsets)
+        K, P = self.K, self.P
+        ll = self._loglik_table(table, offsets_d)
+        gamma, xi, lls = _hip.hmm_forward_backward(ll, offsets_d, self.log_Ps, self.log_pi0)
+        mom, ginit = _hip.arhmm_moments(table, offsets_d, gamma, self.lags, shift=self.shift)
+        # the first row of every trial that has one
+        first = offsets_d[:-1][offsets_d[1:] > offsets_d[:-1]]
+        g0 = gamma.index_select(0, first).sum(dim=0) if first.numel() else gamma.new_zeros((K,))
+        packed = torch.cat([mom.reshape(-1), ginit, xi.sum(dim=0).reshape(-1), g0, lls]).cpu().numpy()
+        o = np.cumsum([0, K * P * P, K, K * K, K])
+        return (packed[o[0]:o[1]].reshape(K, P, P), packed[o[1]:o[2]], packed[o[2]:o[3]].reshape(K, K),
+                packed[o[3]:o[4]], packed[o[4]:])
+
+    def em_step(self, table, offsets):
+        """One EM iteration on the table; returns the per-trial log-likelihoods of the parameters BEFORE the update."""
+        mom, _, xi_sum, g0, lls = self.e_step(table, offsets)
+        self.m_step(mom, xi_sum, g0)
+        return lls
+
+    def initialize(self, table, offsets=None, seed=0):
+        """Per state one least-squares AR fit on a randomly drawn contiguous window of the table (0/1 weights through
+        ``bn_arhmm_moments``), uniform ``pi0``, transition rows ``~ 1 + kappa I``.  ``table`` may be a list of trials."""
+        import torch
+        from behavenet_amd import _hip
+        if offsets is None:
+            table, offsets = self.as_table(table)
+        self._check_table(table)
+        n = int(table.shape[0])
+        self.set_shift(table)
+        rng = np.random.RandomState(seed)
+        width = min(n, max(8 * self.P, n // max(self.K, 1)))
+        gamma = torch.zeros((n, self.K), dtype=torch.float64, device=table.device)
+        for k in range(self.K):
+            start = int(rng.randint(0, n - width + 1))
+            gamma[start:start + width, k] = 1.0
+        mom, _ = _hip.arhmm_moments(table, self._offsets_d(table, offsets), gamma, self.lags, shift=self.shift)
+        self.m_step_observations(mom.cpu().numpy())
+        self.log_pi0 = np.full((self.K,), -np.log(self.K))
+        self.log_Ps = self._initial_log_Ps()
+
+    def fit(self, datas, method='em', num_iters=100, initialize=True, seed=0, **kwargs):
+        """EM on the trials ``datas``; returns the total log-likelihood before every iteration (the library's
+        ``fit`` returns its ``lls`` the same way)."""
+        if method != 'em':
+            raise NotImplementedError('ARHMM.fit: method %r is not served (em is)' % (method,))
+        table, offsets = self.as_table(datas)
+        if initialize:
+            self.initialize(table, offsets, seed=seed)
+        elif not np.any(self.shift):
+            self.set_shift(table)
+        return [float(np.sum(self.em_step(table, offsets))) for _ in range(int(num_iters))]
+
+    def log_likelihood(self, datas):
+        table, offsets = self.as_table(datas)
+        return float(np.sum(self.trial_logliks(table, offsets)))
+
+    def expected_states(self, x):
+        """``(Ez, Ezzp1_sum, loglik)`` of ONE trial: the marginals (T, K), the pairwise posteriors summed over time
+        (K, K) -- the library returns them per step -- and the log-likelihood."""
+        from behavenet_amd import _hip
+        table, offsets = self.as_table(x)
+        offsets_d = self._offsets_d(table, offsets)
+        ll = self._loglik_table(table, offsets_d)
+        gamma, xi, lls = _hip.hmm_forward_backward(ll, offsets_d, self.log_Ps, self.log_pi0)
+        return gamma.cpu().numpy(), xi[0].cpu().numpy(), float(lls[0])
+
+    def table_states(self, table, offsets):
+        """The Viterbi path of every trial of the table in ONE launch: an int32 host array (n,)."""
+        from behavenet_amd import _hip
+        self._check_table(table)
+        offsets_d = self._offsets_d(table, offsets)
+        ll = self._loglik_table(table, offsets_d)
+        return _hip.hmm_viterbi(ll, offsets_d, self.log_Ps, self.log_pi0).cpu().numpy()
+
+    def most_likely_states(self, x):
+        table, offsets = self.as_table(x)
+        return self.table_states(table, offsets)

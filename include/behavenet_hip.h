@@ -762,6 +762,69 @@ size_t bn_softmax_cv_score_ws_bytes(int n, int D, int S, int M);
 int bn_softmax_cv_score(const float* z, int ld, const int* y, const int* fold, const double* W, const int* leave,
                         int n, int D, int S, int M, double* out, void* ws, size_t ws_bytes, bn_stream_t stream);
 
+/* EM for autoregressive hidden Markov models on a table of latents: the launches behind the second stage of the
+ * BehaveNet pipeline (fitting/arhmm_grid_search.py:132-209 drives the `ssm` library on the host copy of every frame).
+ * Gaussian AR observations with full covariance, L lags (L = 0: a plain Gaussian HMM), K states.
+ *
+ * Common operands.  z: fp32 table of n rows and D columns, row-major with leading dimension ld >= D, on any 4-byte
+ * boundary; never written.  c: D float64 values, the shift, or NULL for zeros.  offsets: DEVICE int64 (S + 1), made
+ * safe as bn_segment_gram makes them; segment s = trial s = the rows [e[s], e[s+1]).  Rows outside [e[0], e[S])
+ * belong to no trial: no call reads them and no call writes their rows of ll, gamma or states.  Within a trial, row t
+ * (counted from the trial's first row) is an INITIAL row if t < L and an AR row otherwise, and for an AR row
+ *   a_t = (1, x_t - c, x_{t-1} - c, ..., x_{t-L} - c)          float64, P = 1 + (L + 1) D entries
+ * Limits: 1 <= K <= 32, 0 <= L <= 8, D >= 1, (L + 1) D <= 64, n >= 0, S >= 0.  Everything but z is float64
+ * (states: int32).  No call uses global atomics, every output element named below is written exactly once, and the
+ * order of every sum is fixed by the shapes and the offsets: the same bits on every call.
+ *
+ * bn_arhmm_loglik -> ll (n, K).  G: (K, D, P) and cst: (K), the state's parameters folded by the caller:
+ * G_k = R_k [-(b_k + c-terms) | I | -A_k] with R_k^T R_k = Sigma_k^-1, cst_k = -D/2 log 2 pi + log det R_k.  For an AR
+ * row ll[t][k] = cst_k - 1/2 |G_k a_t|^2 (the (n x P) (P x K D) product on v_mfma_f64_16x16x4_f64, the squared norm
+ * over D taken in the epilogue); for an initial row ll[t][k] = -D/2 log 2 pi - 1/2 |x_t|^2 for every k (x_t not
+ * shifted).  A NaN or Inf in row t reaches the K values of row t and of the AR rows among the L rows after it in its
+ * trial (an initial row does not look back), and nothing else.  ws: bn_arhmm_loglik_ws_bytes bytes (the offsets and one byte a row).
+ *
+ * bn_hmm_forward_backward.  ll: (n, K) as above (any log-likelihoods), logP: (K, K) log transition matrix (row: from),
+ * logpi0: (K).  -> loglik (S): the log-likelihood of every trial, 0 for an empty trial; and, with want = 1,
+ * gamma (n, K): the posterior state marginals, and xi (S, K, K): per trial the sum over t of the pairwise posteriors
+ * p(z_t = i, z_{t+1} = j | trial), zeros for a trial of fewer than two rows.  With want = 0 (likelihood only) gamma
+ * and xi may be NULL and are never written.  One wave a trial, scaled recursion: the row maximum of ll is taken out
+ * before exp, alpha is normalised at every step and the log normalisers and maxima are summed, so a trial of
+ * thousands of rows with ll near -1e4 neither underflows nor loses the likelihood.  gamma holds alpha between the two
+ * sweeps.  A trial is one serial chain: the call's time is (longest trial) x (step latency).
+ * ws: bn_hmm_forward_backward_ws_bytes bytes (the offsets and two doubles a row).
+ *
+ * bn_arhmm_moments -> out (K, P, P): out[k] = sum over the AR rows of every trial of gamma[t][k] a_t^T a_t, both
+ * triangles with the same bits, out[k][0][0] the state's expected count over the AR rows; and gamma0 (K): the sum of
+ * gamma[t][k] over the initial rows (so sum_k (out[k][0][0] + gamma0[k]) is the number of rows in trials when gamma's
+ * rows sum to 1).  gamma: (n, K), never written.  The rows are cut into row blocks (a function of (n, D, L, K)
+ * alone), every (block, state) leaves one partial matrix in the workspace and the partials are added in block order.
+ * ws: bn_arhmm_moments_ws_bytes bytes (60 MiB of partials at most, the offsets and one byte a row).
+ *
+ * bn_hmm_viterbi -> states int32 (n): the most likely state path of every trial, max-sum in float64.  A tie goes to
+ * the lowest state, in every maximum over predecessors and at the trial's last row.  ws: bn_hmm_viterbi_ws_bytes
+ * bytes (the offsets and uint8 back-pointers (n, K)).
+ *
+ * Every ws on a 16-byte boundary; nothing is read from it that the call has not written.  S == 0 returns 0 and writes
+ * nothing.  BN_E_SHAPE (nothing written, to the outputs or to ws): K, L, D, n or S outside the limits (the queries
+ * return 0 for these), ld < D, want not 0 or 1, a workspace smaller than the query's, z off a 4-byte, states off a
+ * 4-byte, any float64 operand or offsets off an 8-byte, ws off a 16-byte boundary.  BN_E_BADARG: an operand NULL (c
+ * may be; gamma and xi may be with want = 0). */
+size_t bn_arhmm_loglik_ws_bytes(int n, int S, int D, int L, int K);
+int bn_arhmm_loglik(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L, int K,
+                    int n, const double* G, const double* cst, double* ll, void* ws, size_t ws_bytes,
+                    bn_stream_t stream);
+size_t bn_hmm_forward_backward_ws_bytes(int n, int S, int K);
+int bn_hmm_forward_backward(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
+                            const double* logpi0, int want, double* gamma, double* xi, double* loglik, void* ws,
+                            size_t ws_bytes, bn_stream_t stream);
+size_t bn_arhmm_moments_ws_bytes(int n, int S, int D, int L, int K);
+int bn_arhmm_moments(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L, int K,
+                     int n, const double* gamma, double* out, double* gamma0, void* ws, size_t ws_bytes,
+                     bn_stream_t stream);
+size_t bn_hmm_viterbi_ws_bytes(int n, int S, int K);
+int bn_hmm_viterbi(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
+                   const double* logpi0, int* states, void* ws, size_t ws_bytes, bn_stream_t stream);
+
 /* unit-float frames -> stored uint8 grey levels, the inverse of bn_u8_to_unit_float on k / 255:
  *   out[i] = NaN -> 0, else clamp(rint(in[i] * 255), 0, 255)
  * The product is one fp32 multiplication and rint rounds half to even, i.e. numpy's
