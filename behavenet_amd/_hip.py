@@ -176,6 +176,9 @@ SIGNATURES = {
                          + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
     'bn_hmm_viterbi_ws_bytes': (_c_size_t, [_c_int] * 3),
     'bn_hmm_viterbi': (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 3 + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
+    'bn_arhmm_sample_ws_bytes': (_c_size_t, [_c_int] * 5),
+    'bn_arhmm_sample': (_c_int, [_c_void_p] * 5 + [_c_int] * 5 + [_c_void_p] * 4 + [_c_int] + [_c_void_p] * 3
+                        + [_c_size_t, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
     'bn_prof_read': (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
@@ -1687,6 +1690,84 @@ def hmm_viterbi(ll, offsets, log_Ps, log_pi0):
                                   states.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes, _stream()),
                'bn_hmm_viterbi')
     return states
+
+
+def arhmm_sample(W, C, cdf0, cdf, offsets, eps, u=None, states=None, init=None, x=None, states_out=None):
+    """Latents and states drawn from an ARHMM's generative process with the noise the caller brings
+    (``bn_arhmm_sample``): ``(x, states)``, float64 (n, D) and int32 (n) DEVICE tensors.  ``W`` (K, D, 1 + L D),
+    ``C`` (K, D, D), ``cdf0`` (K) and ``cdf`` (K, K): ``models.arhmm.ARHMM.generative``, float64, host arrays are
+    uploaded.  ``eps``: float64 DEVICE (n, D) standard normals.  Exactly one of ``u``, float64 DEVICE (n,) uniforms in
+    [0, 1) -- the states are sampled -- and ``states``, int32 DEVICE (n,) -- the states are given, and one device
+    reduction checks their range over the trials' rows first: a state outside [0, K) is a ValueError and nothing is
+    launched.  ``init``: None or an fp32 DEVICE table (n, D) (a row stride is served) whose rows are a trial's first L
+    rows; without it those are ``eps``.  Rows outside the trials are left as they are (zeros in fresh outputs; ``x``
+    and ``states_out`` may be given).  No random number is drawn here: the same operands give the same bits."""
+    who = 'arhmm_sample'
+    if not torch.is_tensor(eps) or eps.dim() != 2 or eps.dtype != torch.float64:
+        raise ValueError('%s: expected eps float64 (n, D) on the device, got %s'
+                         % (who, (eps.dtype, tuple(eps.shape)) if torch.is_tensor(eps) else type(eps).__name__))
+    if not eps.is_cuda:
+        raise ValueError('%s: expected eps on the GPU, got device %s (the HIP path has no CPU fallback)'
+                         % (who, eps.device))
+    n, D = (int(v) for v in eps.shape)
+    if not torch.is_tensor(W) and np.ndim(W) != 3 or torch.is_tensor(W) and W.dim() != 3:
+        raise ValueError('%s: expected W float64 (K, D, 1 + L D)' % who)
+    K, cols = int(W.shape[0]), int(W.shape[2])
+    if int(W.shape[1]) != D or (cols - 1) % D:
+        raise ValueError('%s: W %s does not go with eps (n, %d)' % (who, tuple(W.shape), D))
+    L = (cols - 1) // D
+    check_arhmm_dims(who, D, L, K)
+    if (u is None) == (states is None):
+        raise ValueError('%s: exactly one of u (the states are sampled) and states (they are given)' % who)
+    dev = eps.device
+    W = _f64_operand(who, 'W', W, (K, D, cols), dev)
+    C = _f64_operand(who, 'C', C, (K, D, D), dev)
+    cdf0 = _f64_operand(who, 'cdf0', cdf0, (K,), dev)
+    cdf = _f64_operand(who, 'cdf', cdf, (K, K), dev)
+    eps = _f64_operand(who, 'eps', eps, (n, D), dev)
+    u = _f64_operand(who, 'u', u, (n,), dev, allow_none=True)
+    offsets = _trial_offsets(who, offsets, dev)
+    S = int(offsets.numel()) - 1
+    if states is not None:
+        if not torch.is_tensor(states) or states.dtype != torch.int32 or tuple(states.shape) != (n,) \
+                or states.device != dev:
+            raise ValueError('%s: expected states int32 (%d,) on %s' % (who, n, dev))
+        states = states.contiguous()
+    ld_init = D
+    if init is not None:
+        ni, di, ld_init = _column_table(who, init)
+        if (ni, di) != (n, D) or init.device != dev:
+            raise ValueError('%s: expected init float32 (%d, %d) on %s, got %s on %s'
+                             % (who, n, D, dev, tuple(init.shape), init.device))
+    if x is None:
+        x = torch.zeros((n, D), dtype=torch.float64, device=dev)
+    elif x.dtype != torch.float64 or tuple(x.shape) != (n, D) or x.device != dev or not x.is_contiguous():
+        raise ValueError('%s: expected x float64 (%d, %d) on %s' % (who, n, D, dev))
+    if states_out is None:
+        states_out = torch.zeros((n,), dtype=torch.int32, device=dev)
+    elif states_out.dtype != torch.int32 or tuple(states_out.shape) != (n,) or states_out.device != dev \
+            or not states_out.is_contiguous():
+        raise ValueError('%s: expected states_out int32 (%d,) on %s' % (who, n, dev))
+    if not S or not n:
+        return x, states_out
+    if states is not None:
+        # the rows the launch would read: [e[0], e[S]) of the offsets made safe (clamped, non-decreasing)
+        e = torch.cummax(offsets.clamp(0, n), dim=0)[0]
+        lo, hi = int(e[0]), int(e[-1])
+        if hi > lo:
+            mn, mx = torch.aminmax(states[lo:hi])
+            mn, mx = int(mn), int(mx)
+            if mn < 0 or mx >= K:
+                raise ValueError('%s: states from %d to %d, the model has the states 0 to %d' % (who, mn, mx, K - 1))
+    lib = load()
+    nbytes = lib.bn_arhmm_sample_ws_bytes(n, S, D, L, K)
+    _check(lib.bn_arhmm_sample(W.data_ptr(), C.data_ptr(), cdf0.data_ptr(), cdf.data_ptr(), offsets.data_ptr(), S, D,
+                               L, K, n, eps.data_ptr(), None if u is None else u.data_ptr(),
+                               None if states is None else states.data_ptr(),
+                               None if init is None else init.data_ptr(), ld_init, x.data_ptr(),
+                               states_out.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes, _stream()),
+           'bn_arhmm_sample')
+    return x, states_out
 
 
 def recon_panels_u8(orig, recon, mask=None, show_orig=True, out=None, row=0, n_rows=1):

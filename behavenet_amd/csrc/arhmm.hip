@@ -41,7 +41,28 @@
 // k_hmm_viterbi  max-sum, one wave a trial, the lane layout of k_hmm_fb; uint8 back-pointers (n, K) in the workspace;
 //                a tie goes to the lowest state (strict > in ascending order).  The walk back runs on lane 0 over
 //                64 rows of back-pointers at a time, copied into LDS by the whole wave.
-// No global atomics; every output element is written exactly once.
+// Sampling (bn_arhmm_sample; the caller brings the noise, no random number is drawn here):
+// k_ars_states   the state chain of a trial from its uniforms, one wave a trial.  The K cumulative rows and cdf0 sit
+//                in LDS; lane j < K - 1 compares u_t with entry j of row z_{t-1} and the state is the number of lanes
+//                that say u_t >= cdf (a ballot and a bit count: comparisons only, the host's path bit for bit).  64
+//                uniforms are staged a time and lane i keeps the state of the chunk's row i, so the stores coalesce.
+//                The wave walks every row of its trial, so it leaves the trial's number a row in the workspace too.
+// k_ars_given    given states: copied out, one wave a trial, with the trial's number a row, and the first row whose
+//                state is outside [0, K) is left in the workspace (INT_MAX for none, which k_ars_states writes).
+// k_ars_drive    every row at once, one thread an element (the row's trial is in the workspace: no search): NaN from
+//                the trial's first bad state on, init or eps for an initial row, else v_t = b_z + C_z eps_t (j
+//                ascending, one FMA a term), written into x.  It reads C transposed (k_ars_transpose, into the
+//                workspace): the threads of a row then read neighbouring doubles where the rows of C_z lie D apart
+//                (measured on 4.8 10^6 x 16: 3.0 ms with C as it comes, one cache line a lane and load).
+// k_ars_recur    x_t = v_t + sum_l A_z[l] x_{t-1-l}, one wave a trial, L > 0 only.  A window of 64 rows of v and the L
+//                rows before it sit in LDS and the rows are finished in place, so a step reads and writes LDS only
+//                and the window leaves in one coalesced sweep.  Lane (d, p) = (lane / NP, lane % NP) takes the
+//                history entries p, p + NP, ... of output row d (NP = 8, 4, 2 for D up to 8, 16, 32) in ascending
+//                order; the NP partial sums of a row are neighbours and are added by DPP moves (xor 1, xor 2, the
+//                other half of eight): a fixed tree, the same bits on every call.  Row z of A comes from global
+//                memory (L2) into registers one step ahead, and only when the state changes.
+// No global atomics; every output element is written exactly once by each kernel that owns it.
+#include <limits.h>
 #include <math.h>
 #include "bn_common.h"
 #include "bn_launch.h"
@@ -60,6 +81,8 @@
 #define AR_MO_TARGET_BLOCKS 1024            // row blocks at most ...
 #define AR_MO_SLAB_BYTES (60u << 20)        // ... and no more than fit K partials each into 60 MiB
 #define AR_BT_ROWS 64                       // rows of back-pointers the walk back holds in LDS
+#define AR_S_ROWS 64                        // sampling: rows of a window (k_ars_recur), uniforms of a chunk
+#define AR_S_MAX_D 32                       // D at most where L > 0
 
 typedef double ar_d4 __attribute__((ext_vector_type(4)));
 
@@ -545,6 +568,186 @@ __global__ __launch_bounds__(256) void k_ar_gamma0(const double* __restrict__ ga
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// sampling
+template <int KP>
+__global__ __launch_bounds__(BN_WAVE) void k_ars_states(const double* __restrict__ u, const int* __restrict__ e, int K,
+                                                        const double* __restrict__ cdf0,
+                                                        const double* __restrict__ cdf, int* __restrict__ states,
+                                                        int* __restrict__ bad, int* __restrict__ trial) {
+    __shared__ double rows[(KP + 1) * KP];                 // row K: cdf0
+    __shared__ double ub[AR_S_ROWS];
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int beg = e[s], T = e[s + 1] - beg;
+    if (lane == 0) bad[s] = INT_MAX;
+    if (T <= 0) return;
+    for (int idx = lane; idx < (K + 1) * K; idx += BN_WAVE) rows[idx] = idx < K * K ? cdf[idx] : cdf0[idx - K * K];
+    const bool cmp = lane < K - 1;                         // (the last column is never compared)
+    int z = K;
+    for (int t0 = 0; t0 < T; t0 += AR_S_ROWS) {
+        const int cnt = T - t0 < AR_S_ROWS ? T - t0 : AR_S_ROWS;
+        __syncthreads();                                   // (the chunk before this one has been read; rows is there)
+        if (lane < cnt) ub[lane] = u[(size_t)beg + t0 + lane];
+        __syncthreads();
+        int mine = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const double uu = ub[i];
+            const bool ge = cmp && uu >= rows[z * K + (cmp ? lane : 0)];
+            z = __popcll(__ballot(ge));
+            mine = lane == i ? z : mine;
+        }
+        if (lane < cnt) {
+            states[(size_t)beg + t0 + lane] = mine;
+            trial[(size_t)beg + t0 + lane] = s;
+        }
+    }
+}
+
+__global__ __launch_bounds__(BN_WAVE) void k_ars_given(const int* __restrict__ zin, const int* __restrict__ e, int K,
+                                                       int* __restrict__ states, int* __restrict__ bad,
+                                                       int* __restrict__ trial) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int beg = e[s], T = e[s + 1] - beg;
+    int first = INT_MAX;
+    for (int t = lane; t < T; t += BN_WAVE) {
+        const int z = zin[(size_t)beg + t];
+        states[(size_t)beg + t] = z;
+        trial[(size_t)beg + t] = s;
+        if ((z < 0 || z >= K) && first == INT_MAX) first = t;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int other = __shfl_xor(first, o);
+        first = other < first ? other : first;
+    }
+    if (lane == 0) bad[s] = first;
+}
+
+// ct[k][j][d] = C[k][d][j]: the threads of k_ars_drive that share a row are neighbours in d
+__global__ __launch_bounds__(256) void k_ars_transpose(const double* __restrict__ C, int D, int total,
+                                                       double* __restrict__ ct) {
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= total) return;
+    const int d = o % D, kj = o / D, j = kj % D, k = kj / D;
+    ct[o] = C[((size_t)k * D + d) * D + j];
+}
+
+__global__ __launch_bounds__(256) void k_ars_drive(const double* __restrict__ W, const double* __restrict__ ct,
+                                                   const int* __restrict__ e, const int* __restrict__ bad,
+                                                   const int* __restrict__ trial, int S, int D, int L, int n,
+                                                   const double* __restrict__ eps,
+                                                   const float* __restrict__ init, int ldi,
+                                                   const int* __restrict__ states, double* __restrict__ x) {
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    const long r = gid / D;
+    if (r >= n || r < e[0] || r >= e[S]) return;
+    const int d = (int)(gid - r * D);
+    const int lo = trial[r];                               // (left by the state pass, which walks every row of a trial)
+    const long t = r - e[lo];
+    double v;
+    if (t >= bad[lo]) {
+        v = __builtin_nan("");
+    } else if (t < L) {
+        v = init ? (double)init[(size_t)r * ldi + d] : eps[(size_t)r * D + d];
+    } else {
+        const int z = states[r];
+        const double* c = ct + (size_t)z * D * D + d;
+        const double* ep = eps + (size_t)r * D;
+        v = W[((size_t)z * D + d) * (1 + (size_t)L * D)];
+        for (int j = 0; j < D; ++j) v = fma(c[(size_t)j * D], ep[j], v);
+    }
+    x[(size_t)r * D + d] = v;
+}
+
+// the value of the lane a DPP control names (quad_perm, row_half_mirror), both halves of the double
+template <int CTRL>
+__device__ __forceinline__ double ars_dpp(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+
+template <int EL>
+__global__ __launch_bounds__(BN_WAVE) void k_ars_recur(const double* __restrict__ W, const int* __restrict__ e,
+                                                       const int* __restrict__ bad, int D, int L, int NP,
+                                                       const int* __restrict__ states, double* __restrict__ x) {
+    constexpr int ZERO = (AR_S_ROWS + AR_MAX_L) * AR_S_MAX_D;          // a 0.0 for the lanes without an entry
+    __shared__ double xb[ZERO + 1];                                    // rows t0 - L .. t0 + 63 of the trial
+    __shared__ int zb[AR_S_ROWS + 1];                                  // states of rows t0 .. t0 + 64
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int beg = e[s];
+    int T = e[s + 1] - beg;
+    T = bad[s] < T ? bad[s] : T;                           // (the rows from a bad state on are NaN already)
+    if (T <= L) return;
+    const int H = L * D, P1 = 1 + H;
+    const int d = lane / NP, p = lane - d * NP;
+    const bool row = d < D;
+    // every lane reads EL history entries and EL entries of A a step, all of them at addresses that exist: a lane
+    // without an entry (h >= H, or no output row) reads the 0.0 at ZERO and column 0 of A and multiplies by 0.0
+    int off[EL], col[EL];
+    bool ok[EL];
+#pragma unroll
+    for (int i = 0; i < EL; ++i) {
+        const int h = p + i * NP;
+        ok[i] = row && h < H;
+        const int l = ok[i] ? h / D : 0, j = ok[i] ? h - l * D : 0;
+        off[i] = j - l * D;                                // x_{t-1-l}[j] from the row of x_{t-1}
+        col[i] = ok[i] ? 1 + h : 0;
+    }
+    double* xg = x + (size_t)beg * D;
+    const int* zs = states + beg;
+    for (int idx = lane; idx < H; idx += BN_WAVE) xb[idx] = xg[idx];
+    if (lane == 0) xb[ZERO] = 0.0;
+
+    int zc = zs[L];
+    const double* wz = W + ((size_t)zc * D + (row ? d : 0)) * P1;
+    double a[EL];
+#pragma unroll
+    for (int i = 0; i < EL; ++i) {
+        const double w = wz[col[i]];
+        a[i] = ok[i] ? w : 0.0;
+    }
+
+    for (int t0 = L; t0 < T; t0 += AR_S_ROWS) {
+        const int cnt = T - t0 < AR_S_ROWS ? T - t0 : AR_S_ROWS;
+        for (int idx = lane; idx < cnt * D; idx += BN_WAVE) xb[H + idx] = xg[(size_t)t0 * D + idx];
+        for (int idx = lane; idx <= cnt; idx += BN_WAVE) zb[idx] = t0 + idx < T ? zs[t0 + idx] : zc;
+        __syncthreads();
+        for (int i = 0; i < cnt; ++i) {
+            const int base = (L + i - 1) * D;              // the row of x_{t-1}
+            const int zn = zb[i + 1];
+            const double v = xb[row ? base + D + d : ZERO];
+            double hv[EL];
+#pragma unroll
+            for (int k = 0; k < EL; ++k) hv[k] = xb[ok[k] ? base + off[k] : ZERO];
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < EL; ++k) acc = fma(a[k], hv[k], acc);
+            // A of the next row, asked for before the partial sums are added (same state: same registers)
+            if (zn != zc) {
+                zc = zn;
+                wz = W + ((size_t)zc * D + (row ? d : 0)) * P1;
+#pragma unroll
+                for (int k = 0; k < EL; ++k) {
+                    const double w = wz[col[k]];
+                    a[k] = ok[k] ? w : 0.0;
+                }
+            }
+            acc += ars_dpp<0xB1>(acc);                     // quad_perm [1, 0, 3, 2]: lane ^ 1
+            if (NP >= 4) acc += ars_dpp<0x4E>(acc);        // quad_perm [2, 3, 0, 1]: lane ^ 2
+            if (NP >= 8) acc += ars_dpp<0x141>(acc);       // row_half_mirror: the other four of the eight
+            if (row && p == 0) xb[base + D + d] = v + acc;
+            __syncthreads();
+        }
+        for (int idx = lane; idx < cnt * D; idx += BN_WAVE) xg[(size_t)t0 * D + idx] = xb[H + idx];
+        if (t0 + cnt < T) {                                // the window's last L rows are the next one's history
+            const double keep = lane < H ? xb[cnt * D + lane] : 0.0;
+            __syncthreads();
+            if (lane < H) xb[lane] = keep;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 bool bn_arhmm_ok(int n, int S, int D, int L, int K) {
     return n >= 0 && S >= 0 && S < INT32_MAX && ar_dims_ok(D, L, K);
 }
@@ -666,6 +869,55 @@ int bn_launch_hmm_viterbi(const double* ll, const long long* offsets, int S, int
     else if (K <= 8) hipLaunchKernelGGL(k_hmm_viterbi<8>, grid, block, 0, st, ll, ce, K, logP, logpi0, states, bp);
     else if (K <= 16) hipLaunchKernelGGL(k_hmm_viterbi<16>, grid, block, 0, st, ll, ce, K, logP, logpi0, states, bp);
     else hipLaunchKernelGGL(k_hmm_viterbi<32>, grid, block, 0, st, ll, ce, K, logP, logpi0, states, bp);
+    BN_LAUNCH_CHECK();
+    return 0;
+}
+
+size_t bn_arhmm_sample_ws_bytes_impl(int n, int S, int D, int L, int K) {
+    if (!bn_arhmm_ok(n, S, D, L, K)) return 0;
+    return ar_offsets_bytes(S) + ar_pad16((size_t)S * sizeof(int)) + ar_pad16((size_t)n * sizeof(int)) +
+           (size_t)K * D * D * sizeof(double);
+}
+
+int bn_launch_arhmm_sample(const double* W, const double* C, const double* cdf0, const double* cdf,
+                           const long long* offsets, int S, int D, int L, int K, int n, const double* eps,
+                           const double* u, const int* states_in, const float* init, int ld_init, double* x,
+                           int* states, void* ws, hipStream_t st) {
+    if (!bn_arhmm_ok(n, S, D, L, K)) return BN_E_SHAPE;
+    if (S == 0) return 0;
+    int* e = reinterpret_cast<int*>(ws);
+    int* bad = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + ar_offsets_bytes(S));
+    int* trial = bad + ar_pad16((size_t)S * sizeof(int)) / sizeof(int);
+    double* ct = reinterpret_cast<double*>(trial + ar_pad16((size_t)n * sizeof(int)) / sizeof(int));
+    const int rc = bn_launch_segment_offsets(offsets, S + 1, n, e, st);
+    if (rc) return rc;
+    const dim3 grid((unsigned)S), block(BN_WAVE);
+    const int* ce = e;
+    const int* cbad = bad;
+    if (states_in) hipLaunchKernelGGL(k_ars_given, grid, block, 0, st, states_in, ce, K, states, bad, trial);
+    else if (K <= 4) hipLaunchKernelGGL(k_ars_states<4>, grid, block, 0, st, u, ce, K, cdf0, cdf, states, bad, trial);
+    else if (K <= 8) hipLaunchKernelGGL(k_ars_states<8>, grid, block, 0, st, u, ce, K, cdf0, cdf, states, bad, trial);
+    else if (K <= 16) hipLaunchKernelGGL(k_ars_states<16>, grid, block, 0, st, u, ce, K, cdf0, cdf, states, bad, trial);
+    else hipLaunchKernelGGL(k_ars_states<32>, grid, block, 0, st, u, ce, K, cdf0, cdf, states, bad, trial);
+    BN_LAUNCH_CHECK();
+    if (!n) return 0;
+    const int cells = K * D * D;
+    hipLaunchKernelGGL(k_ars_transpose, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, C, D, cells, ct);
+    BN_LAUNCH_CHECK();
+    const long elems = (long)n * D;
+    hipLaunchKernelGGL(k_ars_drive, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, W, (const double*)ct, ce,
+                       cbad, (const int*)trial, S, D, L, n, eps, init, ld_init, (const int*)states, x);
+    BN_LAUNCH_CHECK();
+    if (L == 0) return 0;
+    // lanes (d, p): NP partial sums a row, EL history entries a lane at most
+    const int NP = D <= 8 ? 8 : (D <= 16 ? 4 : 2), EL = (L * D + NP - 1) / NP;
+    const int* cs = states;
+    if (EL <= 1) hipLaunchKernelGGL(k_ars_recur<1>, grid, block, 0, st, W, ce, cbad, D, L, NP, cs, x);
+    else if (EL <= 2) hipLaunchKernelGGL(k_ars_recur<2>, grid, block, 0, st, W, ce, cbad, D, L, NP, cs, x);
+    else if (EL <= 4) hipLaunchKernelGGL(k_ars_recur<4>, grid, block, 0, st, W, ce, cbad, D, L, NP, cs, x);
+    else if (EL <= 8) hipLaunchKernelGGL(k_ars_recur<8>, grid, block, 0, st, W, ce, cbad, D, L, NP, cs, x);
+    else if (EL <= 16) hipLaunchKernelGGL(k_ars_recur<16>, grid, block, 0, st, W, ce, cbad, D, L, NP, cs, x);
+    else hipLaunchKernelGGL(k_ars_recur<24>, grid, block, 0, st, W, ce, cbad, D, L, NP, cs, x);
     BN_LAUNCH_CHECK();
     return 0;
 }

@@ -155,6 +155,12 @@ int bn_launch_hmm_forward_backward(const double* ll, const long long* offsets, i
                                    double* loglik, void* ws, hipStream_t st);
 int bn_launch_hmm_viterbi(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
                           const double* logpi0, int* states, void* ws, hipStream_t st);
+// ... and the model's generative process from the caller's noise: states from uniforms (or given), latents from normals
+size_t bn_arhmm_sample_ws_bytes_impl(int n, int S, int D, int L, int K);
+int bn_launch_arhmm_sample(const double* W, const double* C, const double* cdf0, const double* cdf,
+                           const long long* offsets, int S, int D, int L, int K, int n, const double* eps,
+                           const double* u, const int* states_in, const float* init, int ld_init, double* x,
+                           int* states, void* ws, hipStream_t st);
 
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);

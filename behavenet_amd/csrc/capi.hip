@@ -2155,6 +2155,26 @@ extern "C" int bn_hmm_viterbi(const double* ll, const long long* offsets, int S,
     return bn_launch_hmm_viterbi(ll, offsets, S, K, n, logP, logpi0, states, ws, (hipStream_t)stream);
 }
 
+extern "C" size_t bn_arhmm_sample_ws_bytes(int n, int S, int D, int L, int K) {
+    return bn_arhmm_sample_ws_bytes_impl(n, S, D, L, K);
+}
+
+extern "C" int bn_arhmm_sample(const double* W, const double* C, const double* cdf0, const double* cdf,
+                               const long long* offsets, int S, int D, int L, int K, int n, const double* eps,
+                               const double* u, const int* states_in, const float* init, int ld_init, double* x,
+                               int* states, void* ws, size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_arhmm_ok(n, S, D, L, K) || (init && ld_init < D)) return BN_E_SHAPE;
+    if (!W || !C || !cdf0 || !cdf || !offsets || !eps || !x || !states || !ws) return BN_E_BADARG;
+    if (!u == !states_in) return BN_E_BADARG;              // exactly one of the two
+    if (((uintptr_t)W & 7) || ((uintptr_t)C & 7) || ((uintptr_t)cdf0 & 7) || ((uintptr_t)cdf & 7) ||
+        ((uintptr_t)offsets & 7) || ((uintptr_t)eps & 7) || ((uintptr_t)u & 7) || ((uintptr_t)states_in & 3) ||
+        ((uintptr_t)init & 3) || ((uintptr_t)x & 7) || ((uintptr_t)states & 3) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_arhmm_sample_ws_bytes_impl(n, S, D, L, K)) return BN_E_SHAPE;
+    return bn_launch_arhmm_sample(W, C, cdf0, cdf, offsets, S, D, L, K, n, eps, u, states_in, init, ld_init, x, states,
+                                  ws, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // fp32 unit-float frames -> stored uint8 grey levels (recon_u8.hip): NaN -> 0, else clamp(rint(x * 255), 0, 255).
 extern "C" int bn_unit_float_to_u8(const float* in, unsigned char* out, size_t n, bn_stream_t stream) {

@@ -2252,3 +2252,123 @@ def export_arhmm(data_generator, model, **kwargs):
     with open(path, 'wb') as f:
         pickle.dump(arhmm, f)
     return arhmm, rows, path, export_states(hparams, data_generator, arhmm, model=model)
+
+
+# ------------------------------------------------------------------------------------------ ARHMM samples
+def sample_arhmm(data_generator, model, arhmm, n_samples=50, conditional=True, dtype='test', sess_idx=None,
+                 data_key='ae_latents', seed=0):
+    """Real and sampled latents of a fitted ARHMM: the dict of the reference's ``get_model_latents_states``
+    (plotting/arhmm_utils.py:134-251) without its ``model`` entry.
+
+    ``latents``, ``states`` and ``trial_idxs``: per split (train / val / test) the trials of the sessions ``sess_idx``
+    in ``_corr_trial_order``'s order, as host arrays (fp32 latents, int32 Viterbi paths -- ONE ``table_states`` launch
+    a split) and ``(session, trial)`` pairs -- the trial numbers alone when one session is asked for, as in the
+    reference.  ``latents_gen``: with ``conditional`` one sampled trial per real trial of ``dtype``, drawn along its
+    most likely states with the real trial's first ``lags`` rows (``ARHMM.sample_conditional``), and ``states_gen`` is
+    ``[]``; else ``n_samples`` fully generated trials as long as the first trial of ``dtype``, 200 burn-in rows
+    dropped (``ARHMM.sample``), with their states.  ``n_samples = 0`` returns two empty lists.  The draws are
+    reproducible for a given ``seed``, device and torch build only (``ARHMM.sample_table``).
+
+    Departures from the reference: the initial rows of a conditional sample are the real trial's (the reference
+    seeds row 0 from the first real latent through ``sample_x``) and those of a generated trial N(0, I); parity with
+    the ``ssm`` library is unchecked."""
+    who = 'sample_arhmm'
+    _splits(who, dtype)
+    if data_key == 'ae_latents':
+        _export_setup(model)
+    wanted = _wanted_sessions(who, data_generator, sess_idx)
+    parts = _arhmm_trials(who, data_generator, model, data_key, ('train', 'val', 'test'), wanted)
+    idxs = [ds.batch_idxs for ds in data_generator.datasets]
+    out = {'latents': {}, 'states': {}, 'trial_idxs': {}, 'latents_gen': [], 'states_gen': []}
+    for dt in ('train', 'val', 'test'):
+        table, offsets, sess, trials = _arhmm_split(parts, _corr_trial_order(idxs, [dt], wanted))
+        n = len(sess)
+        if table is not None:
+            path = arhmm.table_states(table, offsets)
+            host = table.cpu().numpy()
+        else:
+            path, host = np.zeros((0,), dtype=np.int32), np.zeros((0, arhmm.D), dtype=np.float32)
+        out['latents'][dt] = [host[offsets[i]:offsets[i + 1]].copy() for i in range(n)]
+        out['states'][dt] = [path[offsets[i]:offsets[i + 1]].copy() for i in range(n)]
+        out['trial_idxs'][dt] = trials.copy() if len(wanted) == 1 else list(zip(sess.tolist(), trials.tolist()))
+    if int(n_samples) > 0:
+        real = out['latents'][dtype]
+        if not real:
+            raise ValueError('%s: no %s trials to sample by' % (who, dtype))
+        if conditional:
+            _, out['latents_gen'] = arhmm.sample_conditional(real, seed=seed)
+        else:
+            out['states_gen'], out['latents_gen'] = arhmm.sample(real[0].shape[0], n_samples=int(n_samples),
+                                                                 burn_in=200, seed=seed)
+    return out
+
+
+def real_vs_sampled_plan(lengths, max_frames, n_buffer):
+    """Source rows of one column of the real-vs-sampled movie: trials of ``lengths`` frames are appended, each followed
+    by ``n_buffer`` blank frames, until there are at least ``max_frames`` frames (the reference's
+    ``while ims.shape[0] < max_frames`` loop, plotting/arhmm_utils.py:598-619).  -> ``(src, n_trials)``: per movie
+    frame the row of the table of the first ``n_trials`` trials stacked, -1 for a blank frame.  Running out of trials is
+    a ValueError (the reference's IndexError)."""
+    src, used, rows = [], 0, 0
+    while len(src) < max_frames:
+        if used >= len(lengths):
+            raise ValueError('real_vs_sampled_movie: %d trials give %d frames, max_frames is %d'
+                             % (len(lengths), len(src), max_frames))
+        src.extend(range(rows, rows + int(lengths[used])))
+        src.extend([-1] * n_buffer)
+        rows += int(lengths[used])
+        used += 1
+    return np.asarray(src, dtype=np.int64), used
+
+
+def real_vs_sampled_movie_device(model, latents, latents_gen, max_frames=400, n_buffer=5, labels_0=None,
+                                 apply_inverse_transform=True, chunk_size=200):
+    """The frames of the reference's real-vs-sampled movie (``real_vs_sampled_wrapper`` /
+    ``make_real_vs_sampled_movies``, plotting/arhmm_utils.py:513-700) as a uint8 DEVICE tensor ``(T, C * H, 2 * W)``:
+    the left column plays the decoded real latents ``latents`` (a list of (T_i, D) trials), the right the decoded
+    samples ``latents_gen``; the channels of a frame are stacked vertically, as the reference's
+    ``np.concatenate(..., axis=1)`` stacks them.
+
+    Per column trials are appended until there are at least ``max_frames`` frames, ``n_buffer`` all-zero frames after
+    every trial, the last one included (``real_vs_sampled_plan``); ``T`` is the smaller of the two counts.  Running out
+    of trials before ``max_frames`` is a ValueError that says how many frames there were.  The rows of the trials
+    used are decoded in ONE batched pass (``decode_points_device``, which honours ``hparams['hip_decode_dtype']``)
+    and tiled by one mosaic launch per ``chunk_size`` movie frames (``_hip.frame_mosaic_u8`` on the frames viewed as
+    ``(P * C, 1, H, W)``); only the movie crosses to the host.  ``labels_0``: the labels of a cond-AE / cond-VAE, one
+    row for all frames."""
+    max_frames, n_buffer, chunk_size = int(max_frames), int(n_buffer), int(chunk_size)
+    if max_frames < 1 or n_buffer < 0 or chunk_size < 1:
+        raise ValueError('real_vs_sampled_movie: max_frames %d, n_buffer %d, chunk_size %d'
+                         % (max_frames, n_buffer, chunk_size))
+    sides, tables = [], []
+    rows = 0
+    for trials in (latents, latents_gen):
+        trials = [t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in trials]
+        for t in trials:
+            if t.ndim != 2:
+                raise ValueError('real_vs_sampled_movie: a trial must be (T, D), got %s' % (t.shape,))
+        src, used = real_vs_sampled_plan([len(t) for t in trials], max_frames, n_buffer)
+        sides.append(np.where(src >= 0, src + rows, -1))
+        tables.extend(np.asarray(t, dtype=np.float32) for t in trials[:used])
+        rows += sum(len(t) for t in trials[:used])
+    n_t = min(len(sides[0]), len(sides[1]))
+    table = np.ascontiguousarray(np.concatenate(tables, axis=0))
+    if not len(table):
+        raise ValueError('real_vs_sampled_movie: the trials have no frames')
+    frames = decode_points_device(model, table, labels_0, apply_inverse_transform, chunk_size)
+    P, C, H, W = frames.shape
+    planes = frames.contiguous().view(P * C, 1, H, W)
+
+    def src_of(beg, end):
+        # mosaic row c of column q shows channel c of the column's frame: plane s * C + c
+        s = np.stack([sides[0][beg:end], sides[1][beg:end]], axis=1)                  # (t, 2)
+        src = np.where(s[:, None, :] >= 0, s[:, None, :] * C + np.arange(C)[None, :, None], -1)
+        return src.astype(np.int32)                                                   # (t, C, 2)
+    return _mosaic_in_chunks(planes, src_of, n_t, 0, None, chunk_size)
+
+
+def real_vs_sampled_movie(model, latents, latents_gen, max_frames=400, n_buffer=5, labels_0=None,
+                          apply_inverse_transform=True, chunk_size=200):
+    """``real_vs_sampled_movie_device`` as a numpy array ``(T, C * H, 2 * W)`` of uint8."""
+    return real_vs_sampled_movie_device(model, latents, latents_gen, max_frames, n_buffer, labels_0,
+                                        apply_inverse_transform, chunk_size).cpu().numpy()

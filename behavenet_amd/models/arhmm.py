@@ -318,3 +318,89 @@ class ARHMM(object):
     def most_likely_states(self, x):
         table, offsets = self.as_table(x)
         return self.table_states(table, offsets)
+
+    # ------------------------------------------------------------------------------------------------------
+    # the generative process (bn_arhmm_sample)
+    # ------------------------------------------------------------------------------------------------------
+    def generative(self):
+        """``(W, C, cdf0, cdf)`` for ``bn_arhmm_sample``, host float64: ``W[k] = [b_k | A_k]`` (K, D, 1 + L D) in the
+        model's own coordinates, ``C[k]`` the lower Cholesky factor of ``Sigma_k``, ``cdf0`` the cumulative sum in
+        state order of ``exp(log_pi0)`` and ``cdf`` the same for every row of ``exp(log_Ps)``."""
+        K, D = self.K, self.D
+        W = np.concatenate([self.bs[:, :, None], self.As], axis=2).astype(np.float64)
+        C = np.zeros((K, D, D))
+        for k in range(K):
+            try:
+                C[k] = np.linalg.cholesky(self.Sigmas[k])
+            except np.linalg.LinAlgError:
+                raise ValueError('ARHMM.generative: Sigmas[%d] is not positive definite' % k)
+            if not np.all(np.isfinite(C[k])):
+                raise ValueError('ARHMM.generative: Sigmas[%d] is not finite' % k)
+        return (np.ascontiguousarray(W), C, np.cumsum(np.exp(self.log_pi0)),
+                np.cumsum(np.exp(self.log_Ps), axis=1))
+
+    def sample_table(self, offsets, seed=0, states=None, init=None, device=None):
+        """Latents and states of the trials ``offsets`` (int64 (S + 1), rows of ONE table of ``offsets[-1]`` rows)
+        drawn from the model in ONE launch: ``(x, states)``, float64 (n, D) and int32 (n) device tensors.
+
+        The noise comes from a ``torch.Generator`` on the device seeded with ``seed``: ``eps`` (n, D) standard normals
+        first, then -- when ``states`` is None -- ``u`` (n) uniforms, both float64.  So the draws are reproducible for
+        a given seed, device and torch build only; that is torch's generator, the launch itself is a deterministic
+        function of the noise.  ``states``: int32 (n), given states (host arrays are uploaded; a state outside
+        [0, K) is a ValueError).  ``init``: fp32 (n, D) whose rows are a trial's first ``lags`` rows; without it those
+        rows are N(0, I), the model's own density for them."""
+        import torch
+        from behavenet_amd import _hip
+        device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        offsets = np.ascontiguousarray(np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets),
+                                       dtype=np.int64)
+        if offsets.ndim != 1 or offsets.size < 1:
+            raise ValueError('ARHMM.sample_table: expected offsets (S + 1,), got %s' % (offsets.shape,))
+        _hip.check_arhmm_dims('ARHMM.sample_table', self.D, self.lags, self.K)
+        n = max(int(offsets.max()), 0)
+        W, C, cdf0, cdf = self.generative()
+        gen = torch.Generator(device=device)
+        gen.manual_seed(int(seed))
+        eps = torch.randn((n, self.D), dtype=torch.float64, device=device, generator=gen)
+        u = None
+        if states is None:
+            u = torch.rand((n,), dtype=torch.float64, device=device, generator=gen)
+        elif not torch.is_tensor(states):
+            states = torch.from_numpy(np.ascontiguousarray(np.asarray(states), dtype=np.int32)).to(device)
+        if init is not None and not torch.is_tensor(init):
+            init = torch.from_numpy(np.ascontiguousarray(np.asarray(init), dtype=np.float32)).to(device)
+        return _hip.arhmm_sample(W, C, cdf0, cdf, offsets, eps, u=u, states=states, init=init)
+
+    def sample(self, T, n_samples=1, burn_in=200, seed=0):
+        """``n_samples`` trials of ``T`` rows generated by the model, states and latents both drawn:
+        ``(states_list, latents_list)`` of host arrays (T,) int32 and (T, D) float64.  Every trial runs for
+        ``T + burn_in`` rows and the first ``burn_in`` are dropped -- the reference's ``hmm.sample(T + 200)[200:]``
+        loop (plotting/arhmm_utils.py) -- in one launch.  Reproducible for a seed, device and torch build
+        (``sample_table``)."""
+        from behavenet_amd import _hip
+        T, n_samples, burn_in = int(T), int(n_samples), int(burn_in)
+        if T < 0 or n_samples < 0 or burn_in < 0:
+            raise ValueError('ARHMM.sample: T %d, n_samples %d, burn_in %d' % (T, n_samples, burn_in))
+        _hip.check_arhmm_dims('ARHMM.sample', self.D, self.lags, self.K)
+        per = T + burn_in
+        if not n_samples or not per:
+            return ([np.zeros((T,), dtype=np.int32) for _ in range(n_samples)],
+                    [np.zeros((T, self.D)) for _ in range(n_samples)])
+        offsets = np.arange(n_samples + 1, dtype=np.int64) * per
+        x, z = self.sample_table(offsets, seed=seed)
+        x, z = x.cpu().numpy(), z.cpu().numpy()
+        return ([z[i * per + burn_in:(i + 1) * per].copy() for i in range(n_samples)],
+                [x[i * per + burn_in:(i + 1) * per].copy() for i in range(n_samples)])
+
+    def sample_conditional(self, datas, seed=0):
+        """Latents drawn from the model along the most likely state path of every trial of ``datas`` (the reference's
+        ``cond_sampling=True``): ``(states_list, latents_list)`` of host arrays.  One ``table_states`` call gives the
+        Viterbi paths, one launch the samples; the first ``lags`` rows of a sampled trial are the real trial's."""
+        table, offsets = self.as_table(datas)
+        self._check_table(table)
+        states = self.table_states(table, offsets)
+        x, z = self.sample_table(offsets, seed=seed, states=states, init=table, device=table.device)
+        x, z = x.cpu().numpy(), z.cpu().numpy()
+        S = len(offsets) - 1
+        return ([z[offsets[i]:offsets[i + 1]].copy() for i in range(S)],
+                [x[offsets[i]:offsets[i + 1]].copy() for i in range(S)])

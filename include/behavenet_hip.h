@@ -825,6 +825,37 @@ size_t bn_hmm_viterbi_ws_bytes(int n, int S, int K);
 int bn_hmm_viterbi(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
                    const double* logpi0, int* states, void* ws, size_t ws_bytes, bn_stream_t stream);
 
+/* The generative process of the same model, from noise the CALLER brings: no random number is drawn on the device, so
+ * the call is a deterministic function of its operands (the same bits on every call).  Trials as above: offsets
+ * int64 (S + 1) made safe, rows outside [e[0], e[S]) neither read nor written.  float64 but for init and the states.
+ *
+ * W: (K, D, 1 + L D), [b_k | A_k] in the model's own coordinates (no shift); C: (K, D, D), a factor of Sigma_k
+ * (its lower Cholesky factor; all D columns are multiplied); cdf0: (K) and cdf: (K, K), the cumulative sums in state
+ * order of exp(logpi0) and of every row of exp(logP), formed by the caller; eps: (n, D) standard-normal draws.
+ * Exactly one of u: (n) uniform draws in [0, 1), and states_in: int32 (n).  init: NULL or fp32 (n, D) with row stride
+ * ld_init >= D.  -> x (n, D) and states int32 (n).
+ *
+ * States from u: row 0 of a trial takes cdf0, row t > 0 row z_{t-1} of cdf, and z_t is the number of j in [0, K - 1)
+ * with u_t >= cdf[j] -- the last column is never compared, so a row that sums below 1 cannot fall off the end, and
+ * only comparisons happen on the device: the path is the caller's own, bit for bit.  With states_in, states is its
+ * copy.  Rows: for t >= L  x_t = b_z + C_z eps_t + sum_l A_z[l] x_{t-1-l}  with the float64 x the call itself produced
+ * (the drive b_z + C_z eps_t first, one FMA a column in ascending order; then per output row the L D products in NP
+ * interleaved partial sums, NP = 8, 4, 2 for D up to 8, 16, 32, added as a fixed tree); for t < L  x_t = init[t]
+ * widened, or eps_t without init (the model's N(0, I) initial rows).  L = 0 has no initial rows.
+ * A NaN in init or eps stays inside its trial.  A state outside [0, K) in states_in makes its row and the rest of its
+ * trial NaN in x (states still is the copy); nothing is read outside W and C for it.  One wave a trial for the states
+ * and for the recursion, which is one serial chain: the call's time is (longest trial) x (step latency).
+ * ws: bn_arhmm_sample_ws_bytes bytes (the offsets, one int a trial and one a row, C transposed), on a 16-byte
+ * boundary.  S == 0 returns 0 and writes nothing.  BN_E_SHAPE (nothing written): K, L, D, n or S outside the limits
+ * (the query returns 0 for these), init with ld_init < D, a workspace smaller than the query's, a float64 operand or
+ * offsets off an 8-byte, init, states_in or states off a 4-byte, ws off a 16-byte boundary.  BN_E_BADARG: an operand
+ * NULL (init may be), or both or neither of u and states_in. */
+size_t bn_arhmm_sample_ws_bytes(int n, int S, int D, int L, int K);
+int bn_arhmm_sample(const double* W, const double* C, const double* cdf0, const double* cdf, const long long* offsets,
+                    int S, int D, int L, int K, int n, const double* eps, const double* u, const int* states_in,
+                    const float* init, int ld_init, double* x, int* states, void* ws, size_t ws_bytes,
+                    bn_stream_t stream);
+
 /* unit-float frames -> stored uint8 grey levels, the inverse of bn_u8_to_unit_float on k / 255:
  *   out[i] = NaN -> 0, else clamp(rint(in[i] * 255), 0, 255)
  * The product is one fp32 multiplication and rint rounds half to even, i.e. numpy's
