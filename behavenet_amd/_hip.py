@@ -147,6 +147,7 @@ SIGNATURES = {
     'bn_frame_mosaic_u8': (_c_int, [_c_void_p] + [_c_int] * 10 + [_c_void_p] + [_c_int] * 3 + [_c_void_p, _c_void_p]),
     'bn_frame_mosaic_ch_u8': (_c_int, [_c_void_p] + [_c_int] * 11 + [_c_void_p] + [_c_int] * 3
                               + [_c_void_p, _c_void_p]),
+    'bn_stamp_boxes_u8': (_c_int, [_c_void_p] + [_c_int] * 5 + [_c_void_p] + [_c_int] * 5 + [_c_void_p]),
     'bn_recon_panels_u8': (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p] + [_c_int] * 6
                            + [_c_void_p, _c_size_t, _c_void_p]),
     'bn_column_select_ws_bytes': (_c_size_t, [_c_int] * 3),
@@ -179,6 +180,9 @@ SIGNATURES = {
     'bn_arhmm_sample_ws_bytes': (_c_size_t, [_c_int] * 5),
     'bn_arhmm_sample': (_c_int, [_c_void_p] * 5 + [_c_int] * 5 + [_c_void_p] * 4 + [_c_int] + [_c_void_p] * 3
                         + [_c_size_t, _c_void_p]),
+    'bn_state_runs_ws_bytes': (_c_size_t, [_c_int] * 3),
+    'bn_state_runs': (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 3 + [_c_void_p, ctypes.c_longlong] + [_c_void_p] * 5
+                      + [_c_size_t, _c_void_p]),
     'bn_prof_select': (_c_int, [_c_int] * 3),
     'bn_prof_select_nth': (_c_int, [_c_int] * 4),
     'bn_prof_read': (_c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
@@ -1206,6 +1210,43 @@ def frame_mosaic_u8(frames, src, ch=0, crop=None):
     return out
 
 
+def stamp_boxes_u8(movie, mark, panel_hw, box=(5, 5, 10, 10), value=255):
+    """Marker boxes into the uint8 DEVICE ``movie`` (T, R * Hp, Cc * Wp), IN PLACE: for every panel (t, r, c) of
+    ``panel_hw = (Hp, Wp)`` pixels with ``mark[t, r, c] != 0`` the pixels ``box = (y0, x0, h, w)`` of the panel, rows
+    ``y0 .. y0 + h - 1`` and columns ``x0 .. x0 + w - 1`` clipped to the panel, are set to ``value``
+    (``bn_stamp_boxes_u8``, csrc/frame_mosaic.hip); nothing else is written.  ``mark``: (T, R, Cc), a host array
+    (uploaded) or a uint8 device tensor.  ``ValueError`` for a movie that is not uint8, 3-d and contiguous on the
+    GPU and for a ``mark`` whose shape does not divide the movie into panels of ``panel_hw``.  -> ``movie``."""
+    who = 'stamp_boxes_u8'
+    if not torch.is_tensor(movie) or movie.dim() != 3 or movie.dtype != torch.uint8 or not movie.is_contiguous():
+        raise ValueError('%s: expected a contiguous uint8 movie (T, R * Hp, Cc * Wp), got %s'
+                         % (who, (movie.dtype, tuple(movie.shape), tuple(movie.stride())) if torch.is_tensor(movie)
+                            else type(movie).__name__))
+    if not movie.is_cuda:
+        raise ValueError('%s: expected the movie on the GPU, got device %s (the HIP path has no CPU fallback)'
+                         % (who, movie.device))
+    if not torch.is_tensor(mark):
+        mark = torch.from_numpy(np.ascontiguousarray(np.asarray(mark) != 0).astype(np.uint8)).to(movie.device)
+    if mark.dtype != torch.uint8 or mark.device != movie.device:
+        raise ValueError('%s: a device mark must be uint8 on %s, got %s on %s'
+                         % (who, movie.device, mark.dtype, mark.device))
+    Hp, Wp = (int(v) for v in panel_hw)
+    y0, x0, h, w = (int(v) for v in box)
+    value = int(value)
+    if Hp < 1 or Wp < 1 or h < 0 or w < 0 or not 0 <= value <= 255:
+        raise ValueError('%s: panels of %d x %d, a box of %d x %d, value %d' % (who, Hp, Wp, h, w, value))
+    T = int(movie.shape[0])
+    if mark.dim() != 3 or (int(mark.shape[0]), int(mark.shape[1]) * Hp, int(mark.shape[2]) * Wp) != tuple(movie.shape):
+        raise ValueError('%s: mark %s does not divide the movie %s into panels of %d x %d'
+                         % (who, tuple(mark.shape), tuple(movie.shape), Hp, Wp))
+    mark = mark.contiguous()
+    R, Cc = int(mark.shape[1]), int(mark.shape[2])
+    if T * R * Cc:
+        _check(load().bn_stamp_boxes_u8(movie.data_ptr(), T, R, Cc, Hp, Wp, mark.data_ptr(), y0, x0, h, w, value,
+                                        _stream()), 'bn_stamp_boxes_u8')
+    return movie
+
+
 # csrc/column_select.hip's partition, restated for the tests that have to name a row count by it (held against
 # bn_column_select_ws_bytes in tests/test_ranges_cpu.py): CS_HISTS, CS_MIN_ELEMS, CS_TARGET_GROUPS
 COLUMN_SELECT_HISTS, COLUMN_SELECT_MIN_ELEMS, COLUMN_SELECT_TARGET_GROUPS = 60, 1 << 16, 512
@@ -1690,6 +1731,56 @@ def hmm_viterbi(ll, offsets, log_Ps, log_pi0):
                                   states.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes, _stream()),
                'bn_hmm_viterbi')
     return states
+
+
+# csrc/state_runs.hip's partition, restated for the tests that have to name tile boundaries and the row count at which
+# the scan over the tiles' counts takes a second step: SR_TILE rows a workgroup (held against bn_state_runs_ws_bytes
+# in tests/test_state_runs_cpu.py), SR_SCAN counts a step of the scan
+STATE_RUNS_TILE, STATE_RUNS_SCAN = 1024, 1024
+
+
+def state_runs(states, offsets, K):
+    """The runs of the int32 DEVICE state table ``states`` (n,) -- ``hmm_viterbi``'s output -- inside the trials
+    ``offsets`` (int64 (S + 1), a host array is uploaded): ``(runs, frames, trans)``, device tensors
+    (``bn_state_runs``, csrc/state_runs.hip).  ``runs`` int32 (R, 4): one row ``(trial, beg, end, state)`` per maximal
+    stretch of equal states inside one trial, ``beg`` and ``end`` relative to the trial and ``end`` exclusive, in the
+    order of the table.  ``frames`` int64 (K): the rows in trials per state.  ``trans`` int64 (K, K): the pairs
+    ``(states[i - 1], states[i])`` inside one trial, self-pairs included.  Rows outside the trials are not read.  A
+    state outside [0, K) on a row in a trial is a ValueError that names how many there are.  One synchronisation
+    (two int64 come back: R and that count).  ``S == 0`` gives empty runs and zeros."""
+    who = 'state_runs'
+    if not torch.is_tensor(states) or states.dim() != 1 or states.dtype != torch.int32:
+        raise ValueError('%s: expected states int32 (n,), got %s'
+                         % (who, (states.dtype, tuple(states.shape)) if torch.is_tensor(states)
+                            else type(states).__name__))
+    if not states.is_cuda:
+        raise ValueError('%s: expected states on the GPU, got device %s (the HIP path has no CPU fallback)'
+                         % (who, states.device))
+    if not states.is_contiguous():
+        raise ValueError('%s: states must be contiguous, got strides %s' % (who, tuple(states.stride())))
+    K = int(K)
+    if not 1 <= K <= ARHMM_MAX_K:
+        raise ValueError('%s: %d states (1 to %d are served)' % (who, K, ARHMM_MAX_K))
+    dev = states.device
+    n = int(states.shape[0])
+    offsets = _trial_offsets(who, offsets, dev)
+    S = int(offsets.numel()) - 1
+    # frames (K), trans (K, K), n_runs and bad in one tensor: one transfer tells R and bad
+    stats = torch.zeros((K + K * K + 2,), dtype=torch.int64, device=dev)
+    frames, trans = stats[:K], stats[K:K + K * K].view(K, K)
+    if not S or not n:
+        return torch.empty((0, 4), dtype=torch.int32, device=dev), frames, trans
+    runs = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    lib = load()
+    nbytes = lib.bn_state_runs_ws_bytes(n, S, K)
+    at = stats.data_ptr()
+    _check(lib.bn_state_runs(states.data_ptr(), offsets.data_ptr(), S, K, n, runs.data_ptr(), n, at, at + 8 * K,
+                             at + 8 * (K + K * K), at + 8 * (K + K * K + 1), _arena(dev, nbytes, 'state_runs'), nbytes,
+                             _stream()), 'bn_state_runs')
+    R, bad = (int(v) for v in stats[K + K * K:].cpu())
+    if bad:
+        raise ValueError('%s: %d rows in trials hold a state outside [0, %d)' % (who, bad, K))
+    return (runs if R == n else runs[:R].clone()), frames, trans
 
 
 def arhmm_sample(W, C, cdf0, cdf, offsets, eps, u=None, states=None, init=None, x=None, states_out=None):

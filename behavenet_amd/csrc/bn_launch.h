@@ -95,6 +95,11 @@ bool bn_frame_mosaic_ok(int P, int C, int H, int W, int ch0, int n_ch, int y_min
 int bn_launch_frame_mosaic(const void* frames, int frames_u8, int P, int C, int H, int W, int ch0, int n_ch, int y_min,
                            int x_min, int Hc, int Wc, const int* src, int T, int R, int Cc, unsigned char* out,
                            hipStream_t st);
+// ... and marker boxes into a finished mosaic, in place: the box [y0, y0 + h) x [x0, x0 + w) of every panel whose
+// mark is non-zero, clipped to the panel, set to `value`
+bool bn_stamp_boxes_ok(int T, int R, int Cc, int Hp, int Wp, int y0, int x0, int h, int w, int value);
+int bn_launch_stamp_boxes(unsigned char* movie, int T, int R, int Cc, int Hp, int Wp, const unsigned char* mark, int y0,
+                          int x0, int h, int w, int value, hipStream_t st);
 
 // recon_panels.hip: frames, their reconstruction and the residual 0.5 + (orig * mask - recon) as three uint8 panels
 // per row, channels side by side, into frames of out_frame_stride >= 3 C H W bytes (one row of a movie)
@@ -161,6 +166,14 @@ int bn_launch_arhmm_sample(const double* W, const double* C, const double* cdf0,
                            const long long* offsets, int S, int D, int L, int K, int n, const double* eps,
                            const double* u, const int* states_in, const float* init, int ld_init, double* x,
                            int* states, void* ws, hipStream_t st);
+
+// state_runs.hip: the runs (trial, beg, end, state) of an int32 state table cut into trials, in table order, with
+// the frames per state and the in-trial transition counts
+bool bn_state_runs_ok(int n, int S, int K);
+size_t bn_state_runs_ws_bytes_impl(int n, int S, int K);
+int bn_launch_state_runs(const int* states, const long long* offsets, int S, int K, int n, int* runs,
+                         long long runs_cap, long long* frames, long long* trans, long long* n_runs, long long* bad,
+                         void* ws, hipStream_t st);
 
 // batchnorm.hip
 size_t bn_batchnorm_ws_bytes_impl(int N, int C);

@@ -1977,6 +1977,16 @@ extern "C" int bn_frame_mosaic_u8(const void* frames, int frames_u8, int p, int 
                                  stream);
 }
 
+// Marker boxes into a finished mosaic, in place (frame_mosaic.hip): the syllable movie's mark on the first frames of
+// an instance.
+extern "C" int bn_stamp_boxes_u8(unsigned char* movie, int t, int r, int cc, int hp, int wp, const unsigned char* mark,
+                                 int y0, int x0, int h, int w, int value, bn_stream_t stream) {
+    if (!bn_stamp_boxes_ok(t, r, cc, hp, wp, y0, x0, h, w, value)) return BN_E_SHAPE;
+    if ((size_t)t * (size_t)r * (size_t)cc == 0) return 0;
+    if (!movie || !mark) return BN_E_BADARG;
+    return bn_launch_stamp_boxes(movie, t, r, cc, hp, wp, mark, y0, x0, h, w, value, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // Frames and their reconstruction -> original | reconstruction | residual strips (recon_panels.hip): the
 // reconstruction movie.
@@ -2173,6 +2183,26 @@ extern "C" int bn_arhmm_sample(const double* W, const double* C, const double* c
     if (ws_bytes < bn_arhmm_sample_ws_bytes_impl(n, S, D, L, K)) return BN_E_SHAPE;
     return bn_launch_arhmm_sample(W, C, cdf0, cdf, offsets, S, D, L, K, n, eps, u, states_in, init, ld_init, x, states,
                                   ws, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The runs of a state table, per trial and in table order, with the frames per state and the transition counts
+// (state_runs.hip): what the syllable movies and the state-duration statistics are made from.
+extern "C" size_t bn_state_runs_ws_bytes(int n, int S, int K) { return bn_state_runs_ws_bytes_impl(n, S, K); }
+
+extern "C" int bn_state_runs(const int* states, const long long* offsets, int S, int K, int n, int* runs,
+                             long long runs_cap, long long* frames, long long* trans, long long* n_runs,
+                             long long* bad, void* ws, size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_state_runs_ok(n, S, K) || runs_cap < 0) return BN_E_SHAPE;
+    if (!offsets || !frames || !trans || !n_runs || !bad || !ws || (n > 0 && !states) || (runs_cap > 0 && !runs))
+        return BN_E_BADARG;
+    // (a run is one 16-byte store where it is one row long)
+    if (((uintptr_t)states & 3) || ((uintptr_t)offsets & 7) || ((uintptr_t)runs & 15) || ((uintptr_t)frames & 7) ||
+        ((uintptr_t)trans & 7) || ((uintptr_t)n_runs & 7) || ((uintptr_t)bad & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_state_runs_ws_bytes_impl(n, S, K)) return BN_E_SHAPE;
+    return bn_launch_state_runs(states, offsets, S, K, n, runs, runs_cap, frames, trans, n_runs, bad, ws,
+                                (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -173,3 +173,52 @@ int bn_launch_frame_mosaic(const void* frames, int frames_u8, int P, int C, int 
     BN_LAUNCH_CHECK();
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// Marker boxes into a finished mosaic, in place (the syllable movie's "first frames of an instance" mark, the
+// reference's Rectangle((5, 5), 10, 10) in grey): for every panel (t, r, c) with mark[t, r, c] != 0 the pixels
+// [y0, y0 + h) x [x0, x0 + w) of the panel, clipped to it, are set to `value`; nothing else is written.  One wave per
+// panel: a wave reads its panel's mark and leaves at once where it is 0 (most panels of a movie), else its lanes walk
+// the box's pixels with byte stores.  The box is a few hundred bytes a marked panel: the launch is latency, not
+// bandwidth.
+#define MO_BOX_THREADS 64
+
+__global__ __launch_bounds__(MO_BOX_THREADS) void k_stamp_boxes(unsigned char* __restrict__ movie, int Cc, int Hp, int Wp,
+                                                                const unsigned char* __restrict__ mark, int ya,
+                                                                int xa, int hb, int wb, unsigned char value) {
+    const unsigned panel = blockIdx.x;                      // (t R + r) Cc + c
+    if (!mark[panel]) return;
+    const unsigned tr = panel / (unsigned)Cc, c = panel - tr * (unsigned)Cc;
+    // (tr Hp counts the mosaic's rows above the panel: t R Hp + r Hp)
+    unsigned char* o = movie + ((size_t)tr * (size_t)Hp + (size_t)ya) * ((size_t)Cc * (size_t)Wp) + (size_t)c * (size_t)Wp
+                       + (size_t)xa;
+    const int px = hb * wb;
+    for (int i = threadIdx.x; i < px; i += MO_BOX_THREADS) {
+        const int y = i / wb, x = i - y * wb;
+        o[(size_t)y * ((size_t)Cc * (size_t)Wp) + (size_t)x] = value;
+    }
+}
+
+bool bn_stamp_boxes_ok(int T, int R, int Cc, int Hp, int Wp, int y0, int x0, int h, int w, int value) {
+    if (T < 0 || R < 0 || Cc < 0 || Hp <= 0 || Wp <= 0 || h < 0 || w < 0 || value < 0 || value > 255) return false;
+    const size_t lim = (size_t)1 << 31;
+    const size_t panels = (size_t)T * (size_t)R * (size_t)Cc;
+    if ((size_t)T * (size_t)R >= lim || panels >= lim) return false;          // (one workgroup a panel, counted in 32 bits)
+    // (... and a box's pixels in an int)
+    return (size_t)R * (size_t)Hp < lim && (size_t)Cc * (size_t)Wp < lim && (size_t)Hp * (size_t)Wp < lim;
+}
+
+int bn_launch_stamp_boxes(unsigned char* movie, int T, int R, int Cc, int Hp, int Wp, const unsigned char* mark, int y0,
+                          int x0, int h, int w, int value, hipStream_t st) {
+    if (!bn_stamp_boxes_ok(T, R, Cc, Hp, Wp, y0, x0, h, w, value)) return BN_E_SHAPE;
+    const size_t panels = (size_t)T * (size_t)R * (size_t)Cc;
+    // the box clipped to the panel
+    const long long ya = y0 > 0 ? y0 : 0, xa = x0 > 0 ? x0 : 0;
+    const long long yb = (long long)y0 + h < Hp ? (long long)y0 + h : Hp;
+    const long long xb = (long long)x0 + w < Wp ? (long long)x0 + w : Wp;
+    if (panels == 0 || yb <= ya || xb <= xa) return 0;
+    hipLaunchKernelGGL(k_stamp_boxes, dim3((unsigned)panels), dim3(MO_BOX_THREADS), 0, st, movie, Cc, Hp, Wp, mark,
+                       (int)ya, (int)xa, (int)(yb - ya), (int)(xb - xa), (unsigned char)value);
+    BN_LAUNCH_CHECK();
+    return 0;
+}

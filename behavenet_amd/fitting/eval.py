@@ -2372,3 +2372,188 @@ def real_vs_sampled_movie(model, latents, latents_gen, max_frames=400, n_buffer=
     """``real_vs_sampled_movie_device`` as a numpy array ``(T, C * H, 2 * W)`` of uint8."""
     return real_vs_sampled_movie_device(model, latents, latents_gen, max_frames, n_buffer, labels_0,
                                         apply_inverse_transform, chunk_size).cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------ state runs, syllable movies
+def _runs_array(runs, K, lengths):
+    runs = runs.detach().cpu().numpy() if torch.is_tensor(runs) else np.asarray(runs)
+    runs = runs.reshape(-1, 4).astype(np.int64)
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if len(runs) and (runs[:, 0].min() < 0 or runs[:, 0].max() >= len(lengths)):
+        raise ValueError('discrete_chunks: the runs name trial %d of %d' % (int(runs[:, 0].max()), len(lengths)))
+    if len(runs) and (runs[:, 3].min() < 0 or runs[:, 3].max() >= int(K)):
+        raise ValueError('discrete_chunks: the runs name state %d of %d' % (int(runs[:, 3].max()), int(K)))
+    return runs, lengths
+
+
+def discrete_chunks(runs, K, lengths, include_edges=True):
+    """The structure of the reference's ``get_discrete_chunks`` (plotting/arhmm_utils.py:24-68) from the rows
+    ``(trial, beg, end, state)`` of ``_hip.state_runs`` / ``ARHMM.table_runs``: a list of ``K`` int64 arrays
+    ``(m, 3)`` of ``[chunk, beg, end]``, the occurrences of each state in order of appearance, ``(0, 3)`` for a state
+    that never occurs.  ``lengths``: the frames of every trial.  ``include_edges=False`` drops the runs that touch
+    either end of their trial (``beg == 0`` or ``end == lengths[chunk]``), which is what the reference's test on its
+    padded indices amounts to.  Departure: the list has the model's ``K`` entries, not ``max(state) + 1``."""
+    runs, lengths = _runs_array(runs, K, lengths)
+    if not include_edges and len(runs):
+        runs = runs[(runs[:, 1] != 0) & (runs[:, 2] != lengths[runs[:, 0]])]
+    return [runs[runs[:, 3] == k][:, :3].copy() for k in range(int(K))]
+
+
+def state_durations(runs, K, lengths, include_edges=True):
+    """Per state the frame counts ``end - beg`` of its runs (the reference's ``get_state_durations``,
+    plotting/arhmm_utils.py:71-99): a list of ``K`` int64 arrays, and ``[]`` for a single-state model."""
+    if int(K) == 1:
+        return []
+    return [c[:, 2] - c[:, 1] for c in discrete_chunks(runs, K, lengths, include_edges)]
+
+
+def syllable_instances(chunks, min_threshold=0, seed=0):
+    """Per state the instances of ``chunks`` (``discrete_chunks``) with ``end - beg > min_threshold``, shuffled
+    (``make_syllable_movies_wrapper``, plotting/arhmm_utils.py:338-345).  Departure: the reference shuffles with
+    numpy's global generator; here ONE ``np.random.RandomState(seed)`` shuffles the states in order, so the
+    selection is reproducible."""
+    rng = np.random.RandomState(seed)
+    out = []
+    for c in chunks:
+        c = np.asarray(c, dtype=np.int64).reshape(-1, 3)
+        keep = c[(c[:, 2] - c[:, 1]) > min_threshold].copy()
+        if len(c):
+            rng.shuffle(keep)
+        out.append(keep)
+    return out
+
+
+def syllable_movie_plan(state_list, max_frames=400, n_buffer=5, n_pre_frames=3, n_rows=None, single_syllable=None):
+    """The panels of the reference's syllable movie (``make_syllable_movies``, plotting/arhmm_utils.py:391-492), host
+    only: ``(src, mark, n_rows, n_cols)``.  ``src`` int64 ``(T, n_rows, n_cols, 2)`` names per movie frame and panel
+    the ``(chunk, row)`` shown, -1 for a blank panel; ``mark`` uint8 ``(T, n_rows, n_cols)`` is 1 where the reference
+    draws its red box.  Panel ``i`` shows state ``i`` at ``(i // n_cols, i % n_cols)``, ``n_rows`` defaults to
+    ``floor(sqrt(K))`` and ``n_cols = ceil(K / n_rows)``; with ``single_syllable`` there is one panel, for that state.
+
+    Per panel, while fewer than ``max_frames`` frames are planned: the next instance ``[chunk, beg, end]`` of the
+    state gives the rows ``max(beg - n_pre_frames, 0) .. end - 1`` -- the clip frames ``i`` with ``min(n_pre_frames,
+    beg) <= i < min(n_pre_frames, beg) + 2`` are marked -- and ``n_buffer`` blanks; without instances left, one
+    blank.  A clip is never cut, so a panel may pass ``max_frames``; ``T`` is the longest panel, shorter ones and
+    states without instances are blank.  ValueError where no state has an instance, and where ``single_syllable``
+    names a state without any."""
+    who = 'syllable_movie_plan'
+    max_frames, n_buffer, n_pre_frames = int(max_frames), int(n_buffer), int(n_pre_frames)
+    if max_frames < 1 or n_buffer < 0 or n_pre_frames < 0:
+        raise ValueError('%s: max_frames %d, n_buffer %d, n_pre_frames %d' % (who, max_frames, n_buffer, n_pre_frames))
+    lists = [np.asarray(c, dtype=np.int64).reshape(-1, 3) for c in state_list]
+    if single_syllable is not None:
+        k = int(single_syllable)
+        if not 0 <= k < len(lists) or not len(lists[k]):
+            raise ValueError('%s: state %d has no instances' % (who, k))
+        shown, n_rows = [k], 1
+    else:
+        shown = list(range(len(lists)))
+    if not any(len(lists[k]) for k in shown):
+        raise ValueError('%s: no state has an instance' % who)
+    n_rows = int(np.floor(np.sqrt(len(shown)))) if n_rows is None else int(n_rows)
+    if n_rows < 1:
+        raise ValueError('%s: n_rows is %d' % (who, n_rows))
+    n_cols = int(np.ceil(len(shown) / n_rows))
+    panels = []
+    for k in shown:
+        rows = []                                         # (chunk, row, mark) per frame of the panel
+        used = 0
+        while len(lists[k]) and len(rows) < max_frames:
+            if used >= len(lists[k]):
+                rows.append((-1, -1, 0))
+                continue
+            chunk, beg, end = (int(v) for v in lists[k][used])
+            first = max(beg - n_pre_frames, 0)
+            start = min(n_pre_frames, beg)
+            rows.extend((chunk, r, 1 if start <= r - first < start + 2 else 0) for r in range(first, end))
+            rows.extend([(-1, -1, 0)] * n_buffer)
+            used += 1
+        panels.append(rows)
+    n_t = max(len(rows) for rows in panels)
+    src = np.full((n_t, n_rows, n_cols, 2), -1, dtype=np.int64)
+    mark = np.zeros((n_t, n_rows, n_cols), dtype=np.uint8)
+    for i, rows in enumerate(panels):
+        if rows:
+            a = np.asarray(rows, dtype=np.int64)
+            src[:len(a), i // n_cols, i % n_cols] = a[:, :2]
+            mark[:len(a), i // n_cols, i % n_cols] = a[:, 2]
+    return src, mark, n_rows, n_cols
+
+
+SYLLABLE_BOX = (5, 5, 10, 10)            # the reference's Rectangle((5, 5), 10, 10): rows and columns 5 .. 14
+SYLLABLE_BOX_VALUE = 255
+
+
+def syllable_movie_device(trial_frames, state_list, max_frames=400, n_buffer=5, n_pre_frames=3, n_rows=None,
+                          single_syllable=None, chunk_size=200, device=None):
+    """The frames of the reference's syllable movie (``make_syllable_movies``, plotting/arhmm_utils.py:360-511):
+    ``(movie, mark)``, the uint8 DEVICE movie ``(T, n_rows * C * H, n_cols * W)`` and the host plan's ``mark``
+    ``(T, n_rows, n_cols)`` (``syllable_movie_plan``).  Panel ``i`` plays the instances ``state_list[i]`` of state
+    ``i`` (``syllable_instances``) one after the other, ``n_pre_frames`` frames of lead-in before and ``n_buffer``
+    blank frames after each; the channels of a frame are stacked vertically, as the reference's
+    ``np.concatenate(..., axis=1)`` stacks them.
+
+    ``trial_frames[chunk]`` -- or ``trial_frames(chunk)`` for a callable -- is the ``(T_chunk, C, H, W)`` uint8 or
+    fp32 array or tensor of the trial ``chunk`` counts; only the chunks the plan names are asked for.  The rows the
+    clips show, and only those, are stacked into one device table, viewed as planes ``(P * C, 1, H, W)`` and tiled by
+    one mosaic launch per ``chunk_size`` movie frames.  ONE ``stamp_boxes_u8`` launch then sets rows and columns
+    5 .. 14 of every marked panel to 255 -- the reference's red ``Rectangle((5, 5), 10, 10)`` in grey; ``mark`` is
+    returned so a caller can draw it in colour instead."""
+    who = 'syllable_movie'
+    chunk_size = int(chunk_size)
+    if chunk_size < 1:
+        raise ValueError('%s: chunk_size %d' % (who, chunk_size))
+    src, mark, n_rows, n_cols = syllable_movie_plan(state_list, max_frames, n_buffer, n_pre_frames, n_rows,
+                                                    single_syllable)
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    n_t = src.shape[0]
+    shown = src[..., 0] >= 0
+    pairs = np.unique(src[shown], axis=0)                            # (chunk, row), sorted by chunk, then row
+    index = np.full(src.shape[:3], -1, dtype=np.int64)
+    # (np.unique's order is the lexicographic one searchsorted needs on chunk * big + row)
+    big = int(pairs[:, 1].max()) + 1
+    index[shown] = np.searchsorted(pairs[:, 0] * big + pairs[:, 1], src[shown][:, 0] * big + src[shown][:, 1])
+    parts, dims, dtype = [], None, None
+    for chunk in np.unique(pairs[:, 0]):
+        frames = trial_frames(int(chunk)) if callable(trial_frames) else trial_frames[int(chunk)]
+        rows = pairs[pairs[:, 0] == chunk, 1]
+        if not torch.is_tensor(frames):
+            frames = np.asarray(frames)
+        if frames.ndim != 4:
+            raise ValueError('%s: the frames of trial %d must be (T, C, H, W), got %s'
+                             % (who, chunk, tuple(frames.shape)))
+        if int(rows.max()) >= frames.shape[0]:
+            raise ValueError('%s: an instance of trial %d ends at frame %d, the trial has %d'
+                             % (who, chunk, int(rows.max()) + 1, frames.shape[0]))
+        if torch.is_tensor(frames):
+            picked = frames.index_select(0, torch.from_numpy(rows).to(frames.device)).to(device)
+        else:
+            picked = torch.from_numpy(np.ascontiguousarray(frames[rows])).to(device)
+        if picked.dtype not in (torch.uint8, torch.float32):
+            raise ValueError('%s: frames must be uint8 or float32, got %s' % (who, picked.dtype))
+        if dims is None:
+            dims, dtype = tuple(picked.shape[1:]), picked.dtype
+        elif tuple(picked.shape[1:]) != dims or picked.dtype != dtype:
+            raise ValueError('%s: trial %d has frames %s %s, the first trial shown %s %s'
+                             % (who, chunk, picked.dtype, tuple(picked.shape[1:]), dtype, dims))
+        parts.append(picked)
+    table = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+    P, C, H, W = table.shape
+    planes = table.contiguous().view(P * C, 1, H, W)
+
+    def src_of(beg, end):
+        # mosaic row r * C + c of column q shows channel c of the frame of panel (r, q): plane s * C + c
+        s = index[beg:end][:, :, None, :]                                             # (t, n_rows, 1, n_cols)
+        out = np.where(s >= 0, s * C + np.arange(C)[None, None, :, None], -1)         # (t, n_rows, C, n_cols)
+        return out.reshape(end - beg, n_rows * C, n_cols).astype(np.int32)
+    movie = _mosaic_in_chunks(planes, src_of, n_t, 0, None, chunk_size)
+    _hip.stamp_boxes_u8(movie, mark, (C * H, W), SYLLABLE_BOX, SYLLABLE_BOX_VALUE)
+    return movie, mark
+
+
+def syllable_movie(trial_frames, state_list, max_frames=400, n_buffer=5, n_pre_frames=3, n_rows=None,
+                   single_syllable=None, chunk_size=200, device=None):
+    """``syllable_movie_device`` with the movie as a numpy array ``(T, n_rows * C * H, n_cols * W)`` of uint8."""
+    movie, mark = syllable_movie_device(trial_frames, state_list, max_frames, n_buffer, n_pre_frames, n_rows,
+                                        single_syllable, chunk_size, device)
+    return movie.cpu().numpy(), mark

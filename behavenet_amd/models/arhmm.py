@@ -315,6 +315,25 @@ class ARHMM(object):
         ll = self._loglik_table(table, offsets_d)
         return _hip.hmm_viterbi(ll, offsets_d, self.log_Ps, self.log_pi0).cpu().numpy()
 
+    def table_runs(self, table, offsets):
+        """The runs of the Viterbi paths of the table's trials: ``(runs, frames, trans)``, host arrays -- int32
+        (R, 4) rows ``(trial, beg, end, state)`` in table order, ``beg`` / ``end`` relative to the trial and ``end``
+        exclusive, int64 (K) frames per state and int64 (K, K) in-trial transition counts (``_hip.state_runs``).
+        Log-likelihoods, Viterbi and the run search follow each other on the device; the states never leave it and
+        the three results cross in ONE transfer."""
+        import torch
+        from behavenet_amd import _hip
+        self._check_table(table)
+        offsets_d = self._offsets_d(table, offsets)
+        K = self.K
+        ll = self._loglik_table(table, offsets_d)
+        states = _hip.hmm_viterbi(ll, offsets_d, self.log_Ps, self.log_pi0)
+        runs, frames, trans = _hip.state_runs(states, offsets_d, K)
+        packed = torch.cat([runs.reshape(-1).to(torch.int64), frames, trans.reshape(-1)]).cpu().numpy()
+        R = int(runs.shape[0])
+        return (packed[:4 * R].astype(np.int32).reshape(R, 4), packed[4 * R:4 * R + K].copy(),
+                packed[4 * R + K:].reshape(K, K).copy())
+
     def most_likely_states(self, x):
         table, offsets = self.as_table(x)
         return self.table_states(table, offsets)

@@ -611,6 +611,18 @@ int bn_frame_mosaic_ch_u8(const void* frames, int frames_u8, int p, int c, int h
                           int y_min, int x_min, int hc, int wc, const int* src, int t, int r, int cc,
                           unsigned char* out, bn_stream_t stream);
 
+/* Marker boxes into a finished mosaic, in place (the red Rectangle((5, 5), 10, 10) that make_syllable_movies,
+ * plotting/arhmm_utils.py:476-482, draws on the first frames of a syllable instance, in grey): movie uint8
+ * (t, r * hp, cc * wp), panels of hp rows and wp columns; mark uint8 (t, r, cc).  For every panel (i, j, k) with
+ * mark[(i * r + j) * cc + k] != 0
+ *   movie[i, j * hp + y, k * wp + x] = value      y0 <= y < y0 + h, x0 <= x < x0 + w, 0 <= y < hp, 0 <= x < wp
+ * -- the box is clipped to its panel -- and no other byte is written or read.  Plain byte stores, no atomics; one
+ * wave a panel, which leaves at once where the mark is 0.  t * r * cc == 0, h or w == 0 and a box wholly outside the
+ * panel return 0 and launch nothing.  BN_E_SHAPE (nothing written): a negative count, hp or wp <= 0, h or w < 0,
+ * value outside [0, 255], t * r * cc, r * hp, cc * wp or hp * wp at 2^31 or beyond.  BN_E_BADARG: a NULL pointer. */
+int bn_stamp_boxes_u8(unsigned char* movie, int t, int r, int cc, int hp, int wp, const unsigned char* mark,
+                      int y0, int x0, int h, int w, int value, bn_stream_t stream);
+
 /* The strips of a reconstruction movie in one pass (replaces the three fp32 arrays ims_orig, ims_recon and
  * 0.5 + (ims_orig - ims_recon) of make_ae_reconstruction_movie_wrapper, plotting/ae_utils.py:147-186, their
  * concat per frame and matplotlib's vmin=0, vmax=1 clip): for frame i and row y three panels of c * w bytes,
@@ -855,6 +867,34 @@ int bn_arhmm_sample(const double* W, const double* C, const double* cdf0, const 
                     int S, int D, int L, int K, int n, const double* eps, const double* u, const int* states_in,
                     const float* init, int ld_init, double* x, int* states, void* ws, size_t ws_bytes,
                     bn_stream_t stream);
+
+/* The runs of a table of discrete states (get_discrete_chunks / get_state_durations of plotting/arhmm_utils.py:24-99,
+ * which pad and difference every trial on the host): states int32 (n), the output of bn_hmm_viterbi; offsets int64
+ * (S + 1) made safe as above (clamped into [0, n], ascending), empty trials allowed; rows outside [e[0], e[S]) are
+ * never loaded.  1 <= K <= 32.  A run is a maximal stretch of equal states inside ONE trial: row i of trial s starts
+ * one iff i == e[s] or states[i] != states[i - 1], so two neighbouring trials that end and begin in the same state
+ * are two runs.
+ *   runs    int32 (runs_cap, 4): row p = (trial, beg, end, state) of the p-th run in the order of the table rows
+ *           the runs begin at, beg and end relative to e[trial], end exclusive; rows p >= runs_cap are not written
+ *           (n rows always suffice) and rows p >= n_runs are left as they are
+ *   frames  int64 (K): the rows in trials per state
+ *   trans   int64 (K, K): trans[j][k] = the rows i with states[i - 1] == j, states[i] == k and both in one trial
+ *           (self-pairs included)
+ *   n_runs  int64: the number of runs, whatever runs_cap is
+ *   bad     int64: the rows in trials whose state is outside [0, K); they count in neither frames nor trans, and the
+ *           caller is expected to refuse the result when bad != 0
+ * Positions come from a prefix sum over the start flags (tiles of 1024 rows, their counts scanned by one workgroup),
+ * never from the order atomics land in; frames, trans and bad are integer sums from LDS histograms.  So every
+ * output is exact and the same for every launch geometry.  n up to 2^31 - 1.
+ * ws: bn_state_runs_ws_bytes bytes (the offsets and two ints per tile of rows) on a 16-byte boundary.  S == 0 returns
+ * 0 and writes nothing; n == 0 with S > 0 writes zeros to frames, trans, n_runs and bad.  BN_E_SHAPE (nothing
+ * written): K, n or S outside the limits (the query returns 0 for these), runs_cap < 0, a workspace smaller than the
+ * query's, states off a 4-byte, an int64 operand off an 8-byte, runs or ws off a 16-byte boundary.  BN_E_BADARG: an
+ * operand NULL (states may be when n == 0, runs when runs_cap == 0). */
+size_t bn_state_runs_ws_bytes(int n, int S, int K);
+int bn_state_runs(const int* states, const long long* offsets, int S, int K, int n, int* runs, long long runs_cap,
+                  long long* frames, long long* trans, long long* n_runs, long long* bad, void* ws, size_t ws_bytes,
+                  bn_stream_t stream);
 
 /* unit-float frames -> stored uint8 grey levels, the inverse of bn_u8_to_unit_float on k / 255:
  *   out[i] = NaN -> 0, else clamp(rint(in[i] * 255), 0, 255)
