@@ -177,6 +177,15 @@ SIGNATURES = {
                          + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
     'bn_hmm_viterbi_ws_bytes': (_c_size_t, [_c_int] * 3),
     'bn_hmm_viterbi': (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 3 + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
+    'bn_arhmm_grid_loglik_ws_bytes': (_c_size_t, [_c_int] * 5),
+    'bn_arhmm_grid_loglik': (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p] + [_c_int] * 5
+                             + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
+    'bn_arhmm_grid_moments_ws_bytes': (_c_size_t, [_c_int] * 5),
+    'bn_arhmm_grid_moments': (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p] + [_c_int] * 5
+                              + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
+    'bn_hmm_grid_forward_backward_ws_bytes': (_c_size_t, [_c_int] * 5),
+    'bn_hmm_grid_forward_backward': (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 5 + [_c_void_p] * 3 + [_c_int] * 4
+                                     + [_c_void_p, _c_void_p, _c_int] + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
     'bn_arhmm_sample_ws_bytes': (_c_size_t, [_c_int] * 5),
     'bn_arhmm_sample': (_c_int, [_c_void_p] * 5 + [_c_int] * 5 + [_c_void_p] * 4 + [_c_int] + [_c_void_p] * 3
                         + [_c_size_t, _c_void_p]),
@@ -1731,6 +1740,171 @@ def hmm_viterbi(ll, offsets, log_Ps, log_pi0):
                                   states.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes, _stream()),
                'bn_hmm_viterbi')
     return states
+
+
+# A grid of models on one table (bn_arhmm_grid_*, bn_hmm_grid_forward_backward): AR_GRID_MAX_KT, AR_GRID_MAX_M.  The
+# row blocks of bn_arhmm_grid_moments are _arhmm_moments_plan's with K = KT (held against the workspace query in
+# tests/test_arhmm_grid_cpu.py)
+ARHMM_GRID_MAX_STATES, ARHMM_GRID_MAX_MODELS = 512, 512
+_HMM_GRID_CLASSES = (4, 8, 16, 32)
+
+
+def check_arhmm_grid_states(who, Ks):
+    """ValueError unless ``Ks`` are the state counts of a grid the kernels serve: 1 to 512 models of 1 to 32 states,
+    512 states together.  -> ``(koff, xoff)``, int32 (M + 1): the prefix sums of ``K_m`` and of ``K_m^2``."""
+    Ks = [int(k) for k in Ks]
+    if not 1 <= len(Ks) <= ARHMM_GRID_MAX_MODELS:
+        raise ValueError('%s: %d models (1 to %d are served)' % (who, len(Ks), ARHMM_GRID_MAX_MODELS))
+    for k in Ks:
+        if not 1 <= k <= ARHMM_MAX_K:
+            raise ValueError('%s: %d states (1 to %d are served)' % (who, k, ARHMM_MAX_K))
+    if sum(Ks) > ARHMM_GRID_MAX_STATES:
+        raise ValueError('%s: %d states in all models together (1 to %d are served)'
+                         % (who, sum(Ks), ARHMM_GRID_MAX_STATES))
+    return (np.concatenate(([0], np.cumsum(Ks))).astype(np.int32),
+            np.concatenate(([0], np.cumsum([k * k for k in Ks]))).astype(np.int32))
+
+
+def check_arhmm_grid_dims(who, D, L, KT):
+    """ValueError unless (D, L) are served and ``KT`` states together are at most 512."""
+    check_arhmm_dims(who, D, L, 1)
+    if not 1 <= KT <= ARHMM_GRID_MAX_STATES:
+        raise ValueError('%s: %d states in all models together (1 to %d are served)'
+                         % (who, KT, ARHMM_GRID_MAX_STATES))
+
+
+def hmm_grid_plan(Ks):
+    """Where ``bn_hmm_grid_forward_backward`` puts the models of state counts ``Ks``: ``(cls, wave, slot)``, int32
+    arrays (M,).  ``cls[m]`` is the smallest of 4, 8, 16, 32 that holds ``K_m``; the models of a class keep their
+    order and fill waves of ``64 / cls`` slots one after the other, ``wave[m]`` counted within the class.  Pure host
+    code: the launcher and the tests go by it."""
+    cls = np.asarray([next((c for c in _HMM_GRID_CLASSES if int(k) <= c), 0) for k in Ks], dtype=np.int32)
+    if len(cls) and (cls.min() < 1 or min(int(k) for k in Ks) < 1):
+        raise ValueError('hmm_grid_plan: state counts %s (1 to %d are served)' % (list(Ks), ARHMM_MAX_K))
+    wave, slot = np.zeros_like(cls), np.zeros_like(cls)
+    for c in _HMM_GRID_CLASSES:
+        pos = np.arange(int(np.sum(cls == c)), dtype=np.int32)
+        wave[cls == c], slot[cls == c] = pos // (64 // c), pos % (64 // c)
+    return cls, wave, slot
+
+
+def _hmm_grid_order(Ks):
+    """``(order, counts)`` for the launch from the plan: the models class by class, and the models a class."""
+    cls, wave, slot = hmm_grid_plan(Ks)
+    order, counts = [], []
+    for c in _HMM_GRID_CLASSES:
+        members = np.flatnonzero(cls == c)
+        order.extend(members[np.argsort(wave[members] * (64 // c) + slot[members], kind='stable')].tolist())
+        counts.append(len(members))
+    return np.asarray(order, dtype=np.int32), counts
+
+
+def arhmm_grid_loglik(table, offsets, G, cst, lags, shift=None, out=None):
+    """``arhmm_loglik`` for the states of a grid of models side by side: ``G`` (KT, D, P) and ``cst`` (KT) with
+    KT up to 512 -> float64 (n, KT) (``bn_arhmm_grid_loglik``)."""
+    who = 'arhmm_grid_loglik'
+    n, D, ld = _column_table(who, table)
+    L = int(lags)
+    if not torch.is_tensor(G) and np.ndim(G) != 3 or torch.is_tensor(G) and G.dim() != 3:
+        raise ValueError('%s: expected G float64 (KT, D, P)' % who)
+    KT = int(G.shape[0])
+    check_arhmm_grid_dims(who, D, L, KT)
+    P = 1 + (L + 1) * D
+    dev = table.device
+    G = _f64_operand(who, 'G', G, (KT, D, P), dev)
+    cst = _f64_operand(who, 'cst', cst, (KT,), dev)
+    shift = _f64_operand(who, 'shift', shift, (D,), dev, allow_none=True)
+    offsets = _trial_offsets(who, offsets, dev)
+    S = int(offsets.numel()) - 1
+    if out is None:
+        out = torch.zeros((n, KT), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (n, KT) or out.device != dev or not out.is_contiguous():
+        raise ValueError('%s: expected out float64 (%d, %d) on %s' % (who, n, KT, dev))
+    lib = load()
+    nbytes = lib.bn_arhmm_grid_loglik_ws_bytes(n, S, D, L, KT)
+    if S:
+        _check(lib.bn_arhmm_grid_loglik(table.data_ptr(), ld, None if shift is None else shift.data_ptr(),
+                                        offsets.data_ptr(), S, D, L, KT, n, G.data_ptr(), cst.data_ptr(),
+                                        out.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes, _stream()),
+               'bn_arhmm_grid_loglik')
+    return out
+
+
+def arhmm_grid_moments(table, offsets, gamma, lags, shift=None):
+    """``arhmm_moments`` for the states of a grid of models side by side: ``gamma`` float64 DEVICE (n, KT) with KT
+    up to 512 -> ``(out, gamma0)``, (KT, P, P) and (KT,) (``bn_arhmm_grid_moments``)."""
+    who = 'arhmm_grid_moments'
+    n, D, ld = _column_table(who, table)
+    L = int(lags)
+    if not torch.is_tensor(gamma) or gamma.dim() != 2:
+        raise ValueError('%s: expected gamma float64 (n, KT) on the device' % who)
+    KT = int(gamma.shape[1])
+    check_arhmm_grid_dims(who, D, L, KT)
+    dev = table.device
+    gamma = _f64_operand(who, 'gamma', gamma, (n, KT), dev)
+    shift = _f64_operand(who, 'shift', shift, (D,), dev, allow_none=True)
+    offsets = _trial_offsets(who, offsets, dev)
+    S = int(offsets.numel()) - 1
+    P = 1 + (L + 1) * D
+    out = torch.empty((KT, P, P), dtype=torch.float64, device=dev)
+    gamma0 = torch.empty((KT,), dtype=torch.float64, device=dev)
+    if not S:
+        return out.zero_(), gamma0.zero_()
+    lib = load()
+    nbytes = lib.bn_arhmm_grid_moments_ws_bytes(n, S, D, L, KT)
+    _check(lib.bn_arhmm_grid_moments(table.data_ptr(), ld, None if shift is None else shift.data_ptr(),
+                                     offsets.data_ptr(), S, D, L, KT, n, gamma.data_ptr(), out.data_ptr(),
+                                     gamma0.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes, _stream()),
+           'bn_arhmm_grid_moments')
+    return out, gamma0
+
+
+def hmm_grid_forward_backward(ll, offsets, Ks, log_Ps, log_pi0, want_posteriors=True, gamma=None, xi=None):
+    """Forward-backward of every (trial, model) of a grid over the float64 DEVICE table ``ll`` (n, KT), the models'
+    states side by side (``bn_hmm_grid_forward_backward``): ``(gamma, xi, loglik)``, float64 device tensors (n, KT),
+    (S, XT) and (M, S).  ``Ks``: the M state counts, KT = sum K_m, XT = sum K_m^2; ``log_Ps``: (XT,), the models'
+    (K_m, K_m) matrices row-major one after the other; ``log_pi0``: (KT,).  Model m has the columns
+    ``sum(Ks[:m]) ..`` of ``gamma`` and ``sum(K^2 for K in Ks[:m]) ..`` of ``xi``.  ``want_posteriors=False``: the
+    forward sweep alone, ``(None, None, loglik)``."""
+    who = 'hmm_grid_forward_backward'
+    koff, xoff = check_arhmm_grid_states(who, Ks)
+    M, KT, XT = len(koff) - 1, int(koff[-1]), int(xoff[-1])
+    if not torch.is_tensor(ll) or ll.dim() != 2 or ll.dtype != torch.float64 or int(ll.shape[1]) != KT:
+        raise ValueError('%s: expected ll float64 (n, %d), got %s'
+                         % (who, KT, (ll.dtype, tuple(ll.shape)) if torch.is_tensor(ll) else type(ll).__name__))
+    if not ll.is_cuda:
+        raise ValueError('%s: expected ll on the GPU, got device %s (the HIP path has no CPU fallback)'
+                         % (who, ll.device))
+    if not ll.is_contiguous():
+        raise ValueError('%s: ll must be contiguous, got strides %s' % (who, tuple(ll.stride())))
+    n, dev = int(ll.shape[0]), ll.device
+    log_Ps = _f64_operand(who, 'log_Ps', log_Ps, (XT,), dev)
+    log_pi0 = _f64_operand(who, 'log_pi0', log_pi0, (KT,), dev)
+    offsets = _trial_offsets(who, offsets, dev)
+    S = int(offsets.numel()) - 1
+    loglik = torch.empty((M, S), dtype=torch.float64, device=dev)
+    want = 1 if want_posteriors else 0
+    if want:
+        if gamma is None:
+            gamma = torch.zeros((n, KT), dtype=torch.float64, device=dev)
+        if xi is None:
+            xi = torch.empty((S, XT), dtype=torch.float64, device=dev)
+        for name, t, shape in (('gamma', gamma, (n, KT)), ('xi', xi, (S, XT))):
+            if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+                raise ValueError('%s: expected %s float64 %s on %s' % (who, name, shape, dev))
+    order, counts = _hmm_grid_order(Ks)
+    tables = torch.from_numpy(np.concatenate([koff, xoff, order])).to(dev)          # one upload
+    lib = load()
+    nbytes = lib.bn_hmm_grid_forward_backward_ws_bytes(n, S, M, KT, XT)
+    if S:
+        _check(lib.bn_hmm_grid_forward_backward(ll.data_ptr(), offsets.data_ptr(), S, M, KT, XT, n,
+                                                tables.data_ptr(), tables[M + 1:].data_ptr(),
+                                                tables[2 * M + 2:].data_ptr(), counts[0], counts[1], counts[2],
+                                                counts[3], log_Ps.data_ptr(), log_pi0.data_ptr(), want,
+                                                gamma.data_ptr() if want else None, xi.data_ptr() if want else None,
+                                                loglik.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes, _stream()),
+               'bn_hmm_grid_forward_backward')
+    return (gamma, xi, loglik) if want else (None, None, loglik)
 
 
 # csrc/state_runs.hip's partition, restated for the tests that have to name tile boundaries and the row count at which

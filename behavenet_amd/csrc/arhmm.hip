@@ -61,6 +61,20 @@
 //                order; the NP partial sums of a row are neighbours and are added by DPP moves (xor 1, xor 2, the
 //                other half of eight): a fixed tree, the same bits on every call.  Row z of A comes from global
 //                memory (L2) into registers one step ahead, and only when the state changes.
+// A GRID of models on one table (bn_arhmm_grid_*, bn_hmm_grid_forward_backward): M models with the same D and L, their
+// states side by side as KT = sum K_m columns of G, cst, ll and gamma (model m: columns koff[m] .. koff[m + 1]).
+// k_ar_loglik and k_ar_moments take the KT columns as they take K: full 16-state tiles and whole state groups, the
+// table read once for all models, ar_plan's row blocks growing as the KT partials of a block grow.
+// k_hmm_gfb      forward-backward for the grid, one wave a (trial, 64 / KP models of one CLASS KP = 4, 8, 16, 32 --
+//                the smallest that holds K_m).  The wave is cut into SLOTS of KP lanes; lane slot * KP + j is state j
+//                of the slot's model, and the recursion inside a slot is k_hmm_fb's, with everything that was
+//                wave-wide made slot-wide: the row maximum is a butterfly over the slot's KP lanes (xor KP / 2 .. 1),
+//                the broadcast reads go to the slot's own KP doubles in LDS, s_t is kept by lane (t % KP) of the slot
+//                with one log per KP steps, and the final sum is a butterfly over the slot.  No value crosses a slot's
+//                boundary, so a model's bits do not depend on its slot or on its neighbours, and a NaN stays in its
+//                model.  A padding state (j >= K_m) and an empty slot carry probability zero and write nothing.
+//                One launch a class, the grid (trials, waves of the class); (s_t, max_t) a (model, row) in the
+//                workspace.
 // No global atomics; every output element is written exactly once by each kernel that owns it.
 #include <limits.h>
 #include <math.h>
@@ -83,6 +97,8 @@
 #define AR_BT_ROWS 64                       // rows of back-pointers the walk back holds in LDS
 #define AR_S_ROWS 64                        // sampling: rows of a window (k_ars_recur), uniforms of a chunk
 #define AR_S_MAX_D 32                       // D at most where L > 0
+#define AR_GRID_MAX_KT 512                  // a grid of models: states of all models together at most ...
+#define AR_GRID_MAX_M 512                   // ... and models
 
 typedef double ar_d4 __attribute__((ext_vector_type(4)));
 
@@ -91,8 +107,8 @@ struct ArPlan {
     int rows;         // rows per block (the last block takes what is left)
 };
 
-static bool ar_dims_ok(int D, int L, int K) {
-    return K >= 1 && K <= AR_MAX_K && L >= 0 && L <= AR_MAX_L && D >= 1 && (L + 1) * (long)D <= AR_MAX_LD;
+static bool ar_dims_ok(int D, int L, int K, int max_k = AR_MAX_K) {
+    return K >= 1 && K <= max_k && L >= 0 && L <= AR_MAX_L && D >= 1 && (L + 1) * (long)D <= AR_MAX_LD;
 }
 
 // the ONE partition of k_ar_moments the workspace query, the launch and the combine go by
@@ -369,6 +385,183 @@ __global__ __launch_bounds__(BN_WAVE) void k_hmm_fb(const double* __restrict__ l
 #pragma unroll
         for (int j = 0; j < KP; ++j)
             if (j < K) xi[((size_t)s * K + lane) * K + j] = acc[j];
+    }
+}
+
+// ---- the grid of models: slots of KP lanes
+template <int KP>
+__device__ __forceinline__ double ar_slot_max(double v) {
+#pragma unroll
+    for (int o = KP / 2; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+
+template <int KP>
+__device__ __forceinline__ double ar_slot_sum(double v) {
+#pragma unroll
+    for (int o = KP / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// `order` lists the `count` models of the class KP; wave blockIdx.y takes the models order[blockIdx.y * SL + slot].
+// A model number outside [0, M), a state count outside [1, KP] or columns outside [0, KT) / [0, XT) make an empty
+// slot: whatever the tables hold, nothing is read or written outside the operands.
+template <int KP>
+__global__ __launch_bounds__(BN_WAVE) void k_hmm_gfb(const double* __restrict__ ll, const int* __restrict__ e, int n,
+                                                     int S, int M, int KT, int XT, const int* __restrict__ koff,
+                                                     const int* __restrict__ xoff, const int* __restrict__ order,
+                                                     int count, const double* __restrict__ logP,
+                                                     const double* __restrict__ logpi0, int want,
+                                                     double* __restrict__ gamma, double* __restrict__ xi,
+                                                     double* __restrict__ loglik, double* __restrict__ cm) {
+    constexpr int SL = BN_WAVE / KP;
+    __shared__ __attribute__((aligned(16))) double buf[2][2][BN_WAVE];         // [parity][v or g][slot * KP + state]
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int slot = lane / KP, base = slot * KP, j = lane - base;
+    const int beg = e[s], T = e[s + 1] - beg;
+    const int idx = blockIdx.y * SL + slot;
+    int m = idx < count ? order[idx] : -1;
+    int K = 0, k0 = 0, x0 = 0;
+    if (m >= 0 && m < M) {
+        k0 = koff[m];
+        K = koff[m + 1] - k0;
+        x0 = xoff[m];
+        if (K < 1 || K > KP || k0 < 0 || k0 > KT - K || x0 < 0 || x0 > XT - K * K) K = 0;
+    }
+    if (!K) m = 0;                                         // (an empty slot: no lane of it is active)
+    const bool active = j < K, head = active && j == 0;
+    if (T <= 0) {
+        if (head) loglik[(size_t)m * S + s] = 0.0;
+        if (want)
+            for (int o = j; o < K * K; o += KP) xi[(size_t)s * XT + x0 + o] = 0.0;
+        return;
+    }
+    const double* l = ll + (size_t)beg * KT + k0 + j;
+    double* gam = gamma + (size_t)beg * KT + k0 + j;
+    double* cmt = cm + ((size_t)m * n + beg) * 2;
+    const double* lp = logP + x0;
+    const double ninf = -INFINITY;
+
+    double Pc[KP];
+#pragma unroll
+    for (int i = 0; i < KP; ++i) Pc[i] = active && i < K ? exp(lp[i * K + j]) : 0.0;
+    const double pi = active ? exp(logpi0[k0 + j]) : 0.0;
+
+    double lsum = 0.0, msum = 0.0, pend = 1.0, dot = 0.0;
+    double mx, b;
+    {
+        const double lv = active ? l[0] : ninf;
+        mx = ar_slot_max<KP>(lv);
+        b = active ? exp(lv - mx) : 0.0;
+    }
+    double l1 = active && T > 1 ? l[(size_t)KT] : ninf;
+    for (int t = 0; t < T; ++t) {
+        const double l2 = active && t + 2 < T ? l[(size_t)(t + 2) * KT] : ninf;
+        const double u = t == 0 ? pi * b : dot * b;
+        const int par = t & 1;
+        buf[par][0][lane] = u;
+        __syncthreads();
+        const double mn = ar_slot_max<KP>(l1);
+        const double bn = active ? exp(l1 - mn) : 0.0;     // (row T: -inf - -inf, a NaN nobody reads)
+        double s4[4] = {0.0, 0.0, 0.0, 0.0}, d4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int i = 0; i < KP; ++i) {
+            const double ui = buf[par][0][base + i];
+            s4[i & 3] += ui;
+            d4[i & 3] += ui * Pc[i];
+        }
+        const double st = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+        const double inv = 1.0 / st;
+        dot = ((d4[0] + d4[1]) + (d4[2] + d4[3])) * inv;
+        if (want) {
+            if (active) gam[(size_t)t * KT] = u * inv;
+            if (head) {
+                cmt[2 * (size_t)t] = st;
+                cmt[2 * (size_t)t + 1] = mx;
+            }
+        }
+        msum += mx;
+        pend = j == (t & (KP - 1)) ? st : pend;            // lane t % KP of the slot keeps s_t
+        if ((t & (KP - 1)) == KP - 1) {
+            lsum += log(pend);
+            pend = 1.0;
+        }
+        mx = mn;
+        b = bn;
+        l1 = l2;
+    }
+    lsum += log(pend);
+    const double total = ar_slot_sum<KP>(lsum) + msum;
+    if (head) loglik[(size_t)m * S + s] = total;
+    if (!want) return;
+
+    // ---- backward: gamma holds ahat, cm holds (s_t, max_t); lane (slot, i) is the SOURCE state now
+    __syncthreads();                                       // (cm, written by the slot's first lane, is read by all of it)
+    double Pr[KP], acc[KP];
+#pragma unroll
+    for (int i = 0; i < KP; ++i) {
+        Pr[i] = active && i < K ? exp(lp[j * K + i]) : 0.0;
+        acc[i] = 0.0;
+    }
+    int par = 0;
+    {
+        const size_t t = T - 1;
+        const double bl = active ? exp(l[t * KT] - cmt[2 * t + 1]) : 0.0;
+        buf[par][0][lane] = active ? bl / cmt[2 * t] : 0.0;
+        __syncthreads();
+    }
+    double a = 0.0, bq = 0.0, a1 = 0.0, q1 = ninf, s1 = 1.0, m1 = 0.0;
+    if (T >= 2) {
+        const size_t t = T - 2;
+        a = active ? gam[t * KT] : 0.0;
+        bq = active ? exp(l[t * KT] - cmt[2 * t + 1]) / cmt[2 * t] : 0.0;
+    }
+    if (T >= 3 && K) {
+        const size_t t = T - 3;
+        a1 = active ? gam[t * KT] : 0.0;
+        q1 = active ? l[t * KT] : ninf;
+        s1 = cmt[2 * t];
+        m1 = cmt[2 * t + 1];
+    }
+    for (int t = T - 2; t >= 0; --t) {
+        double a2 = 0.0, q2 = ninf, s2 = 1.0, m2 = 0.0;
+        if (t > 1 && K) {
+            const size_t r = t - 2;
+            a2 = active ? gam[r * KT] : 0.0;
+            q2 = active ? l[r * KT] : ninf;
+            s2 = cmt[2 * r];
+            m2 = cmt[2 * r + 1];
+        }
+        const double bq1 = active ? exp(q1 - m1) / s1 : 0.0;
+        double b4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int i = 0; i < KP; ++i) {
+            const double pv = Pr[i] * buf[par][0][base + i];
+            b4[i & 3] += pv;
+            acc[i] += a * pv;
+        }
+        const double beta = (b4[0] + b4[1]) + (b4[2] + b4[3]);
+        const double g = a * beta;
+        par ^= 1;
+        buf[par][0][lane] = bq * beta;
+        buf[par][1][lane] = g;
+        __syncthreads();
+        double z4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int i = 0; i < KP; ++i) z4[i & 3] += buf[par][1][base + i];
+        const double Z = (z4[0] + z4[1]) + (z4[2] + z4[3]);
+        if (active) gam[(size_t)t * KT] = g / Z;
+        a = a1;
+        bq = bq1;
+        a1 = a2;
+        q1 = q2;
+        s1 = s2;
+        m1 = m2;
+    }
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < KP; ++i)
+            if (i < K) xi[(size_t)s * XT + x0 + j * K + i] = acc[i];
     }
 }
 
@@ -752,6 +945,16 @@ bool bn_arhmm_ok(int n, int S, int D, int L, int K) {
     return n >= 0 && S >= 0 && S < INT32_MAX && ar_dims_ok(D, L, K);
 }
 
+// the grid's limits: KT states of all models together, M models, XT = sum K_m^2 transition entries
+bool bn_arhmm_grid_ok(int n, int S, int D, int L, int KT) {
+    return n >= 0 && S >= 0 && S < INT32_MAX && ar_dims_ok(D, L, KT, AR_GRID_MAX_KT);
+}
+
+bool bn_hmm_grid_ok(int n, int S, int M, int KT, int XT) {
+    return n >= 0 && S >= 0 && S < INT32_MAX && M >= 1 && M <= AR_GRID_MAX_M && KT >= M && KT <= AR_GRID_MAX_KT &&
+           XT >= KT && XT <= AR_MAX_K * KT;
+}
+
 bool bn_hmm_ok(int n, int S, int K) { return n >= 0 && S >= 0 && S < INT32_MAX && K >= 1 && K <= AR_MAX_K; }
 
 size_t bn_arhmm_loglik_ws_bytes_impl(int n, int S, int D, int L, int K) {
@@ -763,6 +966,22 @@ size_t bn_arhmm_moments_ws_bytes_impl(int n, int S, int D, int L, int K) {
     if (!bn_arhmm_ok(n, S, D, L, K)) return 0;
     const size_t P = 1 + (size_t)(L + 1) * D;
     return ar_offsets_bytes(S) + ar_pad16((size_t)n) + (size_t)ar_plan(n, D, L, K).blocks * K * P * P * sizeof(double);
+}
+
+size_t bn_arhmm_grid_loglik_ws_bytes_impl(int n, int S, int D, int L, int KT) {
+    if (!bn_arhmm_grid_ok(n, S, D, L, KT)) return 0;
+    return ar_offsets_bytes(S) + ar_pad16((size_t)n);
+}
+
+size_t bn_arhmm_grid_moments_ws_bytes_impl(int n, int S, int D, int L, int KT) {
+    if (!bn_arhmm_grid_ok(n, S, D, L, KT)) return 0;
+    const size_t P = 1 + (size_t)(L + 1) * D;
+    return ar_offsets_bytes(S) + ar_pad16((size_t)n) + (size_t)ar_plan(n, D, L, KT).blocks * KT * P * P * sizeof(double);
+}
+
+size_t bn_hmm_grid_forward_backward_ws_bytes_impl(int n, int S, int M, int KT, int XT) {
+    if (!bn_hmm_grid_ok(n, S, M, KT, XT)) return 0;
+    return ar_offsets_bytes(S) + (size_t)M * n * 2 * sizeof(double);
 }
 
 size_t bn_hmm_forward_backward_ws_bytes_impl(int n, int S, int K) {
@@ -788,9 +1007,9 @@ static int ar_launch_kind(const long long* offsets, int S, int L, int n, void* w
     return 0;
 }
 
-int bn_launch_arhmm_loglik(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L,
-                           int K, int n, const double* G, const double* cst, double* ll, void* ws, hipStream_t st) {
-    if (!bn_arhmm_ok(n, S, D, L, K)) return BN_E_SHAPE;
+// (the callers have checked K against their own limit: 32 for a model, AR_GRID_MAX_KT for a grid)
+static int ar_launch_loglik(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L,
+                            int K, int n, const double* G, const double* cst, double* ll, void* ws, hipStream_t st) {
     if (S == 0) return 0;
     const int rc = ar_launch_kind(offsets, S, L, n, ws, st);
     if (rc) return rc;
@@ -803,10 +1022,22 @@ int bn_launch_arhmm_loglik(const float* z, int ld, const double* c, const long l
     return 0;
 }
 
-int bn_launch_arhmm_moments(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L,
-                            int K, int n, const double* gamma, double* out, double* gamma0, void* ws,
-                            hipStream_t st) {
+int bn_launch_arhmm_loglik(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L,
+                           int K, int n, const double* G, const double* cst, double* ll, void* ws, hipStream_t st) {
     if (!bn_arhmm_ok(n, S, D, L, K)) return BN_E_SHAPE;
+    return ar_launch_loglik(z, ld, c, offsets, S, D, L, K, n, G, cst, ll, ws, st);
+}
+
+int bn_launch_arhmm_grid_loglik(const float* z, int ld, const double* c, const long long* offsets, int S, int D,
+                                int L, int KT, int n, const double* G, const double* cst, double* ll, void* ws,
+                                hipStream_t st) {
+    if (!bn_arhmm_grid_ok(n, S, D, L, KT)) return BN_E_SHAPE;
+    return ar_launch_loglik(z, ld, c, offsets, S, D, L, KT, n, G, cst, ll, ws, st);
+}
+
+static int ar_launch_moments(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L,
+                             int K, int n, const double* gamma, double* out, double* gamma0, void* ws,
+                             hipStream_t st) {
     if (S == 0) return 0;
     const int rc = ar_launch_kind(offsets, S, L, n, ws, st);
     if (rc) return rc;
@@ -836,6 +1067,20 @@ int bn_launch_arhmm_moments(const float* z, int ld, const double* c, const long 
     return 0;
 }
 
+int bn_launch_arhmm_moments(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L,
+                            int K, int n, const double* gamma, double* out, double* gamma0, void* ws,
+                            hipStream_t st) {
+    if (!bn_arhmm_ok(n, S, D, L, K)) return BN_E_SHAPE;
+    return ar_launch_moments(z, ld, c, offsets, S, D, L, K, n, gamma, out, gamma0, ws, st);
+}
+
+int bn_launch_arhmm_grid_moments(const float* z, int ld, const double* c, const long long* offsets, int S, int D,
+                                 int L, int KT, int n, const double* gamma, double* out, double* gamma0, void* ws,
+                                 hipStream_t st) {
+    if (!bn_arhmm_grid_ok(n, S, D, L, KT)) return BN_E_SHAPE;
+    return ar_launch_moments(z, ld, c, offsets, S, D, L, KT, n, gamma, out, gamma0, ws, st);
+}
+
 int bn_launch_hmm_forward_backward(const double* ll, const long long* offsets, int S, int K, int n,
                                    const double* logP, const double* logpi0, int want, double* gamma, double* xi,
                                    double* loglik, void* ws, hipStream_t st) {
@@ -852,6 +1097,43 @@ int bn_launch_hmm_forward_backward(const double* ll, const long long* offsets, i
     else if (K <= 16) hipLaunchKernelGGL(k_hmm_fb<16>, grid, block, 0, st, ll, ce, K, logP, logpi0, want, gamma, xi, loglik, cm);
     else hipLaunchKernelGGL(k_hmm_fb<32>, grid, block, 0, st, ll, ce, K, logP, logpi0, want, gamma, xi, loglik, cm);
     BN_LAUNCH_CHECK();
+    return 0;
+}
+
+// order: the models of class 4, then of 8, 16 and 32 (counts[0..3] of them), every model once; one launch a class
+int bn_launch_hmm_grid_forward_backward(const double* ll, const long long* offsets, int S, int M, int KT, int XT, int n,
+                                        const int* koff, const int* xoff, const int* order, const int* counts,
+                                        const double* logP, const double* logpi0, int want, double* gamma, double* xi,
+                                        double* loglik, void* ws, hipStream_t st) {
+    if (!bn_hmm_grid_ok(n, S, M, KT, XT)) return BN_E_SHAPE;
+    long sum = 0;
+    for (int c = 0; c < 4; ++c) {
+        if (counts[c] < 0 || counts[c] > M) return BN_E_SHAPE;
+        sum += counts[c];
+    }
+    if (sum != M) return BN_E_SHAPE;
+    if (S == 0) return 0;
+    int* e = reinterpret_cast<int*>(ws);
+    double* cm = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + ar_offsets_bytes(S));
+    const int rc = bn_launch_segment_offsets(offsets, S + 1, n, e, st);
+    if (rc) return rc;
+    const int* ce = e;
+    const dim3 block(BN_WAVE);
+    int first = 0;
+    for (int c = 0; c < 4; ++c) {
+        const int cnt = counts[c], KP = 4 << c, SL = BN_WAVE / KP;
+        if (!cnt) continue;
+        const dim3 grid((unsigned)S, (unsigned)((cnt + SL - 1) / SL));
+        const int* ord = order + first;
+        switch (KP) {
+            case 4: hipLaunchKernelGGL(k_hmm_gfb<4>, grid, block, 0, st, ll, ce, n, S, M, KT, XT, koff, xoff, ord, cnt, logP, logpi0, want, gamma, xi, loglik, cm); break;
+            case 8: hipLaunchKernelGGL(k_hmm_gfb<8>, grid, block, 0, st, ll, ce, n, S, M, KT, XT, koff, xoff, ord, cnt, logP, logpi0, want, gamma, xi, loglik, cm); break;
+            case 16: hipLaunchKernelGGL(k_hmm_gfb<16>, grid, block, 0, st, ll, ce, n, S, M, KT, XT, koff, xoff, ord, cnt, logP, logpi0, want, gamma, xi, loglik, cm); break;
+            default: hipLaunchKernelGGL(k_hmm_gfb<32>, grid, block, 0, st, ll, ce, n, S, M, KT, XT, koff, xoff, ord, cnt, logP, logpi0, want, gamma, xi, loglik, cm); break;
+        }
+        BN_LAUNCH_CHECK();
+        first += cnt;
+    }
     return 0;
 }
 

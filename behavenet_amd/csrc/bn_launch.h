@@ -160,6 +160,22 @@ int bn_launch_hmm_forward_backward(const double* ll, const long long* offsets, i
                                    double* loglik, void* ws, hipStream_t st);
 int bn_launch_hmm_viterbi(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
                           const double* logpi0, int* states, void* ws, hipStream_t st);
+// ... and the same for a grid of M models on one table, KT = sum K_m states side by side (XT = sum K_m^2)
+bool bn_arhmm_grid_ok(int n, int S, int D, int L, int KT);
+bool bn_hmm_grid_ok(int n, int S, int M, int KT, int XT);
+size_t bn_arhmm_grid_loglik_ws_bytes_impl(int n, int S, int D, int L, int KT);
+size_t bn_arhmm_grid_moments_ws_bytes_impl(int n, int S, int D, int L, int KT);
+size_t bn_hmm_grid_forward_backward_ws_bytes_impl(int n, int S, int M, int KT, int XT);
+int bn_launch_arhmm_grid_loglik(const float* z, int ld, const double* c, const long long* offsets, int S, int D,
+                                int L, int KT, int n, const double* G, const double* cst, double* ll, void* ws,
+                                hipStream_t st);
+int bn_launch_arhmm_grid_moments(const float* z, int ld, const double* c, const long long* offsets, int S, int D,
+                                 int L, int KT, int n, const double* gamma, double* out, double* gamma0, void* ws,
+                                 hipStream_t st);
+int bn_launch_hmm_grid_forward_backward(const double* ll, const long long* offsets, int S, int M, int KT, int XT, int n,
+                                        const int* koff, const int* xoff, const int* order, const int* counts,
+                                        const double* logP, const double* logpi0, int want, double* gamma, double* xi,
+                                        double* loglik, void* ws, hipStream_t st);
 // ... and the model's generative process from the caller's noise: states from uniforms (or given), latents from normals
 size_t bn_arhmm_sample_ws_bytes_impl(int n, int S, int D, int L, int K);
 int bn_launch_arhmm_sample(const double* W, const double* C, const double* cdf0, const double* cdf,

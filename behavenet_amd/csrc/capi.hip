@@ -2165,6 +2165,63 @@ extern "C" int bn_hmm_viterbi(const double* ll, const long long* offsets, int S,
     return bn_launch_hmm_viterbi(ll, offsets, S, K, n, logP, logpi0, states, ws, (hipStream_t)stream);
 }
 
+// ... and for a grid of models on one table (KT = sum K_m states side by side)
+extern "C" size_t bn_arhmm_grid_loglik_ws_bytes(int n, int S, int D, int L, int KT) {
+    return bn_arhmm_grid_loglik_ws_bytes_impl(n, S, D, L, KT);
+}
+
+extern "C" size_t bn_arhmm_grid_moments_ws_bytes(int n, int S, int D, int L, int KT) {
+    return bn_arhmm_grid_moments_ws_bytes_impl(n, S, D, L, KT);
+}
+
+extern "C" size_t bn_hmm_grid_forward_backward_ws_bytes(int n, int S, int M, int KT, int XT) {
+    return bn_hmm_grid_forward_backward_ws_bytes_impl(n, S, M, KT, XT);
+}
+
+extern "C" int bn_arhmm_grid_loglik(const float* z, int ld, const double* c, const long long* offsets, int S, int D,
+                                    int L, int KT, int n, const double* G, const double* cst, double* ll, void* ws,
+                                    size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_arhmm_grid_ok(n, S, D, L, KT) || ld < D) return BN_E_SHAPE;
+    if (!z || !offsets || !G || !cst || !ll || !ws) return BN_E_BADARG;
+    if (((uintptr_t)z & 3) || ((uintptr_t)c & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)G & 7) ||
+        ((uintptr_t)cst & 7) || ((uintptr_t)ll & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_arhmm_grid_loglik_ws_bytes_impl(n, S, D, L, KT)) return BN_E_SHAPE;
+    return bn_launch_arhmm_grid_loglik(z, ld, c, offsets, S, D, L, KT, n, G, cst, ll, ws, (hipStream_t)stream);
+}
+
+extern "C" int bn_arhmm_grid_moments(const float* z, int ld, const double* c, const long long* offsets, int S, int D,
+                                     int L, int KT, int n, const double* gamma, double* out, double* gamma0, void* ws,
+                                     size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_arhmm_grid_ok(n, S, D, L, KT) || ld < D) return BN_E_SHAPE;
+    if (!z || !offsets || !gamma || !out || !gamma0 || !ws) return BN_E_BADARG;
+    if (((uintptr_t)z & 3) || ((uintptr_t)c & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)gamma & 7) ||
+        ((uintptr_t)out & 7) || ((uintptr_t)gamma0 & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_arhmm_grid_moments_ws_bytes_impl(n, S, D, L, KT)) return BN_E_SHAPE;
+    return bn_launch_arhmm_grid_moments(z, ld, c, offsets, S, D, L, KT, n, gamma, out, gamma0, ws,
+                                        (hipStream_t)stream);
+}
+
+extern "C" int bn_hmm_grid_forward_backward(const double* ll, const long long* offsets, int S, int M, int KT, int XT,
+                                            int n, const int* koff, const int* xoff, const int* order, int n4, int n8,
+                                            int n16, int n32, const double* logP, const double* logpi0, int want,
+                                            double* gamma, double* xi, double* loglik, void* ws, size_t ws_bytes,
+                                            bn_stream_t stream) {
+    if (!bn_hmm_grid_ok(n, S, M, KT, XT) || want < 0 || want > 1) return BN_E_SHAPE;
+    if (n4 < 0 || n8 < 0 || n16 < 0 || n32 < 0 || (long)n4 + n8 + n16 + n32 != M) return BN_E_SHAPE;
+    if (!ll || !offsets || !koff || !xoff || !order || !logP || !logpi0 || !loglik || !ws || (want && (!gamma || !xi)))
+        return BN_E_BADARG;
+    if (((uintptr_t)ll & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)koff & 3) || ((uintptr_t)xoff & 3) ||
+        ((uintptr_t)order & 3) || ((uintptr_t)logP & 7) || ((uintptr_t)logpi0 & 7) || ((uintptr_t)gamma & 7) ||
+        ((uintptr_t)xi & 7) || ((uintptr_t)loglik & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_hmm_grid_forward_backward_ws_bytes_impl(n, S, M, KT, XT)) return BN_E_SHAPE;
+    const int counts[4] = {n4, n8, n16, n32};
+    return bn_launch_hmm_grid_forward_backward(ll, offsets, S, M, KT, XT, n, koff, xoff, order, counts, logP, logpi0,
+                                               want, gamma, xi, loglik, ws, (hipStream_t)stream);
+}
+
 extern "C" size_t bn_arhmm_sample_ws_bytes(int n, int S, int D, int L, int K) {
     return bn_arhmm_sample_ws_bytes_impl(n, S, D, L, K);
 }

@@ -40,7 +40,8 @@ __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconst
            'percentile_plan', 'percentile_lerp', 'column_percentiles', 'compute_range', 'latent_ranges',
            'latent_ranges_device', 'summarise_label_sums', 'label_r2', 'export_label_r2', 'summarise_gram',
            'latent_correlations', 'export_latent_correlations', 'session_classifier', 'export_session_classifier',
-           'classify_table', 'score_table', 'fit_arhmm', 'fit_arhmm_tables', 'export_states', 'export_arhmm']
+           'classify_table', 'score_table', 'fit_arhmm', 'fit_arhmm_tables', 'export_states', 'export_arhmm',
+           'arhmm_grid', 'arhmm_grid_groups', 'fit_arhmm_grid', 'fit_arhmm_grid_tables']
 
 
 def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -2097,18 +2098,60 @@ def _arhmm_loss(lls, offsets, sel, D):
     return float(-np.sum(lls[sel]) / (frames * D)) if frames else float('nan')
 
 
-def _fit_arhmm_splits(splits, n_datasets, n_states, n_lags, transitions, kappa, n_iters, tol, rng_seed_model,
-                      noise_type):
+def _new_arhmm(D, n_states, n_lags, transitions, kappa, noise_type):
+    """The model of one configuration, or the error that names what is not served."""
     from behavenet_amd.models.arhmm import ARHMM
     if noise_type not in _ARHMM_NOISE:
         raise NotImplementedError('fit_arhmm: noise_type %r is not served (gaussian is)' % (noise_type,))
-    train, t_off, t_sess, _ = splits['train']
+    return ARHMM(n_states, D, lags=n_lags, transitions='stationary' if transitions == 'standard' else transitions,
+                 kappa=kappa)
+
+
+def _arhmm_epoch_rows(rows, epoch, tr_lls, val_lls, splits, n_datasets, D, val_prev, tol):
+    """The rows of one epoch -- pooled, then one a session -- appended to ``rows``.  -> ``(stop, val_ll)``: whether
+    the fit stops after this epoch, and the ``val_loss`` the next epoch compares with."""
+    _, t_off, t_sess, _ = splits['train']
+    _, v_off, v_sess, _ = splits['val']
+    every_t, every_v = np.ones(len(t_sess), dtype=bool), np.ones(len(v_sess), dtype=bool)
+    val_ll = _arhmm_loss(val_lls, v_off, every_v, D)
+    rows.append({'epoch': epoch, 'dataset': -1, 'tr_loss': _arhmm_loss(tr_lls, t_off, every_t, D),
+                 'val_loss': val_ll, 'trial': -1})
+    for d in n_datasets:
+        val_ll = _arhmm_loss(val_lls, v_off, v_sess == d, D)
+        rows.append({'epoch': epoch, 'dataset': d, 'tr_loss': _arhmm_loss(tr_lls, t_off, t_sess == d, D),
+                     'val_loss': val_ll, 'trial': -1})
+    # (the reference compares the val_loss it computed last: the last session's)
+    if epoch > 10 and np.abs((val_ll - val_prev) / val_ll) < tol:
+        print('relative change less than tolerance=%1.2f; training terminating!' % tol)
+        return True, val_ll
+    return False, val_ll
+
+
+def _arhmm_test_rows(rows, epoch, test_lls, splits, D):
+    _, s_off, s_sess, s_trial = splits['test']
+    for i in np.argsort(s_sess, kind='stable'):
+        frames = int(s_off[i + 1] - s_off[i])
+        rows.append({'epoch': epoch, 'dataset': int(s_sess[i]),
+                     'test_loss': float(-test_lls[i] / (frames * D)) if frames else float('nan'),
+                     'trial': int(s_trial[i])})
+
+
+def _arhmm_relabel(arhmm, train, t_off):
+    """States relabelled by usage on the training trials."""
+    usage = np.bincount(arhmm.table_states(train, t_off), minlength=arhmm.K)
+    arhmm.permute(np.argsort(usage)[::-1])
+
+
+def _fit_arhmm_splits(splits, n_datasets, n_states, n_lags, transitions, kappa, n_iters, tol, rng_seed_model,
+                      noise_type):
+    if noise_type not in _ARHMM_NOISE:
+        raise NotImplementedError('fit_arhmm: noise_type %r is not served (gaussian is)' % (noise_type,))
+    train, t_off, _, _ = splits['train']
     if train is None:
         raise ValueError('fit_arhmm: no train frames')
-    val, v_off, v_sess, _ = splits['val']
+    val, v_off, _, _ = splits['val']
     D = int(train.shape[1])
-    arhmm = ARHMM(n_states, D, lags=n_lags, transitions='stationary' if transitions == 'standard' else transitions,
-                  kappa=kappa)
+    arhmm = _new_arhmm(D, n_states, n_lags, transitions, kappa, noise_type)
     arhmm.initialize(train, t_off, seed=rng_seed_model)
     rows, stats, val_prev, epoch = [], None, np.inf, 0
     for epoch in range(int(n_iters) + 1):
@@ -2119,31 +2162,159 @@ def _fit_arhmm_splits(splits, n_datasets, n_states, n_lags, transitions, kappa, 
         mom, _, xi_sum, g0, tr_lls = arhmm.e_step(train, t_off)
         stats = (mom, xi_sum, g0)
         val_lls = arhmm.trial_logliks(val, v_off) if val is not None else np.zeros((0,))
-        every_t, every_v = np.ones(len(t_sess), dtype=bool), np.ones(len(v_sess), dtype=bool)
-        val_ll = _arhmm_loss(val_lls, v_off, every_v, D)
-        rows.append({'epoch': epoch, 'dataset': -1, 'tr_loss': _arhmm_loss(tr_lls, t_off, every_t, D),
-                     'val_loss': val_ll, 'trial': -1})
-        for d in n_datasets:
-            val_ll = _arhmm_loss(val_lls, v_off, v_sess == d, D)
-            rows.append({'epoch': epoch, 'dataset': d, 'tr_loss': _arhmm_loss(tr_lls, t_off, t_sess == d, D),
-                         'val_loss': val_ll, 'trial': -1})
-        # (the reference compares the val_loss it computed last: the last session's)
-        if epoch > 10 and np.abs((val_ll - val_prev) / val_ll) < tol:
-            print('relative change less than tolerance=%1.2f; training terminating!' % tol)
+        stop, val_prev = _arhmm_epoch_rows(rows, epoch, tr_lls, val_lls, splits, n_datasets, D, val_prev, tol)
+        if stop:
             break
-        val_prev = val_ll
-    test, s_off, s_sess, s_trial = splits['test']
+    test, s_off, _, _ = splits['test']
     if test is not None:
-        test_lls = arhmm.trial_logliks(test, s_off)
-        for i in np.argsort(s_sess, kind='stable'):
-            frames = int(s_off[i + 1] - s_off[i])
-            rows.append({'epoch': epoch, 'dataset': int(s_sess[i]),
-                         'test_loss': float(-test_lls[i] / (frames * D)) if frames else float('nan'),
-                         'trial': int(s_trial[i])})
-    # states relabelled by usage on the training trials
-    usage = np.bincount(arhmm.table_states(train, t_off), minlength=arhmm.K)
-    arhmm.permute(np.argsort(usage)[::-1])
+        _arhmm_test_rows(rows, epoch, arhmm.trial_logliks(test, s_off), splits, D)
+    _arhmm_relabel(arhmm, train, t_off)
     return arhmm, rows
+
+
+# ------------------------------------------------------------------------------------------ a grid of ARHMMs
+ARHMM_GRID_TABLE_BYTES = 8 << 30        # ll plus gamma of one group of a grid, float64 (rows, states): 8 GiB
+
+
+def arhmm_grid(n_states, n_lags=(1,), transitions=('stationary',), kappa=(0,), rng_seed_model=(0,)):
+    """The configurations of a grid search: the cartesian product of the arguments (a scalar counts as one value) as
+    a list of dicts of ``fit_arhmm``'s keyword arguments, in ``itertools.product``'s order over the arguments as
+    listed, without the combinations the reference's driver refuses to fit (fitting/arhmm_grid_search.py:25-30):
+    ``sticky`` with ``kappa == 0`` and anything else with ``kappa > 0``.  Pure host code."""
+    import itertools
+    names = ('n_states', 'n_lags', 'transitions', 'kappa', 'rng_seed_model')
+    axes = [list(v) if isinstance(v, (list, tuple, np.ndarray, range)) else [v]
+            for v in (n_states, n_lags, transitions, kappa, rng_seed_model)]
+    grid = []
+    for combo in itertools.product(*axes):
+        cfg = dict(zip(names, combo))
+        if cfg['transitions'] == 'sticky' and cfg['kappa'] == 0:
+            continue
+        if cfg['transitions'] != 'sticky' and cfg['kappa'] > 0:
+            continue
+        grid.append(cfg)
+    return grid
+
+
+_ARHMM_GRID_KEYS = ('n_states', 'n_lags', 'transitions', 'kappa', 'rng_seed_model', 'noise_type')
+
+
+def _arhmm_grid_config(cfg):
+    """``cfg`` with ``fit_arhmm``'s defaults filled in."""
+    if not isinstance(cfg, dict) or 'n_states' not in cfg or set(cfg) - set(_ARHMM_GRID_KEYS):
+        raise ValueError('fit_arhmm_grid: a configuration is a dict with n_states and any of %s, got %r'
+                         % (', '.join(_ARHMM_GRID_KEYS[1:]), cfg))
+    full = {'n_lags': 1, 'transitions': 'stationary', 'kappa': 0, 'rng_seed_model': 0, 'noise_type': 'gaussian'}
+    full.update(cfg)
+    return full
+
+
+def arhmm_grid_groups(grid, n_rows, max_states=None, max_bytes=ARHMM_GRID_TABLE_BYTES):
+    """The configurations of ``grid`` cut into groups that advance in one set of launches: lists of positions in
+    ``grid``, every position once.  A group has ONE ``n_lags``, at
+    most ``max_states`` (512) states and 512 models together, and its ``ll`` and ``gamma`` tables on ``n_rows`` rows
+    -- ``2 * 8 * n_rows * states`` bytes -- within ``max_bytes`` (a configuration that is beyond that alone is a
+    group of its own).  The configurations of a group keep the grid's order; a group is closed when the next
+    configuration of its ``n_lags`` does not fit.  Pure host code."""
+    from behavenet_amd import _hip
+    max_states = _hip.ARHMM_GRID_MAX_STATES if max_states is None else int(max_states)
+    groups, open_group = [], {}
+    for i, cfg in enumerate(grid):
+        cfg = _arhmm_grid_config(cfg)
+        K, lags = int(cfg['n_states']), int(cfg['n_lags'])
+        g = open_group.get(lags)
+        if g is not None:
+            states = sum(int(grid[j]['n_states']) for j in g) + K
+            if states > max_states or len(g) >= _hip.ARHMM_GRID_MAX_MODELS or 16 * int(n_rows) * states > max_bytes:
+                g = None
+        if g is None:
+            g = []
+            groups.append(g)
+            open_group[lags] = g
+        g.append(i)
+    return groups
+
+
+def _fit_arhmm_grid_splits(splits, n_datasets, grid, n_iters, tol):
+    from behavenet_amd.models.arhmm import ARHMMGroup
+    train, t_off, _, _ = splits['train']
+    if train is None:
+        raise ValueError('fit_arhmm: no train frames')
+    val, v_off, _, _ = splits['val']
+    test, s_off, _, _ = splits['test']
+    D = int(train.shape[1])
+    grid = [_arhmm_grid_config(cfg) for cfg in grid]
+    # every configuration is built -- and refused, if it is not served -- before the first epoch of any
+    models = [_new_arhmm(D, c['n_states'], c['n_lags'], c['transitions'], c['kappa'], c['noise_type']) for c in grid]
+    out = [None] * len(grid)
+    for members in arhmm_grid_groups(grid, int(train.shape[0])):
+        for i in members:
+            models[i].initialize(train, t_off, seed=grid[i]['rng_seed_model'])
+        rows = {i: [] for i in members}
+        val_prev, last = {i: np.inf for i in members}, {i: 0 for i in members}
+        active, grouped, group, stats = list(members), None, None, {}
+        for epoch in range(int(n_iters) + 1):
+            if not active:
+                break
+            if grouped != active:
+                # a model that has stopped leaves the launches; its parameters are those of its last epoch
+                group, grouped = ARHMMGroup([models[i] for i in active]), list(active)
+            if epoch > 0:
+                group.m_step([stats[i] for i in active])
+            stats = dict(zip(active, group.e_step(train, t_off)))
+            val_lls = group.trial_logliks(val, v_off) if val is not None else np.zeros((len(active), 0))
+            going = []
+            for k, i in enumerate(active):
+                stop, val_prev[i] = _arhmm_epoch_rows(rows[i], epoch, stats[i][4], val_lls[k], splits, n_datasets, D,
+                                                      val_prev[i], tol)
+                last[i] = epoch
+                if not stop:
+                    going.append(i)
+            active = going
+        if test is not None:
+            test_lls = ARHMMGroup([models[i] for i in members]).trial_logliks(test, s_off)
+            for k, i in enumerate(members):
+                _arhmm_test_rows(rows[i], last[i], test_lls[k], splits, D)
+        for i in members:
+            _arhmm_relabel(models[i], train, t_off)
+            out[i] = (models[i], rows[i])
+    return out
+
+
+def fit_arhmm_grid(data_generator, model, grid, n_iters=150, tol=0, sess_idx=None, data_key='ae_latents'):
+    """``fit_arhmm`` for every configuration of ``grid`` (``arhmm_grid``; dicts of ``n_states``, ``n_lags``,
+    ``transitions``, ``kappa``, ``rng_seed_model``) at once: the trials are walked and encoded ONCE, one device table
+    per split, and the configurations advance in groups (``arhmm_grid_groups``: one ``n_lags``, 512 states,
+    ``ARHMM_GRID_TABLE_BYTES``), every model of a group one EM iteration in one set of launches
+    (``models.arhmm.ARHMMGroup``).  -> a list, in grid order, of the ``(arhmm, rows)`` ``fit_arhmm`` returns for the
+    configuration: the same epochs, rows, stop rule per model (a stopped model is frozen and its rows end at its
+    epoch), test rows and usage permutation.  A configuration that is not served is refused before the first epoch
+    with ``fit_arhmm``'s error.  Under ``torch.distributed`` rank 0 fits and the other ranks return None."""
+    who = 'fit_arhmm_grid'
+    grid = [_arhmm_grid_config(cfg) for cfg in grid]
+    for c in grid:                                          # (types and limits that need no table)
+        _new_arhmm(1, c['n_states'], 0, c['transitions'], c['kappa'], c['noise_type'])
+    if data_key == 'ae_latents':
+        _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return None
+    wanted = _wanted_sessions(who, data_generator, sess_idx)
+    parts = _arhmm_trials(who, data_generator, model, data_key, ('train', 'val', 'test'), wanted)
+    idxs = [ds.batch_idxs for ds in data_generator.datasets]
+    splits = {dt: _arhmm_split(parts, _corr_trial_order(idxs, [dt], wanted)) for dt in ('train', 'val', 'test')}
+    return _fit_arhmm_grid_splits(splits, sorted(wanted), grid, n_iters, tol)
+
+
+def fit_arhmm_grid_tables(train, val=None, test=None, grid=(), n_iters=150, tol=0):
+    """``fit_arhmm_grid`` for lists of (T, D) arrays or device tensors, with no generator and no model
+    (``fit_arhmm_tables`` for a grid)."""
+    grid = [_arhmm_grid_config(cfg) for cfg in grid]
+    train = list(train) if train is not None else []
+    if train:
+        D = int(train[0].shape[1])
+        for c in grid:                                      # refused before a table is built
+            _new_arhmm(D, c['n_states'], c['n_lags'], c['transitions'], c['kappa'], c['noise_type'])
+    return _fit_arhmm_grid_splits(_arhmm_table_splits(train, val, test), [0], grid, n_iters, tol)
 
 
 def fit_arhmm(data_generator, model, n_states, n_lags=1, transitions='stationary', kappa=0, n_iters=150, tol=0,
@@ -2177,6 +2348,11 @@ def fit_arhmm_tables(train, val=None, test=None, n_states=2, n_lags=1, transitio
                      tol=0, rng_seed_model=0, noise_type='gaussian'):
     """``fit_arhmm`` for lists of (T, D) arrays or device tensors, with no generator and no model: one session
     (``dataset = 0``), the trials numbered by their position in their list."""
+    return _fit_arhmm_splits(_arhmm_table_splits(train, val, test), [0], n_states, n_lags, transitions, kappa,
+                             n_iters, tol, rng_seed_model, noise_type)
+
+
+def _arhmm_table_splits(train, val, test):
     from behavenet_amd.models.arhmm import ARHMM
     splits = {}
     for name, datas in (('train', train), ('val', val), ('test', test)):
@@ -2187,8 +2363,7 @@ def fit_arhmm_tables(train, val=None, test=None, n_states=2, n_lags=1, transitio
         else:
             table, offsets = None, np.zeros((1,), dtype=np.int64)
         splits[name] = (table, offsets, np.zeros(len(datas), dtype=np.int64), np.arange(len(datas), dtype=np.int64))
-    return _fit_arhmm_splits(splits, [0], n_states, n_lags, transitions, kappa, n_iters, tol, rng_seed_model,
-                             noise_type)
+    return splits
 
 
 def export_states(hparams, data_generator, arhmm, model=None, filename=None):

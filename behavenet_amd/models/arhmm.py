@@ -423,3 +423,117 @@ class ARHMM(object):
         S = len(offsets) - 1
         return ([z[offsets[i]:offsets[i + 1]].copy() for i in range(S)],
                 [x[offsets[i]:offsets[i + 1]].copy() for i in range(S)])
+
+
+class ARHMMGroup(object):
+    """``M`` models with the same ``D`` and ``lags`` that advance one EM iteration in ONE set of launches on one table
+    ("ARHMM: a grid of models"): their states lie side by side as ``KT = sum K_m`` columns of the
+    folded parameters, of ``ll`` and of ``gamma`` (``bn_arhmm_grid_loglik``, ``bn_hmm_grid_forward_backward``,
+    ``bn_arhmm_grid_moments``).  The group holds references to its models and numpy arrays only; every model keeps its
+    own host M-step."""
+
+    def __init__(self, models):
+        from behavenet_amd import _hip
+        models = list(models)
+        if not models:
+            raise ValueError('ARHMMGroup: no models')
+        for m in models:
+            if not isinstance(m, ARHMM):
+                raise ValueError('ARHMMGroup: expected ARHMM models, got %s' % type(m).__name__)
+            if (m.D, m.lags) != (models[0].D, models[0].lags):
+                raise ValueError('ARHMMGroup: the models of a group share D and lags, got (%d, %d) and (%d, %d)'
+                                 % (models[0].D, models[0].lags, m.D, m.lags))
+        self.models = models
+        self.D, self.lags = models[0].D, models[0].lags
+        self.Ks = np.asarray([m.K for m in models], dtype=np.int64)
+        self.koff, self.xoff = _hip.check_arhmm_grid_states('ARHMMGroup', self.Ks)
+        _hip.check_arhmm_grid_dims('ARHMMGroup', self.D, self.lags, int(self.koff[-1]))
+
+    @property
+    def M(self):
+        return len(self.models)
+
+    @property
+    def KT(self):
+        return int(self.koff[-1])
+
+    @property
+    def P(self):
+        return 1 + (self.lags + 1) * self.D
+
+    def fold(self):
+        """``(G, cst)`` of all states side by side: (KT, D, P) and (KT,)."""
+        folded = [m.fold() for m in self.models]
+        return np.concatenate([f[0] for f in folded], axis=0), np.concatenate([f[1] for f in folded])
+
+    def set_shift(self, table):
+        """The shift is a property of the table: computed once, as ``ARHMM.set_shift`` computes it, for every model."""
+        shift = self.models[0].set_shift(table)
+        for m in self.models[1:]:
+            m.shift = shift.copy()
+        return shift
+
+    def _shift(self):
+        shift = self.models[0].shift
+        for m in self.models[1:]:
+            if not np.array_equal(m.shift, shift):
+                raise ValueError('ARHMMGroup: the models of a group share the shift of their table (set_shift)')
+        return shift
+
+    def _transitions(self):
+        return (np.concatenate([m.log_Ps.reshape(-1) for m in self.models]),
+                np.concatenate([m.log_pi0 for m in self.models]))
+
+    def _loglik_table(self, table, offsets_d):
+        from behavenet_amd import _hip
+        G, cst = self.fold()
+        return _hip.arhmm_grid_loglik(table, offsets_d, G, cst, self.lags, shift=self._shift())
+
+    def trial_logliks(self, table, offsets):
+        """The log-likelihood of every trial under every model, a float64 host array (M, S) (forward sweep only)."""
+        from behavenet_amd import _hip
+        self.models[0]._check_table(table)
+        offsets_d = self.models[0]._offsets_d(table, offsets)
+        ll = self._loglik_table(table, offsets_d)
+        log_Ps, log_pi0 = self._transitions()
+        return _hip.hmm_grid_forward_backward(ll, offsets_d, self.Ks, log_Ps, log_pi0,
+                                              want_posteriors=False)[2].cpu().numpy()
+
+    def e_step(self, table, offsets):
+        """Per model the ``(moments, gamma_init, xi_sum, gamma0_sum, logliks)`` of ``ARHMM.e_step``, host arrays, from
+        three launches and ONE transfer for the whole group."""
+        import torch
+        from behavenet_amd import _hip
+        self.models[0]._check_table(table)
+        offsets_d = self.models[0]._offsets_d(table, offsets)
+        M, KT, P, XT = self.M, self.KT, self.P, int(self.xoff[-1])
+        ll = self._loglik_table(table, offsets_d)
+        log_Ps, log_pi0 = self._transitions()
+        gamma, xi, lls = _hip.hmm_grid_forward_backward(ll, offsets_d, self.Ks, log_Ps, log_pi0)
+        del ll
+        mom, ginit = _hip.arhmm_grid_moments(table, offsets_d, gamma, self.lags, shift=self._shift())
+        first = offsets_d[:-1][offsets_d[1:] > offsets_d[:-1]]
+        g0 = gamma.index_select(0, first).sum(dim=0) if first.numel() else gamma.new_zeros((KT,))
+        S = int(lls.shape[1])
+        packed = torch.cat([mom.reshape(-1), ginit, xi.sum(dim=0), g0, lls.reshape(-1)]).cpu().numpy()
+        o = np.cumsum([0, KT * P * P, KT, XT, KT])
+        mom, ginit, xi_sum, g0 = (packed[o[0]:o[1]].reshape(KT, P, P), packed[o[1]:o[2]], packed[o[2]:o[3]],
+                                  packed[o[3]:o[4]])
+        lls = packed[o[4]:].reshape(M, S)
+        out = []
+        for i, m in enumerate(self.models):
+            k0, k1, x0, x1 = self.koff[i], self.koff[i + 1], self.xoff[i], self.xoff[i + 1]
+            out.append((mom[k0:k1], ginit[k0:k1], xi_sum[x0:x1].reshape(m.K, m.K), g0[k0:k1], lls[i]))
+        return out
+
+    def m_step(self, stats):
+        """Every model's own host M-step on its five-tuple of ``e_step``."""
+        for m, (mom, _, xi_sum, g0, _) in zip(self.models, stats):
+            m.m_step(mom, xi_sum, g0)
+
+    def em_step(self, table, offsets):
+        """One EM iteration of every model; returns the per-trial log-likelihoods (M, S) of the parameters BEFORE the
+        update."""
+        stats = self.e_step(table, offsets)
+        self.m_step(stats)
+        return np.stack([s[4] for s in stats]) if stats else np.zeros((0, 0))

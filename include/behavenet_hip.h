@@ -837,6 +837,40 @@ size_t bn_hmm_viterbi_ws_bytes(int n, int S, int K);
 int bn_hmm_viterbi(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
                    const double* logpi0, int* states, void* ws, size_t ws_bytes, bn_stream_t stream);
 
+/* The same three launches for a GRID of M models on one table: models with the same D and L, their states side by
+ * side as KT = sum K_m columns.  Model m owns the columns koff[m] .. koff[m + 1] of G (KT, D, P), cst (KT), ll (n, KT),
+ * gamma (n, KT), out (KT, P, P) and gamma0 (KT), the entries xoff[m] .. xoff[m + 1] (xoff: prefix sums of K_m^2) of
+ * logP -- its (K_m, K_m) matrix, row-major -- and of every row of xi (S, XT), and row m of loglik (M, S).
+ * Limits: 1 <= K_m <= 32, KT <= 512, M <= 512, D, L, n and S as above.
+ *
+ * bn_arhmm_grid_loglik and bn_arhmm_grid_moments are bn_arhmm_loglik and bn_arhmm_moments for KT states: the same
+ * kernels, the same arithmetic per state (full 16-state tiles, whole state groups, the table read once for all
+ * models), the same partition rule (row blocks of at least 512 rows, the KT partials of all blocks within 60 MiB: the
+ * blocks grow with KT).
+ *
+ * bn_hmm_grid_forward_backward: bn_hmm_forward_backward for every (trial, model).  koff, xoff: DEVICE int32 (M + 1);
+ * order: DEVICE int32 (M), every model once -- the n4 models with K_m <= 4 first, then the n8 with 4 < K_m <= 8, the
+ * n16 with 8 < K_m <= 16 and the n32 others (n4 + n8 + n16 + n32 = M).  One launch a class KP = 4, 8, 16, 32; a wave
+ * takes one trial and 64 / KP models that follow each other in `order`, a slot of KP lanes a model.  Nothing crosses
+ * a slot: a model's outputs have the same bits wherever it sits in `order` and whoever shares its wave, and a NaN or
+ * Inf in a model's ll, logP or logpi0 stays in that model's outputs.  An entry of order outside [0, M), a K_m outside
+ * its class and columns outside [0, KT) / [0, XT) make an empty slot (nothing read or written for it).  want = 0:
+ * loglik only, gamma and xi may be NULL.  ws: bn_hmm_grid_forward_backward_ws_bytes bytes (the offsets and two doubles a
+ * (model, row)).  BN_E_SHAPE / BN_E_BADARG as above; koff, xoff and order on 4-byte boundaries. */
+size_t bn_arhmm_grid_loglik_ws_bytes(int n, int S, int D, int L, int KT);
+int bn_arhmm_grid_loglik(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L, int KT,
+                         int n, const double* G, const double* cst, double* ll, void* ws, size_t ws_bytes,
+                         bn_stream_t stream);
+size_t bn_arhmm_grid_moments_ws_bytes(int n, int S, int D, int L, int KT);
+int bn_arhmm_grid_moments(const float* z, int ld, const double* c, const long long* offsets, int S, int D, int L,
+                          int KT, int n, const double* gamma, double* out, double* gamma0, void* ws, size_t ws_bytes,
+                          bn_stream_t stream);
+size_t bn_hmm_grid_forward_backward_ws_bytes(int n, int S, int M, int KT, int XT);
+int bn_hmm_grid_forward_backward(const double* ll, const long long* offsets, int S, int M, int KT, int XT, int n,
+                                 const int* koff, const int* xoff, const int* order, int n4, int n8, int n16, int n32,
+                                 const double* logP, const double* logpi0, int want, double* gamma, double* xi,
+                                 double* loglik, void* ws, size_t ws_bytes, bn_stream_t stream);
+
 /* The generative process of the same model, from noise the CALLER brings: no random number is drawn on the device, so
  * the call is a deterministic function of its operands (the same bits on every call).  Trials as above: offsets
  * int64 (S + 1) made safe, rows outside [e[0], e[S]) neither read nor written.  float64 but for init and the states.
