@@ -186,6 +186,9 @@ SIGNATURES = {
     'bn_hmm_grid_forward_backward_ws_bytes': (_c_size_t, [_c_int] * 5),
     'bn_hmm_grid_forward_backward': (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 5 + [_c_void_p] * 3 + [_c_int] * 4
                                      + [_c_void_p, _c_void_p, _c_int] + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
+    'bn_hmm_grid_viterbi_ws_bytes': (_c_size_t, [_c_int] * 5),
+    'bn_hmm_grid_viterbi': (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 5 + [_c_void_p] * 3 + [_c_int] * 4
+                            + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
     'bn_arhmm_sample_ws_bytes': (_c_size_t, [_c_int] * 5),
     'bn_arhmm_sample': (_c_int, [_c_void_p] * 5 + [_c_int] * 5 + [_c_void_p] * 4 + [_c_int] + [_c_void_p] * 3
                         + [_c_size_t, _c_void_p]),
@@ -1907,6 +1910,52 @@ def hmm_grid_forward_backward(ll, offsets, Ks, log_Ps, log_pi0, want_posteriors=
     return (gamma, xi, loglik) if want else (None, None, loglik)
 
 
+def hmm_grid_viterbi_ws_bytes(n, S, Ks):
+    """``bn_hmm_grid_viterbi_ws_bytes`` restated: the int32 offsets padded to 16 bytes and one uint8 back-pointer a
+    (row, state column), padded to 16 bytes (held against the query in tests/test_arhmm_grid_states_cpu.py)."""
+    pad16 = lambda b: (int(b) + 15) & ~15
+    return pad16((int(S) + 1) * 4) + pad16(int(n) * int(sum(int(k) for k in Ks)))
+
+
+def hmm_grid_viterbi(ll, offsets, Ks, log_Ps, log_pi0, out=None):
+    """The most likely state path of every (trial, model) of a grid over the float64 DEVICE table ``ll`` (n, KT), the
+    models' states side by side (``bn_hmm_grid_viterbi``): an int32 device tensor (M, n), row m the path of model m
+    with the integers ``hmm_viterbi`` gives on that model's own columns; a tie goes to the lowest state.  ``Ks``,
+    ``log_Ps`` (XT,) and ``log_pi0`` (KT,) as ``hmm_grid_forward_backward`` takes them.  Rows outside the trials are
+    not written: they read 0 in a fresh output and are left as they are in ``out`` (int32 (M, n) on the device)."""
+    who = 'hmm_grid_viterbi'
+    koff, xoff = check_arhmm_grid_states(who, Ks)
+    M, KT, XT = len(koff) - 1, int(koff[-1]), int(xoff[-1])
+    if not torch.is_tensor(ll) or ll.dim() != 2 or ll.dtype != torch.float64 or int(ll.shape[1]) != KT:
+        raise ValueError('%s: expected ll float64 (n, %d), got %s'
+                         % (who, KT, (ll.dtype, tuple(ll.shape)) if torch.is_tensor(ll) else type(ll).__name__))
+    if not ll.is_cuda:
+        raise ValueError('%s: expected ll on the GPU, got device %s (the HIP path has no CPU fallback)'
+                         % (who, ll.device))
+    if not ll.is_contiguous():
+        raise ValueError('%s: ll must be contiguous, got strides %s' % (who, tuple(ll.stride())))
+    n, dev = int(ll.shape[0]), ll.device
+    log_Ps = _f64_operand(who, 'log_Ps', log_Ps, (XT,), dev)
+    log_pi0 = _f64_operand(who, 'log_pi0', log_pi0, (KT,), dev)
+    offsets = _trial_offsets(who, offsets, dev)
+    S = int(offsets.numel()) - 1
+    if out is None:
+        out = torch.zeros((M, n), dtype=torch.int32, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.int32 or tuple(out.shape) != (M, n) or out.device != dev \
+            or not out.is_contiguous():
+        raise ValueError('%s: expected out int32 (%d, %d) on %s' % (who, M, n, dev))
+    order, counts = _hmm_grid_order(Ks)
+    tables = torch.from_numpy(np.concatenate([koff, xoff, order])).to(dev)          # one upload
+    lib = load()
+    nbytes = lib.bn_hmm_grid_viterbi_ws_bytes(n, S, M, KT, XT)
+    if S:
+        _check(lib.bn_hmm_grid_viterbi(ll.data_ptr(), offsets.data_ptr(), S, M, KT, XT, n, tables.data_ptr(),
+                                       tables[M + 1:].data_ptr(), tables[2 * M + 2:].data_ptr(), counts[0], counts[1],
+                                       counts[2], counts[3], log_Ps.data_ptr(), log_pi0.data_ptr(), out.data_ptr(),
+                                       _arena(dev, nbytes, 'arhmm'), nbytes, _stream()), 'bn_hmm_grid_viterbi')
+    return out
+
+
 # csrc/state_runs.hip's partition, restated for the tests that have to name tile boundaries and the row count at which
 # the scan over the tiles' counts takes a second step: SR_TILE rows a workgroup (held against bn_state_runs_ws_bytes
 # in tests/test_state_runs_cpu.py), SR_SCAN counts a step of the scan
@@ -1955,6 +2004,73 @@ def state_runs(states, offsets, K):
     if bad:
         raise ValueError('%s: %d rows in trials hold a state outside [0, %d)' % (who, bad, K))
     return (runs if R == n else runs[:R].clone()), frames, trans
+
+
+# state_runs_grid: bytes of run buffers (16 a (model, row)) that are alive at once at most
+STATE_RUNS_GRID_BYTES = 1 << 30
+
+
+def state_runs_grid(states, offsets, Ks):
+    """``state_runs`` for every row of the int32 DEVICE table ``states`` (M, n) -- ``hmm_grid_viterbi``'s output --
+    with the state counts ``Ks``: a list of M triples ``(runs, frames, trans)`` as ``state_runs`` defines them, HOST
+    arrays int32 (R_m, 4), int64 (K_m) and int64 (K_m, K_m).  The ``bn_state_runs`` launches of the models follow
+    each other on the stream with no synchronisation between them; the ``K + K^2 + 2`` int64 statistics of all models
+    come back in ONE transfer and the runs, trimmed on the device to the counts that transfer told, in one more.  The
+    models are taken in chunks whose run buffers (16 bytes a (model, row)) stay within 1 GiB -- one chunk, so two
+    transfers, up to ``2^26 / n`` models; every further chunk costs two more.  A model with a state outside
+    [0, K_m) on a row in a trial is ``state_runs``' ValueError with the model named."""
+    who = 'state_runs_grid'
+    if not torch.is_tensor(states) or states.dim() != 2 or states.dtype != torch.int32:
+        raise ValueError('%s: expected states int32 (M, n), got %s'
+                         % (who, (states.dtype, tuple(states.shape)) if torch.is_tensor(states)
+                            else type(states).__name__))
+    if not states.is_cuda:
+        raise ValueError('%s: expected states on the GPU, got device %s (the HIP path has no CPU fallback)'
+                         % (who, states.device))
+    if not states.is_contiguous():
+        raise ValueError('%s: states must be contiguous, got strides %s' % (who, tuple(states.stride())))
+    Ks = [int(k) for k in Ks]
+    M, n = (int(v) for v in states.shape)
+    if len(Ks) != M or not M:
+        raise ValueError('%s: %d state counts for %d models' % (who, len(Ks), M))
+    for k in Ks:
+        if not 1 <= k <= ARHMM_MAX_K:
+            raise ValueError('%s: %d states (1 to %d are served)' % (who, k, ARHMM_MAX_K))
+    dev = states.device
+    offsets = _trial_offsets(who, offsets, dev)
+    S = int(offsets.numel()) - 1
+    if not S or not n:
+        return [(np.zeros((0, 4), dtype=np.int32), np.zeros((k,), dtype=np.int64), np.zeros((k, k), dtype=np.int64))
+                for k in Ks]
+    lib = load()
+    per = max(1, STATE_RUNS_GRID_BYTES // (16 * n))
+    out = []
+    for m0 in range(0, M, per):
+        ks = Ks[m0:m0 + per]
+        so = np.concatenate(([0], np.cumsum([k + k * k + 2 for k in ks])))
+        stats = torch.zeros((int(so[-1]),), dtype=torch.int64, device=dev)
+        runs = torch.empty((len(ks), n, 4), dtype=torch.int32, device=dev)
+        for i, k in enumerate(ks):
+            nbytes = lib.bn_state_runs_ws_bytes(n, S, k)
+            at = stats.data_ptr() + 8 * int(so[i])
+            _check(lib.bn_state_runs(states[m0 + i].data_ptr(), offsets.data_ptr(), S, k, n, runs[i].data_ptr(), n,
+                                     at, at + 8 * k, at + 8 * (k + k * k), at + 8 * (k + k * k + 1),
+                                     _arena(dev, nbytes, 'state_runs'), nbytes, _stream()), 'bn_state_runs')
+        host = stats.cpu().numpy()                                                  # the chunk's first transfer
+        Rs = []
+        for i, k in enumerate(ks):
+            R, bad = (int(v) for v in host[so[i] + k + k * k:so[i + 1]])
+            if bad:
+                raise ValueError('%s: model %d: %d rows in trials hold a state outside [0, %d)'
+                                 % (who, m0 + i, bad, k))
+            Rs.append(R)
+        trimmed = torch.cat([runs[i, :R] for i, R in enumerate(Rs)]).cpu().numpy()   # ... and its second
+        ro = np.concatenate(([0], np.cumsum(Rs)))
+        for i, k in enumerate(ks):
+            st = host[so[i]:so[i + 1]]
+            out.append((trimmed[ro[i]:ro[i + 1]].copy(), st[:k].copy(), st[k:k + k * k].reshape(k, k).copy()))
+        del runs
+    return out
 
 
 def arhmm_sample(W, C, cdf0, cdf, offsets, eps, u=None, states=None, init=None, x=None, states_out=None):

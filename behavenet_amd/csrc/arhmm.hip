@@ -75,6 +75,15 @@
 //                model.  A padding state (j >= K_m) and an empty slot carry probability zero and write nothing.
 //                One launch a class, the grid (trials, waves of the class); (s_t, max_t) a (model, row) in the
 //                workspace.
+// k_hmm_gviterbi max-sum for the grid (bn_hmm_grid_viterbi): k_hmm_gfb's packing -- the same order, counts, koff, xoff
+//                and empty-slot rules, one launch a class -- and k_hmm_viterbi's arithmetic term for term inside a
+//                slot: delta = best + ll, predecessors in ascending order with strict >, the last row's argmax the
+//                same, the slot's KP deltas read from its own KP doubles in LDS (double buffered, one barrier a step).
+//                A model's path has k_hmm_viterbi's integers wherever it sits.  uint8 back-pointers at
+//                bp[row * KT + koff[m] + j] in the workspace; every lane reads back only bytes it wrote itself.  The
+//                walk back takes all slots at once: 64 rows of the wave's 64 back-pointer bytes are staged in LDS
+//                (4 KiB), the first lane of every slot walks its own chain and leaves the chunk's states in LDS, and
+//                the wave writes them slot after slot as states[m * n + row], neighbouring lanes on neighbouring rows.
 // No global atomics; every output element is written exactly once by each kernel that owns it.
 #include <limits.h>
 #include <math.h>
@@ -635,6 +644,103 @@ __global__ __launch_bounds__(BN_WAVE) void k_hmm_viterbi(const double* __restric
     }
 }
 
+// The grid form: k_hmm_gfb's slots (same order / koff / xoff rules, an empty slot reads and writes nothing) around
+// k_hmm_viterbi's recursion.  states is (M, n); bp holds one byte a (row, state column).
+template <int KP>
+__global__ __launch_bounds__(BN_WAVE) void k_hmm_gviterbi(const double* __restrict__ ll, const int* __restrict__ e,
+                                                          int n, int M, int KT, int XT, const int* __restrict__ koff,
+                                                          const int* __restrict__ xoff, const int* __restrict__ order,
+                                                          int count, const double* __restrict__ logP,
+                                                          const double* __restrict__ logpi0, int* __restrict__ states,
+                                                          unsigned char* __restrict__ bp) {
+    constexpr int SL = BN_WAVE / KP;
+    __shared__ __attribute__((aligned(16))) double buf[2][BN_WAVE];            // [parity][slot * KP + state]
+    __shared__ unsigned char chunk[AR_BT_ROWS * BN_WAVE];                      // [row of the chunk][lane]
+    __shared__ unsigned char path[SL * AR_BT_ROWS];                            // [slot][row of the chunk]
+    __shared__ int model[SL];                                                  // the slot's model, -1 for none
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int slot = lane / KP, base = slot * KP, j = lane - base;
+    const int beg = e[s], T = e[s + 1] - beg;
+    if (T <= 0) return;
+    const int idx = blockIdx.y * SL + slot;
+    int m = idx < count ? order[idx] : -1;
+    int K = 0, k0 = 0, x0 = 0;
+    if (m >= 0 && m < M) {
+        k0 = koff[m];
+        K = koff[m + 1] - k0;
+        x0 = xoff[m];
+        if (K < 1 || K > KP || k0 < 0 || k0 > KT - K || x0 < 0 || x0 > XT - K * K) K = 0;
+    }
+    if (!K) m = -1;                                        // (an empty slot: no lane of it is active)
+    const bool active = j < K, head = active && j == 0;
+    if (j == 0) model[slot] = m;
+    const double ninf = -INFINITY;
+    const double* l = ll + (size_t)beg * KT + k0 + j;
+    unsigned char* back = bp + (size_t)beg * KT + k0 + j;
+    const double* lp = logP + x0;
+
+    double Pc[KP];
+#pragma unroll
+    for (int i = 0; i < KP; ++i) Pc[i] = active && i < K ? lp[i * K + j] : ninf;
+    double delta = active ? logpi0[k0 + j] + l[0] : ninf;
+    double lv = active && T > 1 ? l[(size_t)KT] : ninf;
+    for (int t = 1; t < T; ++t) {
+        const double lnext = active && t + 1 < T ? l[(size_t)(t + 1) * KT] : ninf;
+        const int par = t & 1;
+        buf[par][lane] = delta;
+        __syncthreads();
+        double best = buf[par][base] + Pc[0];
+        int arg = 0;
+#pragma unroll
+        for (int i = 1; i < KP; ++i) {
+            const double v = buf[par][base + i] + Pc[i];
+            if (v > best) {
+                best = v;
+                arg = i;
+            }
+        }
+        if (active) back[(size_t)t * KT] = (unsigned char)arg;
+        delta = best + lv;
+        lv = lnext;
+    }
+    const int par = T & 1;
+    buf[par][lane] = delta;
+    __syncthreads();                                       // (and model[] is visible to the wave)
+    int cur = 0;
+    if (head) {
+        double best = buf[par][base];
+        for (int i = 1; i < K; ++i)
+            if (buf[par][base + i] > best) {
+                best = buf[par][base + i];
+                cur = i;
+            }
+    }
+    for (int hi = T; hi > 0; hi -= AR_BT_ROWS) {
+        const int lo = hi > AR_BT_ROWS ? hi - AR_BT_ROWS : 0;
+        const int cnt = hi - lo;
+        __syncthreads();                                   // (the chunk before this one has been walked and written)
+        // every lane stages the bytes it wrote itself (row 0 has no back-pointers)
+#pragma unroll 8
+        for (int r = 0; r < cnt; ++r)
+            chunk[r * BN_WAVE + lane] = active && lo + r > 0 ? back[(size_t)(lo + r) * KT] : 0;
+        __syncthreads();
+        if (head) {
+            for (int t = hi - 1; t >= lo; --t) {
+                path[slot * AR_BT_ROWS + (t - lo)] = (unsigned char)cur;
+                if (t > 0) cur = chunk[(t - lo) * BN_WAVE + base + cur];
+            }
+        }
+        __syncthreads();
+        if (lane < cnt) {
+#pragma unroll
+            for (int q = 0; q < SL; ++q) {
+                const int mq = model[q];
+                if (mq >= 0) states[(size_t)mq * n + beg + lo + lane] = path[q * AR_BT_ROWS + lane];
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // states a workgroup of k_ar_moments takes with ONE staging of its rows (the accumulators of a state are
 // 2 TB (TB + 1) registers a lane; at TB = 3 four states measured slower than two: one wave a SIMD)
@@ -994,6 +1100,11 @@ size_t bn_hmm_viterbi_ws_bytes_impl(int n, int S, int K) {
     return ar_offsets_bytes(S) + ar_pad16((size_t)n * K);
 }
 
+size_t bn_hmm_grid_viterbi_ws_bytes_impl(int n, int S, int M, int KT, int XT) {
+    if (!bn_hmm_grid_ok(n, S, M, KT, XT)) return 0;
+    return ar_offsets_bytes(S) + ar_pad16((size_t)n * KT);
+}
+
 static int ar_launch_kind(const long long* offsets, int S, int L, int n, void* ws, hipStream_t st) {
     int* e = reinterpret_cast<int*>(ws);
     unsigned char* kind = reinterpret_cast<unsigned char*>(ws) + ar_offsets_bytes(S);
@@ -1152,6 +1263,42 @@ int bn_launch_hmm_viterbi(const double* ll, const long long* offsets, int S, int
     else if (K <= 16) hipLaunchKernelGGL(k_hmm_viterbi<16>, grid, block, 0, st, ll, ce, K, logP, logpi0, states, bp);
     else hipLaunchKernelGGL(k_hmm_viterbi<32>, grid, block, 0, st, ll, ce, K, logP, logpi0, states, bp);
     BN_LAUNCH_CHECK();
+    return 0;
+}
+
+// order and counts as bn_launch_hmm_grid_forward_backward takes them; one launch a class
+int bn_launch_hmm_grid_viterbi(const double* ll, const long long* offsets, int S, int M, int KT, int XT, int n,
+                               const int* koff, const int* xoff, const int* order, const int* counts,
+                               const double* logP, const double* logpi0, int* states, void* ws, hipStream_t st) {
+    if (!bn_hmm_grid_ok(n, S, M, KT, XT)) return BN_E_SHAPE;
+    long sum = 0;
+    for (int c = 0; c < 4; ++c) {
+        if (counts[c] < 0 || counts[c] > M) return BN_E_SHAPE;
+        sum += counts[c];
+    }
+    if (sum != M) return BN_E_SHAPE;
+    if (S == 0) return 0;
+    int* e = reinterpret_cast<int*>(ws);
+    unsigned char* bp = reinterpret_cast<unsigned char*>(ws) + ar_offsets_bytes(S);
+    const int rc = bn_launch_segment_offsets(offsets, S + 1, n, e, st);
+    if (rc) return rc;
+    const int* ce = e;
+    const dim3 block(BN_WAVE);
+    int first = 0;
+    for (int c = 0; c < 4; ++c) {
+        const int cnt = counts[c], KP = 4 << c, SL = BN_WAVE / KP;
+        if (!cnt) continue;
+        const dim3 grid((unsigned)S, (unsigned)((cnt + SL - 1) / SL));
+        const int* ord = order + first;
+        switch (KP) {
+            case 4: hipLaunchKernelGGL(k_hmm_gviterbi<4>, grid, block, 0, st, ll, ce, n, M, KT, XT, koff, xoff, ord, cnt, logP, logpi0, states, bp); break;
+            case 8: hipLaunchKernelGGL(k_hmm_gviterbi<8>, grid, block, 0, st, ll, ce, n, M, KT, XT, koff, xoff, ord, cnt, logP, logpi0, states, bp); break;
+            case 16: hipLaunchKernelGGL(k_hmm_gviterbi<16>, grid, block, 0, st, ll, ce, n, M, KT, XT, koff, xoff, ord, cnt, logP, logpi0, states, bp); break;
+            default: hipLaunchKernelGGL(k_hmm_gviterbi<32>, grid, block, 0, st, ll, ce, n, M, KT, XT, koff, xoff, ord, cnt, logP, logpi0, states, bp); break;
+        }
+        BN_LAUNCH_CHECK();
+        first += cnt;
+    }
     return 0;
 }
 

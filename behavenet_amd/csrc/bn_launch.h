@@ -176,6 +176,11 @@ int bn_launch_hmm_grid_forward_backward(const double* ll, const long long* offse
                                         const int* koff, const int* xoff, const int* order, const int* counts,
                                         const double* logP, const double* logpi0, int want, double* gamma, double* xi,
                                         double* loglik, void* ws, hipStream_t st);
+// ... and max-sum for every (trial, model) of the grid: states int32 (M, n)
+size_t bn_hmm_grid_viterbi_ws_bytes_impl(int n, int S, int M, int KT, int XT);
+int bn_launch_hmm_grid_viterbi(const double* ll, const long long* offsets, int S, int M, int KT, int XT, int n,
+                               const int* koff, const int* xoff, const int* order, const int* counts,
+                               const double* logP, const double* logpi0, int* states, void* ws, hipStream_t st);
 // ... and the model's generative process from the caller's noise: states from uniforms (or given), latents from normals
 size_t bn_arhmm_sample_ws_bytes_impl(int n, int S, int D, int L, int K);
 int bn_launch_arhmm_sample(const double* W, const double* C, const double* cdf0, const double* cdf,

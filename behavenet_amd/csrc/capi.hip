@@ -2222,6 +2222,27 @@ extern "C" int bn_hmm_grid_forward_backward(const double* ll, const long long* o
                                                want, gamma, xi, loglik, ws, (hipStream_t)stream);
 }
 
+extern "C" size_t bn_hmm_grid_viterbi_ws_bytes(int n, int S, int M, int KT, int XT) {
+    return bn_hmm_grid_viterbi_ws_bytes_impl(n, S, M, KT, XT);
+}
+
+extern "C" int bn_hmm_grid_viterbi(const double* ll, const long long* offsets, int S, int M, int KT, int XT, int n,
+                                   const int* koff, const int* xoff, const int* order, int n4, int n8, int n16,
+                                   int n32, const double* logP, const double* logpi0, int* states, void* ws,
+                                   size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_hmm_grid_ok(n, S, M, KT, XT)) return BN_E_SHAPE;
+    if (n4 < 0 || n8 < 0 || n16 < 0 || n32 < 0 || (long)n4 + n8 + n16 + n32 != M) return BN_E_SHAPE;
+    if (!ll || !offsets || !koff || !xoff || !order || !logP || !logpi0 || !states || !ws) return BN_E_BADARG;
+    if (((uintptr_t)ll & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)koff & 3) || ((uintptr_t)xoff & 3) ||
+        ((uintptr_t)order & 3) || ((uintptr_t)logP & 7) || ((uintptr_t)logpi0 & 7) || ((uintptr_t)states & 3) ||
+        !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_hmm_grid_viterbi_ws_bytes_impl(n, S, M, KT, XT)) return BN_E_SHAPE;
+    const int counts[4] = {n4, n8, n16, n32};
+    return bn_launch_hmm_grid_viterbi(ll, offsets, S, M, KT, XT, n, koff, xoff, order, counts, logP, logpi0, states,
+                                      ws, (hipStream_t)stream);
+}
+
 extern "C" size_t bn_arhmm_sample_ws_bytes(int n, int S, int D, int L, int K) {
     return bn_arhmm_sample_ws_bytes_impl(n, S, D, L, K);
 }

@@ -41,7 +41,9 @@ __all__ = ['export_latents', 'encode_trial', 'encode_trial_device', 'get_reconst
            'latent_ranges_device', 'summarise_label_sums', 'label_r2', 'export_label_r2', 'summarise_gram',
            'latent_correlations', 'export_latent_correlations', 'session_classifier', 'export_session_classifier',
            'classify_table', 'score_table', 'fit_arhmm', 'fit_arhmm_tables', 'export_states', 'export_arhmm',
-           'arhmm_grid', 'arhmm_grid_groups', 'fit_arhmm_grid', 'fit_arhmm_grid_tables']
+           'arhmm_grid', 'arhmm_grid_groups', 'fit_arhmm_grid', 'fit_arhmm_grid_tables',
+           'arhmm_grid_runs', 'arhmm_grid_states', 'arhmm_grid_selection', 'export_states_grid',
+           'check_export_arhmm_grid', 'export_arhmm_grid']
 
 
 def encode_trial(model, y, sess=None, labels_2d=None, chunk_size=200):
@@ -2275,10 +2277,20 @@ def _fit_arhmm_grid_splits(splits, n_datasets, grid, n_iters, tol):
             test_lls = ARHMMGroup([models[i] for i in members]).trial_logliks(test, s_off)
             for k, i in enumerate(members):
                 _arhmm_test_rows(rows[i], last[i], test_lls[k], splits, D)
+        # every member, stopped early or not
+        _arhmm_grid_relabel([models[i] for i in members], train, t_off)
         for i in members:
-            _arhmm_relabel(models[i], train, t_off)
             out[i] = (models[i], rows[i])
     return out
+
+
+def _arhmm_grid_relabel(models, train, t_off):
+    """``_arhmm_relabel`` for the models of one group from ONE decoding of the group: every row of the train table
+    lies in a trial, so ``frames`` is ``_arhmm_relabel``'s bincount, and the paths are its paths integer for integer
+    (``bn_hmm_grid_viterbi``)."""
+    from behavenet_amd.models.arhmm import ARHMMGroup
+    for m, (_, frames, _) in zip(models, ARHMMGroup(models).table_runs(train, t_off)):
+        m.permute(np.argsort(frames)[::-1])
 
 
 def fit_arhmm_grid(data_generator, model, grid, n_iters=150, tol=0, sess_idx=None, data_key='ae_latents'):
@@ -2427,6 +2439,241 @@ def export_arhmm(data_generator, model, **kwargs):
     with open(path, 'wb') as f:
         pickle.dump(arhmm, f)
     return arhmm, rows, path, export_states(hparams, data_generator, arhmm, model=model)
+
+
+# ------------------------------------------------------------------------------------------ states of a grid of ARHMMs
+ARHMM_GRID_DIR = 'arhmm_grid'
+ARHMM_GRID_SELECTION_FILE = 'selection.pkl'
+
+
+def _grid_models(who, fits):
+    """The models of ``fits``: the ``(arhmm, rows)`` pairs ``fit_arhmm_grid`` returns, or bare models."""
+    from behavenet_amd.models.arhmm import ARHMM
+    models = [f[0] if isinstance(f, (tuple, list)) else f for f in fits]
+    for m in models:
+        if not isinstance(m, ARHMM):
+            raise ValueError('%s: expected fitted ARHMMs or (arhmm, rows) pairs, got %s' % (who, type(m).__name__))
+    return models
+
+
+def _grid_groups_of(models, n_rows):
+    """``(positions, ARHMMGroup)`` for the fitted ``models`` cut by ``arhmm_grid_groups``' limits."""
+    from behavenet_amd.models.arhmm import ARHMMGroup
+    grid = [{'n_states': m.K, 'n_lags': m.lags} for m in models]
+    return [(members, ARHMMGroup([models[i] for i in members])) for members in arhmm_grid_groups(grid, n_rows)]
+
+
+def arhmm_grid_runs(fits, tables, offsets=None):
+    """Per fitted model of ``fits`` (``fit_arhmm_grid``'s list, or bare models) the ``(runs, frames, trans)`` of
+    ``ARHMM.table_runs`` on one table, host arrays, in the order of ``fits``.  ``tables``: an fp32 device table (n, D)
+    with its ``offsets`` (int64 (S + 1)), or a list of (T, D) arrays or device tensors without.  The models are
+    decoded in groups with the limits of ``arhmm_grid_groups`` (one ``n_lags``, 512 states, 512 models): a group is one
+    log-likelihood launch, one Viterbi launch a class, the run searches and two transfers
+    (``ARHMMGroup.table_runs``)."""
+    from behavenet_amd.models.arhmm import ARHMM
+    who = 'arhmm_grid_runs'
+    models = _grid_models(who, fits)
+    if offsets is None:
+        tables, offsets = ARHMM.as_table(list(tables))
+    out = [None] * len(models)
+    for members, group in _grid_groups_of(models, int(tables.shape[0])):
+        for i, triple in zip(members, group.table_runs(tables, offsets)):
+            out[i] = triple
+    return out
+
+
+def arhmm_grid_states(data_generator, model, fits, dtype='test', sess_idx=None, data_key='ae_latents'):
+    """``arhmm_grid_runs`` on the trials of the split ``dtype`` of the sessions ``sess_idx``: the trials are walked
+    and encoded ONCE for all models (``fit_arhmm``'s walk and order), then every group is decoded on that one table.
+    -> the per-model triples, or ``None`` per model when the split has no frames.  Under ``torch.distributed`` rank
+    0 works and the other ranks return None."""
+    who = 'arhmm_grid_states'
+    dtypes = _splits(who, dtype)
+    models = _grid_models(who, fits)
+    if data_key == 'ae_latents':
+        _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return None
+    wanted = _wanted_sessions(who, data_generator, sess_idx)
+    parts = _arhmm_trials(who, data_generator, model, data_key, dtypes, wanted)
+    idxs = [ds.batch_idxs for ds in data_generator.datasets]
+    table, offsets, _, _ = _arhmm_split(parts, _corr_trial_order(idxs, dtypes, wanted))
+    if table is None:
+        return [None] * len(models)
+    return arhmm_grid_runs(models, table, offsets)
+
+
+def arhmm_grid_selection(grid, fits, stats, test_frames=None):
+    """The table a choice over a grid is made from: one dict per configuration of ``grid``, in grid order.  Pure host
+    code.  ``fits``: ``fit_arhmm_grid``'s ``(arhmm, rows)`` pairs; ``stats``: the per-model ``(runs, frames, trans)``
+    of ``arhmm_grid_runs`` / ``arhmm_grid_states``, None (or None for a model) where there are none.  A dict holds
+
+    * the configuration's own keys;
+    * ``epochs``: the number of the last epoch the model was scored at (0 is the initialised model);
+    * ``tr_loss`` and ``val_loss``: those of the last row with ``dataset == -1`` (pooled over the sessions);
+    * ``test_loss``: the mean of the rows' ``test_loss`` weighted by the trials' frames -- ``test_frames``, a dict
+      ``{(dataset, trial): frames}``; without it every test trial weighs the same, which is the same number where the
+      trials are equally long -- NaN rows (empty trials) left out, NaN without test rows;
+    * ``usage``: ``frames / sum(frames)``, a float64 array (K) (zeros when no frame was decoded);
+    * ``n_states_used``: the states with ``frames > 0``;
+    * ``n_states_99``: the fewest states whose frames, taken from the most used down, cover 99 % of all frames
+      (``cumulative >= 0.99 * total`` in integers: ``100 * cumulative >= 99 * total``), 0 without frames;
+    * ``n_runs``; ``median_duration`` and ``mean_duration`` over ``end - beg`` of ALL runs, those that touch the
+      ends of their trials included (NaN without runs).
+
+    The run fields are None for a model without ``stats``."""
+    who = 'arhmm_grid_selection'
+    grid = list(grid)
+    fits = list(fits)
+    stats = [None] * len(grid) if stats is None else list(stats)
+    if len(fits) != len(grid) or len(stats) != len(grid):
+        raise ValueError('%s: %d configurations, %d fits and %d stats' % (who, len(grid), len(fits), len(stats)))
+    table = []
+    for cfg, fit, st in zip(grid, fits, stats):
+        if not isinstance(cfg, dict):
+            raise ValueError('%s: a configuration is a dict, got %r' % (who, cfg))
+        rows = fit[1]
+        out = dict(cfg)
+        pooled = [r for r in rows if r.get('dataset') == -1 and 'val_loss' in r]
+        out['epochs'] = int(pooled[-1]['epoch']) if pooled else 0
+        out['tr_loss'] = float(pooled[-1]['tr_loss']) if pooled else float('nan')
+        out['val_loss'] = float(pooled[-1]['val_loss']) if pooled else float('nan')
+        num = den = 0.0
+        for r in rows:
+            if 'test_loss' not in r or np.isnan(r['test_loss']):
+                continue
+            w = 1.0 if test_frames is None else float(test_frames[(int(r['dataset']), int(r['trial']))])
+            num += w * float(r['test_loss'])
+            den += w
+        out['test_loss'] = num / den if den else float('nan')
+        if st is None:
+            for key in ('usage', 'n_states_used', 'n_states_99', 'n_runs', 'median_duration', 'mean_duration'):
+                out[key] = None
+        else:
+            runs, frames, _ = st
+            runs = np.asarray(runs).reshape(-1, 4).astype(np.int64)
+            frames = np.asarray(frames, dtype=np.int64).reshape(-1)
+            total = int(frames.sum())
+            out['usage'] = frames / float(total) if total else np.zeros(len(frames))
+            out['n_states_used'] = int(np.sum(frames > 0))
+            covered = np.cumsum(np.sort(frames)[::-1])
+            out['n_states_99'] = int(np.argmax(100 * covered >= 99 * total)) + 1 if total else 0
+            durations = runs[:, 2] - runs[:, 1]
+            out['n_runs'] = int(len(runs))
+            out['median_duration'] = float(np.median(durations)) if len(runs) else float('nan')
+            out['mean_duration'] = float(np.mean(durations)) if len(runs) else float('nan')
+        table.append(out)
+    return table
+
+
+def _grid_model_dir(hparams, i):
+    return os.path.join(hparams['expt_dir'], 'version_%i' % hparams['version'], ARHMM_GRID_DIR, 'model_%03i' % i)
+
+
+def export_states_grid(hparams, data_generator, fits, model=None, _parts=None):
+    """``export_states`` for every fitted model of ``fits`` at once: the trials of all sessions go into ONE device
+    table -- walked and encoded once -- and every group of models (``arhmm_grid_groups``' limits) is decoded by one
+    group Viterbi (``ARHMMGroup.table_states``).  Model ``i`` gets ``export_states``' files,
+    ``<lab>_<expt>_<animal>_<session>_states.pkl``, under ``version_<v>/arhmm_grid/model_%03i/``.  -> per model the
+    list of its file names (an empty list on the ranks other than 0)."""
+    who = 'export_states_grid'
+    models = _grid_models(who, fits)
+    data_key = 'labels' if str(hparams.get('model_class', 'arhmm')).find('label') > -1 else 'ae_latents'
+    if data_key == 'ae_latents' and model is not None:
+        _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return []
+    parts = _parts
+    if parts is None:
+        parts = _arhmm_trials(who, data_generator, model, data_key, ('train', 'val', 'test'),
+                              set(range(len(data_generator.datasets))))
+    keys = sorted(parts)
+    table, offsets, _, _ = _arhmm_split(parts, keys)
+    paths = [None] * len(models)
+    if table is not None:
+        for members, group in _grid_groups_of(models, int(table.shape[0])):
+            for i, path in zip(members, group.table_states(table, offsets)):
+                paths[i] = path
+    filenames = []
+    for i in range(len(models)):
+        states = [[np.array([]) for _ in range(ds.n_trials)] for ds in data_generator.datasets]
+        if paths[i] is not None:
+            for t, (sess, trial) in enumerate(keys):
+                states[sess][trial] = paths[i][offsets[t]:offsets[t + 1]].copy()
+        out_dir = _grid_model_dir(hparams, i)
+        os.makedirs(out_dir, exist_ok=True)
+        names = []
+        for sess, dataset in enumerate(data_generator.datasets):
+            out = os.path.join(out_dir, '%s_%s_%s_%s_states.pkl' % (dataset.lab, dataset.expt, dataset.animal,
+                                                                     dataset.session))
+            with open(out, 'wb') as f:
+                pickle.dump({'states': states[sess], 'trials': dataset.batch_idxs}, f)
+            names.append(out)
+        filenames.append(names)
+    print('saved the states of %i models under %s' % (len(models), os.path.dirname(_grid_model_dir(hparams, 0))))
+    return filenames
+
+
+def check_export_arhmm_grid(who, kwargs):
+    """``hparams['export_arhmm_grid']``: a dict of ``export_arhmm_grid``'s keyword arguments with ``grid``, a
+    non-empty list of configurations, among them.  Every configuration is built -- a type or a limit that is not
+    served is ``fit_arhmm``'s error -- and ``dtype`` is checked, before any epoch."""
+    import inspect
+    known = set(inspect.signature(export_arhmm_grid).parameters) - {'data_generator', 'model'}
+    if not isinstance(kwargs, dict) or 'grid' not in kwargs or not set(kwargs) <= known:
+        raise ValueError('%s: expected a dict with grid and any of %s, got %r' % (who, sorted(known), kwargs))
+    grid = kwargs['grid']
+    if not isinstance(grid, (list, tuple)) or not len(grid):
+        raise ValueError('%s: grid is a non-empty list of configurations (arhmm_grid), got %r' % (who, grid))
+    dtype = kwargs.get('dtype', 'val')
+    if not isinstance(dtype, str):
+        raise ValueError("%s: dtype must be 'train', 'val' or 'test', got %r" % (who, dtype))
+    _splits(who, dtype)
+    if kwargs.get('data_key', 'ae_latents') not in ('ae_latents', 'labels'):
+        raise ValueError("%s: data_key must be 'ae_latents' or 'labels', got %r" % (who, kwargs['data_key']))
+    for cfg in grid:
+        c = _arhmm_grid_config(cfg)
+        _new_arhmm(1, c['n_states'], c['n_lags'], c['transitions'], c['kappa'], c['noise_type'])
+
+
+def export_arhmm_grid(data_generator, model, grid, n_iters=150, tol=0, sess_idx=None, data_key='ae_latents',
+                      dtype='val'):
+    """``fit_arhmm_grid`` + ``arhmm_grid_selection`` on the split ``dtype`` + ``export_states_grid`` for a trained
+    model.  The train / val / test trials are walked and encoded ONCE for the fit, the selection table and -- when
+    ``sess_idx`` names every session -- the states.  Under ``version_<v>/arhmm_grid/``: ``selection.pkl``, a dict of
+    ``grid``, ``rows`` (per configuration the rows of its fit) and ``selection`` (the table), and per configuration
+    ``model_%03i/arhmm_best_val_model.pt`` with its states files.
+    -> ``(fits, selection, selection file, states files)``, None on the ranks other than 0."""
+    who = 'export_arhmm_grid'
+    check_export_arhmm_grid(who, {'grid': grid, 'dtype': dtype, 'data_key': data_key})
+    full = [_arhmm_grid_config(cfg) for cfg in grid]
+    if data_key == 'ae_latents':
+        _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return None
+    wanted = _wanted_sessions(who, data_generator, sess_idx)
+    parts = _arhmm_trials(who, data_generator, model, data_key, ('train', 'val', 'test'), wanted)
+    idxs = [ds.batch_idxs for ds in data_generator.datasets]
+    splits = {dt: _arhmm_split(parts, _corr_trial_order(idxs, [dt], wanted)) for dt in ('train', 'val', 'test')}
+    fits = _fit_arhmm_grid_splits(splits, sorted(wanted), full, n_iters, tol)
+    table, offsets, _, _ = splits[dtype]
+    stats = arhmm_grid_runs(fits, table, offsets) if table is not None else None
+    _, s_off, s_sess, s_trial = splits['test']
+    test_frames = {(int(s), int(t)): int(f) for s, t, f in zip(s_sess, s_trial, np.diff(s_off))}
+    selection = arhmm_grid_selection(list(grid), fits, stats, test_frames=test_frames)
+    labels = data_key == 'labels'
+    hparams = {'expt_dir': model.hparams['expt_dir'], 'version': model.version,
+               'model_class': 'arhmm' + ('-labels' if labels else '')}
+    for i, (arhmm, _) in enumerate(fits):
+        os.makedirs(_grid_model_dir(hparams, i), exist_ok=True)
+        with open(os.path.join(_grid_model_dir(hparams, i), ARHMM_MODEL_FILE), 'wb') as f:
+            pickle.dump(arhmm, f)
+    path = os.path.join(os.path.dirname(_grid_model_dir(hparams, 0)), ARHMM_GRID_SELECTION_FILE)
+    with open(path, 'wb') as f:
+        pickle.dump({'grid': list(grid), 'rows': [rows for _, rows in fits], 'selection': selection}, f)
+    every = wanted == set(range(len(data_generator.datasets)))
+    files = export_states_grid(hparams, data_generator, fits, model=model, _parts=parts if every else None)
+    return fits, selection, path, files
 
 
 # ------------------------------------------------------------------------------------------ ARHMM samples

@@ -599,6 +599,10 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
         # (a state count or a transition type that is not served: an error now, not after the last epoch)
         from behavenet_amd.fitting.eval import check_export_arhmm
         check_export_arhmm("fit: hparams['export_arhmm']", hparams['export_arhmm'])
+    if method == 'ae' and hparams.get('export_arhmm_grid'):
+        # (a bad dict, a configuration that is not served or a broken limit: an error now, as above)
+        from behavenet_amd.fitting.eval import check_export_arhmm_grid
+        check_export_arhmm_grid("fit: hparams['export_arhmm_grid']", hparams['export_arhmm_grid'])
     # hparams['shard_optimizer'] (BN_SHARD_OPTIMIZER=0/1): reduce-scatter -> Adam on this rank's 1/R
     # shard of the arena -> all-gather, instead of all-reduce + R identical steps
     # (fitting/distributed.py sharded_step, default_shard_optimizer: on for frame sharding over >= 4 ranks)
@@ -868,6 +872,11 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
             print('fitting an ARHMM on the latents and exporting its states')
         from behavenet_amd.fitting.eval import export_arhmm
         export_arhmm(data_generator, best_val_model, **hparams['export_arhmm'])
+    if method == 'ae' and hparams.get('export_arhmm_grid'):
+        if is_main:
+            print('fitting a grid of ARHMMs on the latents and exporting its selection table and states')
+        from behavenet_amd.fitting.eval import export_arhmm_grid
+        export_arhmm_grid(data_generator, best_val_model, **hparams['export_arhmm_grid'])
     if resume and is_main:
         if state_writer is not None:
             state_writer.wait()

@@ -499,6 +499,30 @@ class ARHMMGroup(object):
         return _hip.hmm_grid_forward_backward(ll, offsets_d, self.Ks, log_Ps, log_pi0,
                                               want_posteriors=False)[2].cpu().numpy()
 
+    def table_states_device(self, table, offsets):
+        """The Viterbi paths of every trial under every model: an int32 DEVICE tensor (M, n), row m what
+        ``models[m].table_states`` returns.  One grid log-likelihood launch and one Viterbi launch a class
+        (``bn_hmm_grid_viterbi``); nothing crosses to the host."""
+        from behavenet_amd import _hip
+        self.models[0]._check_table(table)
+        offsets_d = self.models[0]._offsets_d(table, offsets)
+        ll = self._loglik_table(table, offsets_d)
+        log_Ps, log_pi0 = self._transitions()
+        return _hip.hmm_grid_viterbi(ll, offsets_d, self.Ks, log_Ps, log_pi0)
+
+    def table_states(self, table, offsets):
+        """``table_states_device`` on the host: a list of M int32 arrays (n,), one transfer for the group."""
+        states = self.table_states_device(table, offsets).cpu().numpy()
+        return [states[i].copy() for i in range(self.M)]
+
+    def table_runs(self, table, offsets):
+        """Per model the ``(runs, frames, trans)`` of ``ARHMM.table_runs``, host arrays.  Log-likelihoods, Viterbi and
+        the run searches of all models follow each other on the device; the states never leave it and the results
+        cross in TWO transfers for the whole group (``_hip.state_runs_grid``: the statistics, then the trimmed runs)."""
+        from behavenet_amd import _hip
+        states = self.table_states_device(table, offsets)
+        return _hip.state_runs_grid(states, self.models[0]._offsets_d(table, offsets), self.Ks)
+
     def e_step(self, table, offsets):
         """Per model the ``(moments, gamma_init, xi_sum, gamma0_sum, logliks)`` of ``ARHMM.e_step``, host arrays, from
         three launches and ONE transfer for the whole group."""

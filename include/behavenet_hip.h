@@ -871,6 +871,20 @@ int bn_hmm_grid_forward_backward(const double* ll, const long long* offsets, int
                                  const double* logP, const double* logpi0, int want, double* gamma, double* xi,
                                  double* loglik, void* ws, size_t ws_bytes, bn_stream_t stream);
 
+/* bn_hmm_grid_viterbi: bn_hmm_viterbi for every (trial, model) of a grid -> states int32 (M, n), row m the path of
+ * model m.  ll, koff, xoff, order, n4 .. n32, logP and logpi0 exactly as bn_hmm_grid_forward_backward takes them, the
+ * same packing (one launch a class, a slot of KP lanes a model) and the same empty-slot rules.  The arithmetic of a
+ * slot is bn_hmm_viterbi's term for term, ties to the lowest state: a model's path has the integers bn_hmm_viterbi
+ * gives on that model's own columns, wherever it sits in `order` and whoever shares its wave; a NaN in a model's ll
+ * stays in that model's path, which still lies in [0, K_m).  Rows outside the trials are not written.
+ * ws: bn_hmm_grid_viterbi_ws_bytes bytes (the offsets and uint8 back-pointers (n, KT)).  BN_E_SHAPE / BN_E_BADARG as
+ * above; states on a 4-byte boundary. */
+size_t bn_hmm_grid_viterbi_ws_bytes(int n, int S, int M, int KT, int XT);
+int bn_hmm_grid_viterbi(const double* ll, const long long* offsets, int S, int M, int KT, int XT, int n,
+                        const int* koff, const int* xoff, const int* order, int n4, int n8, int n16, int n32,
+                        const double* logP, const double* logpi0, int* states, void* ws, size_t ws_bytes,
+                        bn_stream_t stream);
+
 /* The generative process of the same model, from noise the CALLER brings: no random number is drawn on the device, so
  * the call is a deterministic function of its operands (the same bits on every call).  Trials as above: offsets
  * int64 (S + 1) made safe, rows outside [e[0], e[S]) neither read nor written.  float64 but for init and the states.
