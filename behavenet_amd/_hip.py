@@ -192,6 +192,11 @@ SIGNATURES = {
     'bn_arhmm_sample_ws_bytes': (_c_size_t, [_c_int] * 5),
     'bn_arhmm_sample': (_c_int, [_c_void_p] * 5 + [_c_int] * 5 + [_c_void_p] * 4 + [_c_int] + [_c_void_p] * 3
                         + [_c_size_t, _c_void_p]),
+    'bn_hmm_predictive_ws_bytes': (_c_size_t, [_c_int] * 3),
+    'bn_hmm_predictive': (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 3 + [_c_void_p] * 4 + [_c_size_t, _c_void_p]),
+    'bn_arhmm_predict_ws_bytes': (_c_size_t, [_c_int] * 5),
+    'bn_arhmm_predict': (_c_int, [_c_void_p, _c_int, _c_void_p] + [_c_int] * 5 + [_c_void_p] * 4
+                         + [_c_size_t, _c_void_p]),
     'bn_state_runs_ws_bytes': (_c_size_t, [_c_int] * 3),
     'bn_state_runs': (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 3 + [_c_void_p, ctypes.c_longlong] + [_c_void_p] * 5
                       + [_c_size_t, _c_void_p]),
@@ -1743,6 +1748,64 @@ def hmm_viterbi(ll, offsets, log_Ps, log_pi0):
                                   states.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes, _stream()),
                'bn_hmm_viterbi')
     return states
+
+
+def hmm_predictive(ll, offsets, log_Ps, log_pi0, out=None):
+    """The causal state weights ``w_t = p(z_t | x_0 .. x_{t-1})`` of every trial over the float64 DEVICE table ``ll``
+    (n, K): a float64 device tensor (n, K) (``bn_hmm_predictive``, csrc/arhmm.hip) -- ``hmm_forward_backward``'s
+    forward sweep with one store a step.  Row t of ``ll`` does not reach ``w_t``; ``w_0 = exp(log_pi0)``.  Rows
+    outside the trials are left as they are (zeros in a fresh ``out``)."""
+    n, K = _ll_table('hmm_predictive', ll)
+    dev = ll.device
+    log_Ps = _f64_operand('hmm_predictive', 'log_Ps', log_Ps, (K, K), dev)
+    log_pi0 = _f64_operand('hmm_predictive', 'log_pi0', log_pi0, (K,), dev)
+    offsets = _trial_offsets('hmm_predictive', offsets, dev)
+    S = int(offsets.numel()) - 1
+    if out is None:
+        out = torch.zeros((n, K), dtype=torch.float64, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.float64 or tuple(out.shape) != (n, K) or out.device != dev \
+            or not out.is_contiguous():
+        raise ValueError('hmm_predictive: expected out float64 (%d, %d) on %s' % (n, K, dev))
+    lib = load()
+    nbytes = lib.bn_hmm_predictive_ws_bytes(n, S, K)
+    if S:
+        _check(lib.bn_hmm_predictive(ll.data_ptr(), offsets.data_ptr(), S, K, n, log_Ps.data_ptr(),
+                                     log_pi0.data_ptr(), out.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes,
+                                     _stream()), 'bn_hmm_predictive')
+    return out
+
+
+def arhmm_predict(table, offsets, W, weights, lags, out=None):
+    """One-step-ahead predictions of an ARHMM on the fp32 DEVICE ``table`` (n, D): a float64 device tensor (n, D)
+    (``bn_arhmm_predict``, csrc/arhmm.hip).  Row t >= lags of a trial gets
+    ``sum_k weights[t, k] (b_k + sum_l A_k[l] x_{t-1-l})`` with ``W[k] = [b_k | A_k]`` float64 (K, D, 1 + lags D)
+    (``models.arhmm.ARHMM.generative()[0]``; host arrays are uploaded) and ``weights`` float64 DEVICE (n, K); a row
+    t < lags gets the row's own values.  Rows outside the trials are left as they are (zeros in a fresh ``out``)."""
+    n, D, ld = _column_table('arhmm_predict', table)
+    L = int(lags)
+    if not torch.is_tensor(W) and np.ndim(W) != 3 or torch.is_tensor(W) and W.dim() != 3:
+        raise ValueError('arhmm_predict: expected W float64 (K, D, 1 + lags D)')
+    K = int(W.shape[0])
+    check_arhmm_dims('arhmm_predict', D, L, K)
+    dev = table.device
+    W = _f64_operand('arhmm_predict', 'W', W, (K, D, 1 + L * D), dev)
+    if not torch.is_tensor(weights) or weights.dim() != 2:
+        raise ValueError('arhmm_predict: expected weights float64 (n, K) on the device')
+    weights = _f64_operand('arhmm_predict', 'weights', weights, (n, K), dev)
+    offsets = _trial_offsets('arhmm_predict', offsets, dev)
+    S = int(offsets.numel()) - 1
+    if out is None:
+        out = torch.zeros((n, D), dtype=torch.float64, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.float64 or tuple(out.shape) != (n, D) or out.device != dev \
+            or not out.is_contiguous():
+        raise ValueError('arhmm_predict: expected out float64 (%d, %d) on %s' % (n, D, dev))
+    lib = load()
+    nbytes = lib.bn_arhmm_predict_ws_bytes(n, S, D, L, K)
+    if S:
+        _check(lib.bn_arhmm_predict(table.data_ptr(), ld, offsets.data_ptr(), S, D, L, K, n, W.data_ptr(),
+                                    weights.data_ptr(), out.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes,
+                                    _stream()), 'bn_arhmm_predict')
+    return out
 
 
 # A grid of models on one table (bn_arhmm_grid_*, bn_hmm_grid_forward_backward): AR_GRID_MAX_KT, AR_GRID_MAX_M.  The

@@ -84,6 +84,25 @@
 //                walk back takes all slots at once: 64 rows of the wave's 64 back-pointer bytes are staged in LDS
 //                (4 KiB), the first lane of every slot walks its own chain and leaves the chunk's states in LDS, and
 //                the wave writes them slot after slot as states[m * n + row], neighbouring lanes on neighbouring rows.
+// One-step-ahead predictions (bn_hmm_predictive, bn_arhmm_predict):
+// k_hmm_pred     the causal weights w_t = p(z_t | x_0 .. x_{t-1}), one wave a trial: k_hmm_fb's forward sweep (the same
+//                lane layout, LDS exchange and scaling) with ONE store added and the likelihood left out.  The readers
+//                of step t form dot[j] = sum_i u_t[i] P[i][j] / sum_i u_t[i] anyway; that is w_{t+1}[j], written before
+//                row t + 1 of ll enters (w_0 = exp(logpi0)), so row t of ll never reaches w_t.  The last step is not
+//                run: nobody reads it.
+// k_arp_fold     W (K, D, Q), Q = 1 + L D, into the workspace as the B operand wt[j][d], j = k Q + q: JP = K Q padded
+//                to a multiple of 16 rows of DP = D padded to a multiple of 16 doubles, zeros in the padding, so
+//                the B loads of k_ar_predict are whole tile rows (128 B a k-index) and need no bounds.
+// k_ar_predict   xhat_t = sum_k w_t[k] (b_k + sum_l A_k[l] x_{t-1-l}) for AR rows: the (n x K Q) (K Q x D) product on
+//                v_mfma_f64_16x16x4_f64.  A wave takes 32 rows (two row tiles of 16); phi_t = (1, x_{t-1}, ..,
+//                x_{t-L}) is staged in LDS as float64 rows as k_ar_loglik stages a_t, and the rows' K weights beside
+//                them (zeros for the rows that are not AR rows).  The A entry (row, j = k Q + q) is w[k] phi[q], the
+//                weight folded into the fragment as k_ar_moments folds gamma; lane (col, kk) walks j = kk, kk + 4,
+//                ... with k = j / Q by the fp32 reciprocal (exact for these sizes), four B loads in flight.  The tile COLUMNS are the output dimensions d (16 a
+//                tile, D / 16 tiles one after the other): the chain over j leaves xhat for 16 rows x 16 dimensions in
+//                the accumulators, no cross-lane step.  Initial rows get the row's own values, one lane a row.  A NaN
+//                in row t is in the staged rows phi_{t+1} .. phi_{t+L} of its trial and nowhere else, and a row of A
+//                reaches its own row of the product only.
 // No global atomics; every output element is written exactly once by each kernel that owns it.
 #include <limits.h>
 #include <math.h>
@@ -108,6 +127,9 @@
 #define AR_S_MAX_D 32                       // D at most where L > 0
 #define AR_GRID_MAX_KT 512                  // a grid of models: states of all models together at most ...
 #define AR_GRID_MAX_M 512                   // ... and models
+#define AR_PR_THREADS 128                   // k_ar_predict: two waves ...
+#define AR_PR_WAVES (AR_PR_THREADS / BN_WAVE)
+#define AR_PR_ROWS 32                       // ... of 32 rows (two row tiles) each
 
 typedef double ar_d4 __attribute__((ext_vector_type(4)));
 
@@ -1047,6 +1069,149 @@ __global__ __launch_bounds__(BN_WAVE) void k_ars_recur(const double* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// one-step-ahead predictions
+template <int KP>
+__global__ __launch_bounds__(BN_WAVE) void k_hmm_pred(const double* __restrict__ ll, const int* __restrict__ e, int K,
+                                                      const double* __restrict__ logP,
+                                                      const double* __restrict__ logpi0, double* __restrict__ w) {
+    __shared__ __attribute__((aligned(16))) double buf[2][KP];                 // [parity][state]
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int beg = e[s], T = e[s + 1] - beg;
+    if (T <= 0) return;
+    const bool active = lane < K, writer = lane < KP;
+    const double* l = ll + (size_t)beg * K;
+    double* wt = w + (size_t)beg * K;
+    const double ninf = -INFINITY;
+
+    double Pc[KP];
+#pragma unroll
+    for (int i = 0; i < KP; ++i) Pc[i] = active && i < K ? exp(logP[i * K + lane]) : 0.0;
+    const double pi = active ? exp(logpi0[lane]) : 0.0;
+    if (active) wt[lane] = pi;
+
+    // k_hmm_fb's pipeline: the row maximum and exp of row t + 1 are formed during step t, row t + 2 is asked for then
+    double b, dot = 0.0;
+    {
+        const double lv = active ? l[lane] : ninf;
+        const double m = ar_wave_max(lv);
+        b = active ? exp(lv - m) : 0.0;
+    }
+    double l1 = active && T > 1 ? l[(size_t)K + lane] : ninf;
+    for (int t = 0; t + 1 < T; ++t) {
+        const double l2 = active && t + 2 < T ? l[(size_t)(t + 2) * K + lane] : ninf;
+        const double u = t == 0 ? pi * b : dot * b;
+        const int par = t & 1;
+        if (writer) buf[par][lane] = u;
+        __syncthreads();
+        const double mn = ar_wave_max(l1);
+        const double bn = active ? exp(l1 - mn) : 0.0;
+        double s4[4] = {0.0, 0.0, 0.0, 0.0}, d4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int i = 0; i < KP; ++i) {
+            const double ui = buf[par][i];
+            s4[i & 3] += ui;
+            d4[i & 3] += ui * Pc[i];
+        }
+        const double st = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+        const double inv = 1.0 / st;
+        dot = ((d4[0] + d4[1]) + (d4[2] + d4[3])) * inv;
+        if (active) wt[(size_t)(t + 1) * K + lane] = dot;  // the ONE store: p(z_{t+1} = lane | x_0 .. x_t)
+        b = bn;
+        l1 = l2;
+    }
+}
+
+// wt[j][d] = W[k][d][q] for j = k Q + q < K Q and d < D, zeros in the padding; one thread an element
+__global__ __launch_bounds__(256) void k_arp_fold(const double* __restrict__ W, int D, int Q, int K, int DP, int total,
+                                                  double* __restrict__ wt) {
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= total) return;
+    const int j = o / DP, d = o - j * DP;
+    const int k = j / Q, q = j - k * Q;
+    wt[o] = k < K && d < D ? W[((size_t)k * D + d) * Q + q] : 0.0;
+}
+
+// doubles a staged row of phi: Q padded to a multiple of four, plus 4 (k_ar_loglik's row stride)
+__host__ __device__ constexpr int arp_lw(int Q) { return ((Q + 3) & ~3) + 4; }
+
+__global__ __launch_bounds__(AR_PR_THREADS) void k_ar_predict(const float* __restrict__ z, int ld,
+                                                              const unsigned char* __restrict__ kind, int D, int L,
+                                                              int K, int n, const double* __restrict__ wt, int DP,
+                                                              const double* __restrict__ w,
+                                                              double* __restrict__ xhat) {
+    // a wave's 32 rows of phi (LW doubles a row) and of weights (WW a row), sized by the launch: a
+    // few KiB at D = 16 and one lag, so that many waves share a CU and hide the B loads of each other
+    extern __shared__ double arp_lds[];
+    const int tid = threadIdx.x, lane = tid & (BN_WAVE - 1), wave = tid / BN_WAVE;
+    const int kk = lane >> 4, col = lane & 15;
+    const int Q = 1 + L * D, LW = arp_lw(Q), WW = K + 1, JS = (K * Q + 3) >> 2;     // (taken four at a time: wt has the rows)
+    const long row0 = ((long)blockIdx.x * AR_PR_WAVES + wave) * AR_PR_ROWS;
+    double* st = arp_lds + (size_t)wave * AR_PR_ROWS * (LW + WW);
+    double* wg = st + AR_PR_ROWS * LW;
+    const float rq = 1.0f / (float)Q;
+
+    for (int idx = lane; idx < AR_PR_ROWS * Q; idx += BN_WAVE) {
+        const int r = idx / Q, q = idx - r * Q;
+        const long row = row0 + r;
+        double v = 0.0;
+        if (row < n && kind[row] == 2) {
+            if (q == 0) {
+                v = 1.0;
+            } else {
+                const int lag = (q - 1) / D, j = q - 1 - lag * D;
+                v = (double)z[(size_t)(row - 1 - lag) * ld + j];
+            }
+        }
+        st[r * LW + q] = v;
+    }
+    for (int idx = lane; idx < AR_PR_ROWS * K; idx += BN_WAVE) {
+        const int r = idx / K, k = idx - r * K;
+        const long row = row0 + r;
+        wg[r * WW + k] = row < n && kind[row] == 2 ? w[(size_t)row * K + k] : 0.0;
+    }
+    __syncthreads();
+
+    for (int ct = 0; ct * 16 < D; ++ct) {
+        const int d = ct * 16 + col;
+        const double* bp = wt + (size_t)kk * DP + d;       // row j = 4 step + kk of the folded operand
+        ar_d4 c0 = {0.0, 0.0, 0.0, 0.0}, c1 = {0.0, 0.0, 0.0, 0.0};
+        // A: row `col` of the tile, entry j = k Q + q: w[k] phi[q]; B: entry j of column d.  k = j / Q by the fp32
+        // reciprocal: (j + 1/2) / Q is at least 1 / (2 Q) >= 0.008 away from an integer and j < 2048, far more than
+        // the product's rounding (2048 x 2^-23).  Four k-steps at a time without a branch (the operand's rows are
+        // padded to 16 with zeros), so four B loads are in flight
+        for (int s4 = 0; s4 < JS; s4 += 4) {
+#pragma unroll
+            for (int step = s4; step < s4 + 4; ++step) {
+                const int j = 4 * step + kk;
+                const int k = (int)(((float)j + 0.5f) * rq), q = j - k * Q;
+                const bool live = k < K;
+                const int kc = live ? k : 0, qc = live ? q : 0;
+                const double b = bp[(size_t)step * 4 * DP];
+                const double a0 = live ? wg[col * WW + kc] * st[col * LW + qc] : 0.0;
+                const double a1 = live ? wg[(16 + col) * WW + kc] * st[(16 + col) * LW + qc] : 0.0;
+                c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, c0, 0, 0, 0);
+                c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, c1, 0, 0, 0);
+            }
+        }
+        // C/D of the f64 MFMA: column lane & 15 (the dimension), row (lane >> 4) + 4 * reg
+        if (d < D) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long ra = row0 + kk + 4 * r, rb = ra + 16;
+                if (ra < n && kind[ra] == 2) xhat[(size_t)ra * D + d] = c0[r];
+                if (rb < n && kind[rb] == 2) xhat[(size_t)rb * D + d] = c1[r];
+            }
+        }
+    }
+    // the initial rows: nothing to predict from, the row's own values
+    if (lane < AR_PR_ROWS) {
+        const long row = row0 + lane;
+        if (row < n && kind[row] == 1)
+            for (int j = 0; j < D; ++j) xhat[(size_t)row * D + j] = (double)z[(size_t)row * ld + j];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 bool bn_arhmm_ok(int n, int S, int D, int L, int K) {
     return n >= 0 && S >= 0 && S < INT32_MAX && ar_dims_ok(D, L, K);
 }
@@ -1347,6 +1512,59 @@ int bn_launch_arhmm_sample(const double* W, const double* C, const double* cdf0,
     else if (EL <= 8) hipLaunchKernelGGL(k_ars_recur<8>, grid, block, 0, st, W, ce, cbad, D, L, NP, cs, x);
     else if (EL <= 16) hipLaunchKernelGGL(k_ars_recur<16>, grid, block, 0, st, W, ce, cbad, D, L, NP, cs, x);
     else hipLaunchKernelGGL(k_ars_recur<24>, grid, block, 0, st, W, ce, cbad, D, L, NP, cs, x);
+    BN_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- one-step-ahead predictions
+static int arp_dp(int D) { return (D + 15) & ~15; }
+static int arp_jp(int D, int L, int K) { return (K * (1 + L * D) + 15) & ~15; }   // four k-steps of four rows
+
+size_t bn_hmm_predictive_ws_bytes_impl(int n, int S, int K) {
+    if (!bn_hmm_ok(n, S, K)) return 0;
+    return ar_offsets_bytes(S);
+}
+
+size_t bn_arhmm_predict_ws_bytes_impl(int n, int S, int D, int L, int K) {
+    if (!bn_arhmm_ok(n, S, D, L, K)) return 0;
+    return ar_offsets_bytes(S) + ar_pad16((size_t)n) + (size_t)arp_jp(D, L, K) * arp_dp(D) * sizeof(double);
+}
+
+int bn_launch_hmm_predictive(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
+                             const double* logpi0, double* w, void* ws, hipStream_t st) {
+    if (!bn_hmm_ok(n, S, K)) return BN_E_SHAPE;
+    if (S == 0) return 0;
+    int* e = reinterpret_cast<int*>(ws);
+    const int rc = bn_launch_segment_offsets(offsets, S + 1, n, e, st);
+    if (rc) return rc;
+    const dim3 grid((unsigned)S), block(BN_WAVE);
+    const int* ce = e;
+    if (K <= 4) hipLaunchKernelGGL(k_hmm_pred<4>, grid, block, 0, st, ll, ce, K, logP, logpi0, w);
+    else if (K <= 8) hipLaunchKernelGGL(k_hmm_pred<8>, grid, block, 0, st, ll, ce, K, logP, logpi0, w);
+    else if (K <= 16) hipLaunchKernelGGL(k_hmm_pred<16>, grid, block, 0, st, ll, ce, K, logP, logpi0, w);
+    else hipLaunchKernelGGL(k_hmm_pred<32>, grid, block, 0, st, ll, ce, K, logP, logpi0, w);
+    BN_LAUNCH_CHECK();
+    return 0;
+}
+
+int bn_launch_arhmm_predict(const float* z, int ld, const long long* offsets, int S, int D, int L, int K, int n,
+                            const double* W, const double* w, double* xhat, void* ws, hipStream_t st) {
+    if (!bn_arhmm_ok(n, S, D, L, K)) return BN_E_SHAPE;
+    if (S == 0) return 0;
+    const int rc = ar_launch_kind(offsets, S, L, n, ws, st);
+    if (rc) return rc;
+    if (!n) return 0;
+    const unsigned char* kind = reinterpret_cast<const unsigned char*>(ws) + ar_offsets_bytes(S);
+    double* wt = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + ar_offsets_bytes(S) + ar_pad16((size_t)n));
+    const int DP = arp_dp(D), total = arp_jp(D, L, K) * DP;
+    hipLaunchKernelGGL(k_arp_fold, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W, D, 1 + L * D, K, DP,
+                       total, wt);
+    BN_LAUNCH_CHECK();
+    const long per = AR_PR_WAVES * AR_PR_ROWS;
+    // LDS a workgroup: at most 2 x 32 x (64 + 33) doubles = 48.5 KiB (Q <= 57, K <= 32)
+    const size_t lds = (size_t)AR_PR_WAVES * AR_PR_ROWS * (arp_lw(1 + L * D) + K + 1) * sizeof(double);
+    hipLaunchKernelGGL(k_ar_predict, dim3((unsigned)(((long)n + per - 1) / per)), dim3(AR_PR_THREADS), lds, st, z, ld,
+                       kind, D, L, K, n, (const double*)wt, DP, w, xhat);
     BN_LAUNCH_CHECK();
     return 0;
 }

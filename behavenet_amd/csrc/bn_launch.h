@@ -187,6 +187,13 @@ int bn_launch_arhmm_sample(const double* W, const double* C, const double* cdf0,
                            const long long* offsets, int S, int D, int L, int K, int n, const double* eps,
                            const double* u, const int* states_in, const float* init, int ld_init, double* x,
                            int* states, void* ws, hipStream_t st);
+// ... and one-step-ahead predictions: the causal weights p(z_t | x_0 .. x_{t-1}), and sum_k w_t[k] (b_k + A_k history)
+size_t bn_hmm_predictive_ws_bytes_impl(int n, int S, int K);
+size_t bn_arhmm_predict_ws_bytes_impl(int n, int S, int D, int L, int K);
+int bn_launch_hmm_predictive(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
+                             const double* logpi0, double* w, void* ws, hipStream_t st);
+int bn_launch_arhmm_predict(const float* z, int ld, const long long* offsets, int S, int D, int L, int K, int n,
+                            const double* W, const double* w, double* xhat, void* ws, hipStream_t st);
 
 // state_runs.hip: the runs (trial, beg, end, state) of an int32 state table cut into trials, in table order, with
 // the frames per state and the in-trial transition counts

@@ -2263,6 +2263,36 @@ extern "C" int bn_arhmm_sample(const double* W, const double* C, const double* c
                                   ws, (hipStream_t)stream);
 }
 
+// ... and one-step-ahead predictions of a fitted model
+extern "C" size_t bn_hmm_predictive_ws_bytes(int n, int S, int K) { return bn_hmm_predictive_ws_bytes_impl(n, S, K); }
+
+extern "C" size_t bn_arhmm_predict_ws_bytes(int n, int S, int D, int L, int K) {
+    return bn_arhmm_predict_ws_bytes_impl(n, S, D, L, K);
+}
+
+extern "C" int bn_hmm_predictive(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
+                                 const double* logpi0, double* w, void* ws, size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_hmm_ok(n, S, K)) return BN_E_SHAPE;
+    if (!ll || !offsets || !logP || !logpi0 || !w || !ws) return BN_E_BADARG;
+    if (((uintptr_t)ll & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)logP & 7) || ((uintptr_t)logpi0 & 7) ||
+        ((uintptr_t)w & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_hmm_predictive_ws_bytes_impl(n, S, K)) return BN_E_SHAPE;
+    return bn_launch_hmm_predictive(ll, offsets, S, K, n, logP, logpi0, w, ws, (hipStream_t)stream);
+}
+
+extern "C" int bn_arhmm_predict(const float* z, int ld, const long long* offsets, int S, int D, int L, int K, int n,
+                                const double* W, const double* w, double* xhat, void* ws, size_t ws_bytes,
+                                bn_stream_t stream) {
+    if (!bn_arhmm_ok(n, S, D, L, K) || ld < D) return BN_E_SHAPE;
+    if (!z || !offsets || !W || !w || !xhat || !ws) return BN_E_BADARG;
+    if (((uintptr_t)z & 3) || ((uintptr_t)offsets & 7) || ((uintptr_t)W & 7) || ((uintptr_t)w & 7) ||
+        ((uintptr_t)xhat & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_arhmm_predict_ws_bytes_impl(n, S, D, L, K)) return BN_E_SHAPE;
+    return bn_launch_arhmm_predict(z, ld, offsets, S, D, L, K, n, W, w, xhat, ws, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // The runs of a state table, per trial and in table order, with the frames per state and the transition counts
 // (state_runs.hip): what the syllable movies and the state-duration statistics are made from.

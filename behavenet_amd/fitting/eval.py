@@ -2676,6 +2676,100 @@ def export_arhmm_grid(data_generator, model, grid, n_iters=150, tol=0, sess_idx=
     return fits, selection, path, files
 
 
+# ------------------------------------------------------------------------------------------ ARHMM predictions
+ARHMM_PREDICTIONS_FILE = 'arhmm_predictions.csv'
+_PREDICTION_MEASURES = ('mse', 'r2', 'mse_persistence', 'r2_persistence')
+
+
+def summarise_prediction_sums(sums, min_valid=10):
+    """Prediction scores from the sums ``ARHMM.prediction_sums`` returns, ``(2, S, D, 4)`` -- the model's and the
+    persistence baseline's, per trial and dimension -- in numpy float64 on the host, by ``summarise_label_sums``:
+    ``'n'``, ``'mse'``, ``'r2'``, ``'mse_persistence'``, ``'r2_persistence'``, each ``(S, D)`` (scores NaN where
+    ``n <= min_valid``), and ``'pooled'``, the same five per dimension ``(D,)`` from the sums added over the trials
+    plus, over all dimensions, ``'mse_all'`` / ``'mse_persistence_all'`` (``sum_d sd / sum_d n``) and ``'r2_all'`` /
+    ``'r2_persistence_all'`` (the variance-weighted R^2, ``1 - sum_d sd / sum_d ss_tot``)."""
+    sums = np.asarray(sums, dtype=np.float64)
+    if sums.ndim != 4 or sums.shape[0] != 2 or sums.shape[3] != 4:
+        raise ValueError('summarise_prediction_sums: expected sums (2, S, D, 4), got %s' % (tuple(sums.shape),))
+    model, base = summarise_label_sums(sums[0], min_valid), summarise_label_sums(sums[1], min_valid)
+    out = {'n': model['n'], 'mse': model['mse'], 'r2': model['r2'], 'mse_persistence': base['mse'],
+           'r2_persistence': base['r2']}
+    pooled = {'n': model['pooled']['n']}
+    for scored, tot, tag in ((model, sums[0].sum(axis=0), ''), (base, sums[1].sum(axis=0), '_persistence')):
+        pooled['mse' + tag], pooled['r2' + tag] = scored['pooled']['mse'], scored['pooled']['r2']
+        rows = float(tot[:, 0].sum())
+        pooled['mse%s_all' % tag] = float(tot[:, 3].sum() / rows) if rows else float('nan')
+        pooled['r2%s_all' % tag] = scored['pooled']['r2_variance_weighted']
+    out['pooled'] = pooled
+    return out
+
+
+def arhmm_predictions(data_generator, model, arhmm, dtype='test', weights='predictive', sess_idx=None,
+                      data_key='ae_latents', return_latents=False):
+    """How well a fitted ARHMM predicts the next latent, in the latents' own units: per trial and dimension the mean
+    squared error and R^2 of the one-step-ahead prediction ``sum_k w_t[k] (b_k + sum_l A_k[l] x_{t-1-l})`` and of the
+    persistence baseline ``x_{t-1}`` over the rows ``t >= max(lags, 1)`` of every trial of the split ``dtype`` (or a
+    list of splits) of the sessions ``sess_idx``.  ``weights``: ``'predictive'``, the causal
+    ``p(z_t | x_0 .. x_{t-1})``, or ``'smoothed'``, the posterior marginals (the ``ssm`` library's ``smooth``).
+
+    The trials are walked and encoded ONCE as ``fit_arhmm`` walks and encodes them (``data_key='labels'``: the
+    generator's labels, ``model`` may be None) into one device table; log-likelihoods, weights, predictions and the
+    two ``bn_segment_label_sums`` reductions follow each other on the device (``ARHMM.prediction_sums``) and
+    ``(2, S, D, 4)`` doubles cross to the host.
+    -> ``summarise_prediction_sums``'s dict plus ``'session'`` and ``'trial'``, int arrays ``(S,)`` in the table's
+    order, and ``'sums'``; with ``return_latents`` also ``'latents'`` and ``'latents_pred'``, lists of host (T, D)
+    arrays per trial -- the operands of ``real_vs_sampled_movie(model, latents, latents_pred)`` for a
+    real-versus-predicted movie.  Under ``torch.distributed`` rank 0 works and the other ranks return None."""
+    who = 'arhmm_predictions'
+    dtypes = _splits(who, dtype)
+    if data_key == 'ae_latents':
+        _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return None
+    wanted = _wanted_sessions(who, data_generator, sess_idx)
+    parts = _arhmm_trials(who, data_generator, model, data_key, dtypes, wanted)
+    idxs = [ds.batch_idxs for ds in data_generator.datasets]
+    table, offsets, sessions, trials = _arhmm_split(parts, _corr_trial_order(idxs, dtypes, wanted))
+    if table is None:
+        raise ValueError('%s: the sessions %s have no %s frames' % (who, sorted(wanted), ' or '.join(dtypes)))
+    xhat, valid = arhmm.table_predictions(table, offsets, weights)
+    sums = arhmm.sums_of_predictions(table, offsets, xhat, valid)
+    out = summarise_prediction_sums(sums)
+    out.update({'session': sessions, 'trial': trials, 'sums': sums})
+    if return_latents:
+        host, pred = table.cpu().numpy(), xhat.cpu().numpy()
+        out['latents'] = [host[offsets[i]:offsets[i + 1]].copy() for i in range(len(sessions))]
+        out['latents_pred'] = [pred[offsets[i]:offsets[i + 1]].copy() for i in range(len(sessions))]
+    return out
+
+
+def export_arhmm_predictions(hparams, data_generator, arhmm, model=None, dtype='test', weights='predictive',
+                             filename=None):
+    """``arhmm_predictions`` as a table next to the states files: ``arhmm_predictions.csv`` under
+    ``hparams['expt_dir']/version_<hparams['version']>`` (or ``filename``), one row per (trial, dimension) in the
+    table's order with the columns ``Session, Trial, Dim, N, MSE, R2, MSE_persistence, R2_persistence``; a NaN is an
+    empty field, as in ``export_label_r2``'s table.  Latents or labels by ``hparams['model_class']`` as
+    ``export_states`` chooses.  Written with the ``csv`` module.  -> the path (None on the ranks other than 0)."""
+    import csv
+    data_key = 'labels' if str(hparams.get('model_class', 'arhmm')).find('label') > -1 else 'ae_latents'
+    scores = arhmm_predictions(data_generator, model, arhmm, dtype=dtype, weights=weights, data_key=data_key)
+    if scores is None:
+        return None
+    if filename is None:
+        filename = os.path.join(hparams['expt_dir'], 'version_%i' % hparams['version'], ARHMM_PREDICTIONS_FILE)
+
+    def field(v):
+        return '' if np.isnan(v) else repr(float(v))
+    with open(filename, 'w', newline='') as f:
+        writer = csv.writer(f, lineterminator='\n')
+        writer.writerow(['Session', 'Trial', 'Dim', 'N', 'MSE', 'R2', 'MSE_persistence', 'R2_persistence'])
+        for k, (sess, trial) in enumerate(zip(scores['session'], scores['trial'])):
+            for d in range(scores['n'].shape[1]):
+                writer.writerow([int(sess), int(trial), d, int(scores['n'][k, d])]
+                                + [field(scores[name][k, d]) for name in _PREDICTION_MEASURES])
+    return filename
+
+
 # ------------------------------------------------------------------------------------------ ARHMM samples
 def sample_arhmm(data_generator, model, arhmm, n_samples=50, conditional=True, dtype='test', sess_idx=None,
                  data_key='ae_latents', seed=0):

@@ -9,7 +9,9 @@ Everything else is a ``NotImplementedError`` that names the type.
 
 Host side: numpy float64 only -- the M-step, the fold of the parameters for the kernel, the priors.  Device side (per EM
 iteration): ``bn_arhmm_loglik`` -> ``bn_hmm_forward_backward`` -> ``bn_arhmm_moments`` on one fp32 table that holds
-every trial, one transfer of ``K (P^2 + K + 1)`` doubles.
+every trial, one transfer of ``K (P^2 + K + 1)`` doubles.  A fitted model predicts the next latent
+(``table_predictions``, ``prediction_sums``, ``predict``, ``smooth``): ``bn_hmm_predictive`` or the posterior marginals
+for the state weights, ``bn_arhmm_predict`` for the mixture of the states' regressions.
 
 Model, with ``x_t`` the row, ``L = lags`` and state ``k`` at time ``t``:
 
@@ -27,6 +29,7 @@ import numpy as np
 _LOG_2PI = float(np.log(2.0 * np.pi))
 _SERVED_TRANSITIONS = ('stationary', 'sticky')
 _SERVED_OBSERVATIONS = ('ar', 'gaussian')
+PREDICTION_WEIGHTS = ('predictive', 'smoothed')
 
 
 class ARHMM(object):
@@ -337,6 +340,71 @@ class ARHMM(object):
     def most_likely_states(self, x):
         table, offsets = self.as_table(x)
         return self.table_states(table, offsets)
+
+    # ------------------------------------------------------------------------------------------------------
+    # one-step-ahead predictions (bn_hmm_predictive, bn_arhmm_predict)
+    # ------------------------------------------------------------------------------------------------------
+    def table_weights(self, table, offsets, weights='predictive'):
+        """The state weights (n, K) the predictions are mixed with, a float64 device tensor: ``'predictive'``, the
+        causal ``p(z_t | x_0 .. x_{t-1})`` (``bn_hmm_predictive``), or ``'smoothed'``, the posterior marginals
+        ``gamma`` (``bn_hmm_forward_backward``), which have seen the whole trial."""
+        from behavenet_amd import _hip
+        if weights not in PREDICTION_WEIGHTS:
+            raise ValueError('ARHMM: weights %r are not served (%s are)' % (weights, ', '.join(PREDICTION_WEIGHTS)))
+        self._check_table(table)
+        offsets_d = self._offsets_d(table, offsets)
+        ll = self._loglik_table(table, offsets_d)
+        if weights == 'predictive':
+            return _hip.hmm_predictive(ll, offsets_d, self.log_Ps, self.log_pi0)
+        return _hip.hmm_forward_backward(ll, offsets_d, self.log_Ps, self.log_pi0)[0]
+
+    def table_predictions(self, table, offsets, weights='predictive'):
+        """``(xhat, valid)`` for every row of the table, device tensors float64 (n, D) and bool (n,):
+        ``xhat_t = sum_k w_t[k] (b_k + sum_l A_k[l] x_{t-1-l})`` for row ``t >= lags`` of a trial, the row's own
+        values before (nothing to predict from), zeros outside the trials; ``valid`` marks the in-trial rows with
+        ``t >= max(lags, 1)``, on which the prediction and the persistence baseline ``x_{t-1}`` are both defined.
+        Three launches (log-likelihoods, weights, the product); nothing crosses to the host."""
+        import torch
+        from behavenet_amd import _hip
+        w = self.table_weights(table, offsets, weights)
+        offsets_d = self._offsets_d(table, offsets)
+        xhat = _hip.arhmm_predict(table, offsets_d, self.generative()[0], w, self.lags)
+        n = int(table.shape[0])
+        e = offsets_d.clamp(0, n)
+        beg = torch.minimum(e[:-1] + max(self.lags, 1), e[1:])
+        steps = torch.zeros((n + 1,), dtype=torch.int32, device=table.device)
+        steps.index_add_(0, beg, torch.ones_like(beg, dtype=torch.int32))
+        steps.index_add_(0, torch.maximum(e[1:], beg), -torch.ones_like(beg, dtype=torch.int32))
+        return xhat, steps.cumsum(0)[:n] > 0
+
+    def prediction_sums(self, table, offsets, weights='predictive'):
+        """Per trial and dimension the count, ``sum x``, ``sum x^2`` and ``sum (x - pred)^2`` over the valid rows, for
+        the model's prediction ([0]) and for the persistence baseline ``pred_t = x_{t-1}`` ([1]): a float64 host array
+        ``(2, S, D, 4)`` for ``fitting.eval.summarise_label_sums``.  R^2 of a one-step prediction on smooth latents is
+        close to 1 for any model; the baseline says what the model adds.  The prediction is rounded to fp32, the
+        table's own format; both reductions are ``bn_segment_label_sums`` launches and ONE transfer follows."""
+        return self.sums_of_predictions(table, offsets, *self.table_predictions(table, offsets, weights))
+
+    def sums_of_predictions(self, table, offsets, xhat, valid):
+        """``prediction_sums`` for predictions ``table_predictions`` has made already."""
+        import torch
+        from behavenet_amd import _hip
+        offsets_d = self._offsets_d(table, offsets)
+        mask = valid.to(torch.float32)[:, None].expand(-1, self.D).contiguous()
+        previous = torch.zeros(tuple(table.shape), dtype=torch.float32, device=table.device)
+        previous[1:] = table[:-1]
+        sums = torch.stack([_hip.segment_label_sums(xhat.to(torch.float32), table, mask, offsets_d),
+                            _hip.segment_label_sums(previous, table, mask, offsets_d)])
+        return sums.cpu().numpy()
+
+    def predict(self, x, weights='predictive'):
+        """``table_predictions`` for ONE host trial (T, D): a float64 host array (T, D)."""
+        table, offsets = self.as_table(x)
+        return self.table_predictions(table, offsets, weights)[0].cpu().numpy()
+
+    def smooth(self, x):
+        """The posterior-weighted mean of the observation model for one trial (the library's ``smooth``)."""
+        return self.predict(x, 'smoothed')
 
     # ------------------------------------------------------------------------------------------------------
     # the generative process (bn_arhmm_sample)

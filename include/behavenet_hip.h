@@ -916,6 +916,33 @@ int bn_arhmm_sample(const double* W, const double* C, const double* cdf0, const 
                     const float* init, int ld_init, double* x, int* states, void* ws, size_t ws_bytes,
                     bn_stream_t stream);
 
+/* One-step-ahead predictions of the same model, in the latents' own units.  Trials, limits, alignment and error rules
+ * as above; rows outside [e[0], e[S]) are neither read nor written.  No atomics, every sum in a fixed order: the same
+ * bits on every call.
+ *
+ * bn_hmm_predictive -> w (n, K): the causal state weights w_t = p(z_t | x_0 .. x_{t-1}) of every trial.  ll, logP and
+ * logpi0 as bn_hmm_forward_backward takes them.  w_0 = exp(logpi0) and w_t[j] = sum_i ahat_{t-1}[i] P[i][j] divided by
+ * sum_i ahat_{t-1}[i], with ahat the filtered marginals of bn_hmm_forward_backward's scaled forward sweep: one wave a
+ * trial, that sweep with one store a step added (the call's time is (longest trial) x (step latency)).  Row t of ll
+ * does not reach w_t.  A row of ll that is not finite makes the weights of the LATER rows of its trial non-finite (all
+ * K of each) and touches nothing else.  ws: bn_hmm_predictive_ws_bytes bytes (the offsets).
+ *
+ * bn_arhmm_predict -> xhat (n, D): for an AR row  xhat_t = sum_k w_t[k] (b_k + sum_l A_k[l] x_{t-1-l}),  for an
+ * initial row (nothing to predict from) the row's own values widened.  W: (K, D, 1 + L D), [b_k | A_k] in the model's
+ * own coordinates as bn_arhmm_sample takes it; w: (n, K), any weights (bn_hmm_predictive's, or gamma of
+ * bn_hmm_forward_backward for the smoothed mean); read for AR rows only.  The (n x K Q) (K Q x D) product, Q = 1 + L D,
+ * on v_mfma_f64_16x16x4_f64 with the A entry w_t[k] phi_t[q], phi_t = (1, x_{t-1}, .., x_{t-L}); sums over (k, q) in
+ * ascending order.  No shift: a product of fp32 values in float64, not a difference of moments.  A NaN or Inf in row t
+ * of z reaches xhat of the AR rows among the L rows after it in its trial (and row t itself if it is an initial row);
+ * one in row t of w reaches row t of xhat.  ws: bn_arhmm_predict_ws_bytes bytes (the offsets, one byte a row and W
+ * as a padded operand, under 1 MiB).  BN_E_SHAPE also for ld < D. */
+size_t bn_hmm_predictive_ws_bytes(int n, int S, int K);
+int bn_hmm_predictive(const double* ll, const long long* offsets, int S, int K, int n, const double* logP,
+                      const double* logpi0, double* w, void* ws, size_t ws_bytes, bn_stream_t stream);
+size_t bn_arhmm_predict_ws_bytes(int n, int S, int D, int L, int K);
+int bn_arhmm_predict(const float* z, int ld, const long long* offsets, int S, int D, int L, int K, int n,
+                     const double* W, const double* w, double* xhat, void* ws, size_t ws_bytes, bn_stream_t stream);
+
 /* The runs of a table of discrete states (get_discrete_chunks / get_state_durations of plotting/arhmm_utils.py:24-99,
  * which pad and difference every trial on the host): states int32 (n), the output of bn_hmm_viterbi; offsets int64
  * (S + 1) made safe as above (clamped into [0, n], ascending), empty trials allowed; rows outside [e[0], e[S]) are
