@@ -197,6 +197,9 @@ SIGNATURES = {
     'bn_arhmm_predict_ws_bytes': (_c_size_t, [_c_int] * 5),
     'bn_arhmm_predict': (_c_int, [_c_void_p, _c_int, _c_void_p] + [_c_int] * 5 + [_c_void_p] * 4
                          + [_c_size_t, _c_void_p]),
+    'bn_arhmm_forecast_sums_ws_bytes': (_c_size_t, [_c_int] * 6),
+    'bn_arhmm_forecast_sums': (_c_int, [_c_void_p, _c_int, _c_void_p] + [_c_int] * 6 + [_c_void_p] * 4
+                               + [_c_size_t, _c_void_p]),
     'bn_state_runs_ws_bytes': (_c_size_t, [_c_int] * 3),
     'bn_state_runs': (_c_int, [_c_void_p, _c_void_p] + [_c_int] * 3 + [_c_void_p, ctypes.c_longlong] + [_c_void_p] * 5
                       + [_c_size_t, _c_void_p]),
@@ -1805,6 +1808,50 @@ def arhmm_predict(table, offsets, W, weights, lags, out=None):
         _check(lib.bn_arhmm_predict(table.data_ptr(), ld, offsets.data_ptr(), S, D, L, K, n, W.data_ptr(),
                                     weights.data_ptr(), out.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes,
                                     _stream()), 'bn_arhmm_predict')
+    return out
+
+
+ARHMM_MAX_HORIZONS = 32                                 # AR_FC_MAX_H
+
+
+def check_arhmm_horizons(who, H):
+    """ValueError unless ``H`` is a number of horizons the forecasts serve."""
+    if isinstance(H, bool) or not isinstance(H, (int, np.integer)) or not 1 <= H <= ARHMM_MAX_HORIZONS:
+        raise ValueError('%s: %r horizons (an int from 1 to %d is served)' % (who, H, ARHMM_MAX_HORIZONS))
+
+
+def arhmm_forecast_sums(table, offsets, N, weights, lags, out=None):
+    """The sums of the exact multi-step forecasts of an ARHMM on the fp32 DEVICE ``table`` (n, D): a float64 device
+    tensor (H, S, D, 5) (``bn_arhmm_forecast_sums``, csrc/arhmm.hip).  Origin row t of a trial, ``t - beg >= max(lags,
+    1)``, forecasts ``x_{t+h-1}`` as ``sum_k weights[t, k] N[h - 1, k] phi_t`` for every h with ``t + h - 1 < end``;
+    over those pairs, per horizon, trial and dimension: the count, ``sum y``, ``sum y^2``, ``sum (y - xhat)^2`` and
+    ``sum (y - x_{t-1})^2``.  ``N`` float64 (H, K, D, 1 + lags D) (``models.arhmm.ARHMM.forecast_maps``; host arrays
+    are uploaded), ``weights`` float64 DEVICE (n, K).  The forecasts themselves never reach memory."""
+    n, D, ld = _column_table('arhmm_forecast_sums', table)
+    L = int(lags)
+    if not torch.is_tensor(N) and np.ndim(N) != 4 or torch.is_tensor(N) and N.dim() != 4:
+        raise ValueError('arhmm_forecast_sums: expected N float64 (H, K, D, 1 + lags D)')
+    H, K = int(N.shape[0]), int(N.shape[1])
+    check_arhmm_dims('arhmm_forecast_sums', D, L, K)
+    check_arhmm_horizons('arhmm_forecast_sums', H)
+    dev = table.device
+    N = _f64_operand('arhmm_forecast_sums', 'N', N, (H, K, D, 1 + L * D), dev)
+    if not torch.is_tensor(weights) or weights.dim() != 2:
+        raise ValueError('arhmm_forecast_sums: expected weights float64 (n, K) on the device')
+    weights = _f64_operand('arhmm_forecast_sums', 'weights', weights, (n, K), dev)
+    offsets = _trial_offsets('arhmm_forecast_sums', offsets, dev)
+    S = int(offsets.numel()) - 1
+    if out is None:
+        out = torch.zeros((H, S, D, 5), dtype=torch.float64, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.float64 or tuple(out.shape) != (H, S, D, 5) \
+            or out.device != dev or not out.is_contiguous():
+        raise ValueError('arhmm_forecast_sums: expected out float64 (%d, %d, %d, 5) on %s' % (H, S, D, dev))
+    lib = load()
+    nbytes = lib.bn_arhmm_forecast_sums_ws_bytes(n, S, D, L, K, H)
+    if S:
+        _check(lib.bn_arhmm_forecast_sums(table.data_ptr(), ld, offsets.data_ptr(), S, D, L, K, H, n, N.data_ptr(),
+                                          weights.data_ptr(), out.data_ptr(), _arena(dev, nbytes, 'arhmm'), nbytes,
+                                          _stream()), 'bn_arhmm_forecast_sums')
     return out
 
 

@@ -103,6 +103,29 @@
 //                the accumulators, no cross-lane step.  Initial rows get the row's own values, one lane a row.  A NaN
 //                in row t is in the staged rows phi_{t+1} .. phi_{t+L} of its trial and nowhere else, and a row of A
 //                reaches its own row of the product only.
+// Multi-step forecasts (bn_arhmm_forecast_sums): E[x_{t+h-1} | x_0 .. x_{t-1}] = sum_k w_t[k] N_h[k] phi_t, h = 1 .. H,
+// scored in the epilogue; the (n, H, D) forecasts never go to memory.
+// k_arf_plan     the row blocks, none across a trial boundary: trial s has its origin rows beg + max(L, 1) .. end - 1
+//                cut
+//                into blocks of AR_FC_BLOCK_ROWS; first[s] is the exclusive prefix sum of the blocks per trial (one
+//                workgroup, thread i the trials of chunk i, 256 chunk sums added in thread order).
+// k_arf_fold     N (H, K, D, Q) into the B operand bt[j][c], j = k Q + q, c = (h - 1) D + d (the horizons packed, no
+//                padding between them): JP = K Q padded to 16 rows of CP = H D padded to AR_FC_COLS doubles, zeros in
+//                the padding.
+// k_ar_forecast  a workgroup (x, y) takes row block x and the column group y of AR_FC_CT = 4 column tiles (64 columns
+//                (h, d); four horizons at D = 16).  A wave takes 32 origin rows at a time, staged as k_ar_predict
+//                stages
+//                them; the A entry w[k] phi[q] of a k-step is formed ONCE and feeds the 2 x 4 accumulator tiles of the
+//                group, four B loads a k-step.  The group is register-bound: 2 x 4 tiles x 8 VGPRs of accumulators and
+//                5 x 4 x 2 of running sums are 104 registers before any address or operand, and the compiler ends at
+//                238 (two waves a SIMD); eight tiles would pass 256 and leave one.  With four, eight MFMAs follow the
+//                two LDS reads and the multiply of every A entry where k_ar_predict at D = 16 issues two.  The last
+//                group's tiles without a column (H D not a multiple of 64) are skipped, the same for the workgroup.
+//                Epilogue: lane (col, kk) owns column c and the rows kk + 4 r; the target y = x_{t+h-1} and x_{t-1} are
+//                read as fp32 and widened, the five terms formed in float64 and kept only where t + h - 1 < end.  The
+//                lane adds its rows in row order, the four lanes of a column by two exchanges, the two waves through
+//                LDS in wave order: one (columns, 5) partial a block.
+// k_arf_combine  sums[h][s][d][term] = the partials of trial s added in block order; zeros for a trial without blocks.
 // No global atomics; every output element is written exactly once by each kernel that owns it.
 #include <limits.h>
 #include <math.h>
@@ -130,6 +153,14 @@
 #define AR_PR_THREADS 128                   // k_ar_predict: two waves ...
 #define AR_PR_WAVES (AR_PR_THREADS / BN_WAVE)
 #define AR_PR_ROWS 32                       // ... of 32 rows (two row tiles) each
+#define AR_FC_MAX_H 32                      // k_ar_forecast: horizons at most
+#define AR_FC_THREADS 128                   // two waves ...
+#define AR_FC_WAVES (AR_FC_THREADS / BN_WAVE)
+#define AR_FC_ROWS 32                       // ... of 32 origin rows (two row tiles) at a time
+#define AR_FC_BLOCK_ROWS 256                // origin rows of a row block at most, all of one trial
+#define AR_FC_CT 4                          // column tiles of a column group ...
+#define AR_FC_COLS (16 * AR_FC_CT)          // ... and its columns (h, d)
+#define AR_FC_TERMS 5                       // count, sum y, sum y^2, sum (y - xhat)^2, sum (y - x_{t-1})^2
 
 typedef double ar_d4 __attribute__((ext_vector_type(4)));
 
@@ -1212,6 +1243,209 @@ __global__ __launch_bounds__(AR_PR_THREADS) void k_ar_predict(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// multi-step forecasts and their sums
+// first[s] = the row blocks of the trials before s (first[S]: of all); m = max(L, 1) rows of a trial are no origins
+__global__ __launch_bounds__(256) void k_arf_plan(const int* __restrict__ e, int S, int m, int* __restrict__ first) {
+    __shared__ long part[256];
+    const int tid = threadIdx.x;
+    const long per = ((long)S + 255) / 256;
+    const long s0 = tid * per < S ? tid * per : S, s1 = s0 + per < S ? s0 + per : S;
+    long sum = 0;
+    for (long s = s0; s < s1; ++s) {
+        const long no = (long)e[s + 1] - e[s] - m;
+        if (no > 0) sum += (no + AR_FC_BLOCK_ROWS - 1) / AR_FC_BLOCK_ROWS;
+    }
+    part[tid] = sum;
+    __syncthreads();
+    long run = 0;
+    for (int i = 0; i < tid; ++i) run += part[i];
+    for (long s = s0; s < s1; ++s) {
+        first[s] = (int)run;
+        const long no = (long)e[s + 1] - e[s] - m;
+        if (no > 0) run += (no + AR_FC_BLOCK_ROWS - 1) / AR_FC_BLOCK_ROWS;
+    }
+    if (tid == 255) first[S] = (int)run;
+}
+
+// bt[j][c] = N[h][k][d][q] for j = k Q + q < K Q and c = h D + d < H D, zeros in the padding; one thread an element
+__global__ __launch_bounds__(256) void k_arf_fold(const double* __restrict__ N, int D, int Q, int K, int H, int CP,
+                                                  long total, double* __restrict__ bt) {
+    const long o = (long)blockIdx.x * 256 + threadIdx.x;
+    if (o >= total) return;
+    const int j = (int)(o / CP), c = (int)(o - (long)j * CP);
+    const int k = j / Q, q = j - k * Q;
+    const int h = c / D, d = c - h * D;
+    bt[o] = k < K && h < H ? N[(((size_t)h * K + k) * D + d) * Q + q] : 0.0;
+}
+
+__global__ __launch_bounds__(AR_FC_THREADS) void k_ar_forecast(const float* __restrict__ z, int ld,
+                                                               const int* __restrict__ e, int S,
+                                                               const int* __restrict__ first, int D, int L, int K,
+                                                               int H, const double* __restrict__ bt, int CP,
+                                                               const double* __restrict__ w,
+                                                               double* __restrict__ slabs) {
+    extern __shared__ double arf_lds[];                    // a wave's 32 rows of phi and of weights, as k_ar_predict's
+    __shared__ double red[AR_FC_COLS * AR_FC_TERMS];
+    const int blk = blockIdx.x;
+    if (blk >= first[S]) return;                           // (the grid is the host's upper bound)
+    int s;
+    {
+        int lo = 0, hi = S - 1;                            // the first trial whose blocks end after blk
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (first[mid + 1] > blk) hi = mid; else lo = mid + 1;
+        }
+        s = lo;
+    }
+    const int tid = threadIdx.x, lane = tid & (BN_WAVE - 1), wave = tid / BN_WAVE;
+    const int kk = lane >> 4, col = lane & 15;
+    const int Q = 1 + L * D, LW = arp_lw(Q), WW = K + 1, JS = (K * Q + 3) >> 2, HD = H * D;
+    const long end = e[s + 1];
+    const long b0 = (long)e[s] + (L > 1 ? L : 1) + (long)(blk - first[s]) * AR_FC_BLOCK_ROWS;
+    const long b1 = b0 + AR_FC_BLOCK_ROWS < end ? b0 + AR_FC_BLOCK_ROWS : end;        // the block's origin rows
+    double* st = arf_lds + (size_t)wave * AR_FC_ROWS * (LW + WW);
+    double* wg = st + AR_FC_ROWS * LW;
+    const float rq = 1.0f / (float)Q;
+    const int c0 = blockIdx.y * AR_FC_COLS;
+    const int nct = (HD - c0 + 15) / 16;                   // the group's tiles with a column in them (the last group)
+
+    int hh[AR_FC_CT], dd[AR_FC_CT];                        // the lane's column of every tile: horizon - 1, dimension
+    bool cl[AR_FC_CT];
+#pragma unroll
+    for (int ct = 0; ct < AR_FC_CT; ++ct) {
+        const int c = c0 + ct * 16 + col;
+        cl[ct] = c < HD;
+        hh[ct] = cl[ct] ? c / D : 0;
+        dd[ct] = cl[ct] ? c - hh[ct] * D : 0;
+    }
+    double sums[AR_FC_CT][AR_FC_TERMS];
+#pragma unroll
+    for (int ct = 0; ct < AR_FC_CT; ++ct)
+#pragma unroll
+        for (int i = 0; i < AR_FC_TERMS; ++i) sums[ct][i] = 0.0;
+
+    // the same number of rounds for both waves (the barrier); a wave without rows in a round has nothing to add
+    for (long base = b0; base < b1; base += AR_FC_WAVES * AR_FC_ROWS) {
+        const long row0 = base + (long)wave * AR_FC_ROWS;
+        __syncthreads();
+        for (int idx = lane; idx < AR_FC_ROWS * Q; idx += BN_WAVE) {
+            const int r = idx / Q, q = idx - r * Q;
+            const long row = row0 + r;
+            double v = 0.0;
+            if (row < b1) {
+                if (q == 0) {
+                    v = 1.0;
+                } else {
+                    const int lag = (q - 1) / D, j = q - 1 - lag * D;
+                    v = (double)z[(size_t)(row - 1 - lag) * ld + j];
+                }
+            }
+            st[r * LW + q] = v;
+        }
+        for (int idx = lane; idx < AR_FC_ROWS * K; idx += BN_WAVE) {
+            const int r = idx / K, k = idx - r * K;
+            const long row = row0 + r;
+            wg[r * WW + k] = row < b1 ? w[(size_t)row * K + k] : 0.0;
+        }
+        __syncthreads();
+        if (row0 >= b1) continue;
+
+        ar_d4 acc[AR_FC_CT][2];
+#pragma unroll
+        for (int ct = 0; ct < AR_FC_CT; ++ct) {
+            acc[ct][0] = ar_d4{0.0, 0.0, 0.0, 0.0};
+            acc[ct][1] = ar_d4{0.0, 0.0, 0.0, 0.0};
+        }
+        const double* bp = bt + (size_t)kk * CP + c0 + col;    // row j = 4 step + kk of the folded operand
+        // A as in k_ar_predict (k = j / Q by the fp32 reciprocal, exact for j < 2048), built once a k-step for the
+        // 2 x AR_FC_CT tiles; bt's rows are padded to 16 and its columns to AR_FC_COLS with zeros: no bounds
+        for (int s4 = 0; s4 < JS; s4 += 4) {
+#pragma unroll
+            for (int step = s4; step < s4 + 4; ++step) {
+                const int j = 4 * step + kk;
+                const int k = (int)(((float)j + 0.5f) * rq), q = j - k * Q;
+                const bool live = k < K;
+                const int kc = live ? k : 0, qc = live ? q : 0;
+                const double a0 = live ? wg[col * WW + kc] * st[col * LW + qc] : 0.0;
+                const double a1 = live ? wg[(16 + col) * WW + kc] * st[(16 + col) * LW + qc] : 0.0;
+                double b[AR_FC_CT];
+#pragma unroll
+                for (int ct = 0; ct < AR_FC_CT; ++ct) b[ct] = bp[(size_t)step * 4 * CP + ct * 16];
+#pragma unroll
+                for (int ct = 0; ct < AR_FC_CT; ++ct)
+                    if (ct < nct) {                        // (the same for the whole workgroup)
+                        acc[ct][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b[ct], acc[ct][0], 0, 0, 0);
+                        acc[ct][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b[ct], acc[ct][1], 0, 0, 0);
+                    }
+            }
+        }
+        // C/D of the f64 MFMA: column lane & 15, row (lane >> 4) + 4 * reg.  The pair (t, h) counts iff t is an origin
+        // row of the block and t + h - 1 < end; nothing is read for a pair that does not count
+#pragma unroll
+        for (int ct = 0; ct < AR_FC_CT; ++ct) {
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const long row = row0 + half * 16 + kk + 4 * r;
+                    if (cl[ct] && row < b1 && row + hh[ct] < end) {
+                        const double y = (double)z[(size_t)(row + hh[ct]) * ld + dd[ct]];
+                        const double pv = (double)z[(size_t)(row - 1) * ld + dd[ct]];
+                        const double em = y - acc[ct][half][r], ep = y - pv;
+                        sums[ct][0] += 1.0;
+                        sums[ct][1] += y;
+                        sums[ct][2] += y * y;
+                        sums[ct][3] += em * em;
+                        sums[ct][4] += ep * ep;
+                    }
+                }
+            }
+        }
+    }
+    // the four lanes of a column: (kk 0 + kk 1) + (kk 2 + kk 3) in every one of them
+#pragma unroll
+    for (int ct = 0; ct < AR_FC_CT; ++ct)
+#pragma unroll
+        for (int i = 0; i < AR_FC_TERMS; ++i) {
+            double v = sums[ct][i];
+            v += __shfl_xor(v, 16);
+            v += __shfl_xor(v, 32);
+            sums[ct][i] = v;
+        }
+    __syncthreads();
+    if (wave == 1 && kk == 0)
+#pragma unroll
+        for (int ct = 0; ct < AR_FC_CT; ++ct)
+#pragma unroll
+            for (int i = 0; i < AR_FC_TERMS; ++i) red[(ct * 16 + col) * AR_FC_TERMS + i] = sums[ct][i];
+    __syncthreads();
+    if (wave == 0 && kk == 0)
+#pragma unroll
+        for (int ct = 0; ct < AR_FC_CT; ++ct)
+            if (cl[ct]) {
+                double* o = slabs + ((size_t)blk * HD + c0 + ct * 16 + col) * AR_FC_TERMS;
+#pragma unroll
+                for (int i = 0; i < AR_FC_TERMS; ++i) o[i] = sums[ct][i] + red[(ct * 16 + col) * AR_FC_TERMS + i];
+            }
+}
+
+// sums[h][s][d][i] = the partials of trial s's row blocks added in block order; one thread an element
+__global__ __launch_bounds__(256) void k_arf_combine(const double* __restrict__ slabs, const int* __restrict__ first,
+                                                     int S, int D, int H, size_t total, double* __restrict__ sums) {
+    const size_t o = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= total) return;
+    const int i = (int)(o % AR_FC_TERMS);
+    size_t rest = o / AR_FC_TERMS;
+    const int d = (int)(rest % D);
+    rest /= D;
+    const int s = (int)(rest % S), h = (int)(rest / S);
+    double sum = 0.0;
+    const size_t c = (size_t)h * D + d, HD = (size_t)H * D;
+    for (int b = first[s]; b < first[s + 1]; ++b) sum += slabs[((size_t)b * HD + c) * AR_FC_TERMS + i];
+    sums[o] = sum;
+}
+
+// ------------------------------------------------------------------------------------------------------------
 bool bn_arhmm_ok(int n, int S, int D, int L, int K) {
     return n >= 0 && S >= 0 && S < INT32_MAX && ar_dims_ok(D, L, K);
 }
@@ -1565,6 +1799,56 @@ int bn_launch_arhmm_predict(const float* z, int ld, const long long* offsets, in
     const size_t lds = (size_t)AR_PR_WAVES * AR_PR_ROWS * (arp_lw(1 + L * D) + K + 1) * sizeof(double);
     hipLaunchKernelGGL(k_ar_predict, dim3((unsigned)(((long)n + per - 1) / per)), dim3(AR_PR_THREADS), lds, st, z, ld,
                        kind, D, L, K, n, (const double*)wt, DP, w, xhat);
+    BN_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- multi-step forecasts and their sums
+static bool arf_ok(int n, int S, int D, int L, int K, int H) {
+    return bn_arhmm_ok(n, S, D, L, K) && H >= 1 && H <= AR_FC_MAX_H;
+}
+static int arf_cp(int D, int H) { return (H * D + AR_FC_COLS - 1) / AR_FC_COLS * AR_FC_COLS; }
+// row blocks at most: every trial with origin rows ends with one block that may not be full, and a block holds an
+// origin row at least
+static long arf_blocks(int n, int S) {
+    const long by_rows = (long)n / AR_FC_BLOCK_ROWS + S;
+    return by_rows < n ? by_rows : n;
+}
+
+size_t bn_arhmm_forecast_sums_ws_bytes_impl(int n, int S, int D, int L, int K, int H) {
+    if (!arf_ok(n, S, D, L, K, H)) return 0;
+    return 2 * ar_offsets_bytes(S) + (size_t)arp_jp(D, L, K) * arf_cp(D, H) * sizeof(double) +
+           (size_t)arf_blocks(n, S) * H * D * AR_FC_TERMS * sizeof(double);
+}
+
+int bn_launch_arhmm_forecast_sums(const float* z, int ld, const long long* offsets, int S, int D, int L, int K, int H,
+                                  int n, const double* N, const double* w, double* sums, void* ws, hipStream_t st) {
+    if (!arf_ok(n, S, D, L, K, H)) return BN_E_SHAPE;
+    if (S == 0) return 0;
+    int* e = reinterpret_cast<int*>(ws);
+    int* first = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + ar_offsets_bytes(S));
+    double* bt = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + 2 * ar_offsets_bytes(S));
+    const int CP = arf_cp(D, H), JP = arp_jp(D, L, K);
+    double* slabs = bt + (size_t)JP * CP;
+    const int rc = bn_launch_segment_offsets(offsets, S + 1, n, e, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_arf_plan, dim3(1), dim3(256), 0, st, (const int*)e, S, L > 1 ? L : 1, first);
+    BN_LAUNCH_CHECK();
+    const long blocks = arf_blocks(n, S);
+    if (blocks) {
+        const long total = (long)JP * CP;
+        hipLaunchKernelGGL(k_arf_fold, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, N, D, 1 + L * D, K, H,
+                           CP, total, bt);
+        BN_LAUNCH_CHECK();
+        // LDS a workgroup: k_ar_predict's, at most 48.5 KiB, and 2.5 KiB of partial sums
+        const size_t lds = (size_t)AR_FC_WAVES * AR_FC_ROWS * (arp_lw(1 + L * D) + K + 1) * sizeof(double);
+        hipLaunchKernelGGL(k_ar_forecast, dim3((unsigned)blocks, (unsigned)(CP / AR_FC_COLS)), dim3(AR_FC_THREADS), lds,
+                           st, z, ld, (const int*)e, S, (const int*)first, D, L, K, H, (const double*)bt, CP, w, slabs);
+        BN_LAUNCH_CHECK();
+    }
+    const size_t total = (size_t)H * S * D * AR_FC_TERMS;
+    hipLaunchKernelGGL(k_arf_combine, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)slabs,
+                       (const int*)first, S, D, H, total, sums);
     BN_LAUNCH_CHECK();
     return 0;
 }

@@ -194,6 +194,11 @@ int bn_launch_hmm_predictive(const double* ll, const long long* offsets, int S, 
                              const double* logpi0, double* w, void* ws, hipStream_t st);
 int bn_launch_arhmm_predict(const float* z, int ld, const long long* offsets, int S, int D, int L, int K, int n,
                             const double* W, const double* w, double* xhat, void* ws, hipStream_t st);
+// ... and exact multi-step forecasts sum_k w_t[k] N_h[k] phi_t, h = 1 .. H, reduced to five sums per horizon, trial and
+// dimension in the launch that forms them
+size_t bn_arhmm_forecast_sums_ws_bytes_impl(int n, int S, int D, int L, int K, int H);
+int bn_launch_arhmm_forecast_sums(const float* z, int ld, const long long* offsets, int S, int D, int L, int K, int H,
+                                  int n, const double* N, const double* w, double* sums, void* ws, hipStream_t st);
 
 // state_runs.hip: the runs (trial, beg, end, state) of an int32 state table cut into trials, in table order, with
 // the frames per state and the in-trial transition counts

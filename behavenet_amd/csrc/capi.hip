@@ -2293,6 +2293,23 @@ extern "C" int bn_arhmm_predict(const float* z, int ld, const long long* offsets
     return bn_launch_arhmm_predict(z, ld, offsets, S, D, L, K, n, W, w, xhat, ws, (hipStream_t)stream);
 }
 
+// ... and multi-step forecasts with their sums
+extern "C" size_t bn_arhmm_forecast_sums_ws_bytes(int n, int S, int D, int L, int K, int H) {
+    return bn_arhmm_forecast_sums_ws_bytes_impl(n, S, D, L, K, H);
+}
+
+extern "C" int bn_arhmm_forecast_sums(const float* z, int ld, const long long* offsets, int S, int D, int L, int K,
+                                      int H, int n, const double* N, const double* w, double* sums, void* ws,
+                                      size_t ws_bytes, bn_stream_t stream) {
+    if (!bn_arhmm_ok(n, S, D, L, K) || H < 1 || H > 32 || ld < D) return BN_E_SHAPE;
+    if (!z || !offsets || !N || !w || !sums || !ws) return BN_E_BADARG;
+    if (((uintptr_t)z & 3) || ((uintptr_t)offsets & 7) || ((uintptr_t)N & 7) || ((uintptr_t)w & 7) ||
+        ((uintptr_t)sums & 7) || !aligned16(ws))
+        return BN_E_SHAPE;
+    if (ws_bytes < bn_arhmm_forecast_sums_ws_bytes_impl(n, S, D, L, K, H)) return BN_E_SHAPE;
+    return bn_launch_arhmm_forecast_sums(z, ld, offsets, S, D, L, K, H, n, N, w, sums, ws, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // The runs of a state table, per trial and in table order, with the frames per state and the transition counts
 // (state_runs.hip): what the syllable movies and the state-duration statistics are made from.

@@ -2770,6 +2770,102 @@ def export_arhmm_predictions(hparams, data_generator, arhmm, model=None, dtype='
     return filename
 
 
+# ------------------------------------------------------------------------------------------ ARHMM forecasts
+ARHMM_FORECASTS_FILE = 'arhmm_forecasts.csv'
+
+
+def summarise_forecast_sums(sums, min_valid=10):
+    """Forecast scores per horizon from the sums ``ARHMM.forecast_sums`` returns, ``(2, H, S, D, 4)``, in numpy float64
+    on the host: ``summarise_prediction_sums`` a horizon, stacked -- ``'n'``, ``'mse'``, ``'r2'``,
+    ``'mse_persistence'``, ``'r2_persistence'``, each ``(H, S, D)``; ``'pooled'`` with the same five ``(H, D)`` and
+    ``'mse_all'``, ``'r2_all'``, ``'mse_persistence_all'``, ``'r2_persistence_all'`` ``(H,)`` -- and
+    ``'horizon_of_no_gain'``: the first horizon (from 1) at which the pooled ``mse_all`` is not below the pooled
+    ``mse_persistence_all`` (a NaN is not below), or None if the model wins at every horizon served."""
+    sums = np.asarray(sums, dtype=np.float64)
+    if sums.ndim != 5 or sums.shape[0] != 2 or sums.shape[4] != 4:
+        raise ValueError('summarise_forecast_sums: expected sums (2, H, S, D, 4), got %s' % (tuple(sums.shape),))
+    per = [summarise_prediction_sums(sums[:, h], min_valid) for h in range(sums.shape[1])]
+    out = {key: np.stack([p[key] for p in per]) for key in ('n',) + _PREDICTION_MEASURES}
+    out['pooled'] = {key: np.stack([np.asarray(p['pooled'][key]) for p in per]) for key in per[0]['pooled']}
+    out['horizon_of_no_gain'] = None
+    for h, (mse, base) in enumerate(zip(out['pooled']['mse_all'], out['pooled']['mse_persistence_all'])):
+        if not mse < base:
+            out['horizon_of_no_gain'] = h + 1
+            break
+    return out
+
+
+def arhmm_forecasts(data_generator, model, arhmm, horizons=10, dtype='test', sess_idx=None, data_key='ae_latents'):
+    """How many frames ahead a fitted ARHMM still beats ``x_{t-1}``: per horizon ``h = 1 .. horizons``, trial and
+    dimension the mean squared error and R^2 of the exact forecast ``E[x_{t+h-1} | x_0 .. x_{t-1}]`` and of the
+    persistence baseline ``x_{t-1}`` over the origin rows ``t >= max(lags, 1)`` of every trial with ``t + h - 1``
+    still in the trial.  The trials are walked and encoded ONCE as ``arhmm_predictions`` walks and encodes them;
+    ``ARHMM.forecast_sums`` scores all horizons in one launch and ``(2, H, S, D, 4)`` doubles cross to the host.
+    -> ``summarise_forecast_sums``'s dict plus ``'session'`` and ``'trial'``, int arrays ``(S,)`` in the table's
+    order, and ``'sums'``.  Under ``torch.distributed`` rank 0 works and the other ranks return None."""
+    who = 'arhmm_forecasts'
+    dtypes = _splits(who, dtype)
+    if data_key == 'ae_latents':
+        _export_setup(model)
+    if bdist.world_size() > 1 and bdist.rank() != 0:
+        return None
+    wanted = _wanted_sessions(who, data_generator, sess_idx)
+    parts = _arhmm_trials(who, data_generator, model, data_key, dtypes, wanted)
+    idxs = [ds.batch_idxs for ds in data_generator.datasets]
+    table, offsets, sessions, trials = _arhmm_split(parts, _corr_trial_order(idxs, dtypes, wanted))
+    if table is None:
+        raise ValueError('%s: the sessions %s have no %s frames' % (who, sorted(wanted), ' or '.join(dtypes)))
+    sums = arhmm.forecast_sums(table, offsets, horizons)
+    out = summarise_forecast_sums(sums)
+    out.update({'session': sessions, 'trial': trials, 'sums': sums})
+    return out
+
+
+def export_arhmm_forecasts(hparams, data_generator, arhmm, model=None, horizons=10, dtype='test', filename=None):
+    """``arhmm_forecasts`` as a table next to ``arhmm_predictions.csv``: ``arhmm_forecasts.csv`` under
+    ``hparams['expt_dir']/version_<hparams['version']>`` (or ``filename``), one row per (horizon, trial, dimension)
+    with the columns ``Horizon, Session, Trial, Dim, N, MSE, R2, MSE_persistence, R2_persistence``; a NaN is an empty
+    field.  Latents or labels by ``hparams['model_class']`` as ``export_states`` chooses.  -> the path (None on the
+    ranks other than 0)."""
+    data_key = 'labels' if str(hparams.get('model_class', 'arhmm')).find('label') > -1 else 'ae_latents'
+    scores = arhmm_forecasts(data_generator, model, arhmm, horizons=horizons, dtype=dtype, data_key=data_key)
+    if scores is None:
+        return None
+    if filename is None:
+        filename = os.path.join(hparams['expt_dir'], 'version_%i' % hparams['version'], ARHMM_FORECASTS_FILE)
+    write_forecasts_csv(filename, scores)
+    return filename
+
+
+def write_forecasts_csv(filename, scores):
+    """The rows of ``export_arhmm_forecasts`` from ``arhmm_forecasts``'s dict."""
+    import csv
+
+    def field(v):
+        return '' if np.isnan(v) else repr(float(v))
+    with open(filename, 'w', newline='') as f:
+        writer = csv.writer(f, lineterminator='\n')
+        writer.writerow(['Horizon', 'Session', 'Trial', 'Dim', 'N', 'MSE', 'R2', 'MSE_persistence', 'R2_persistence'])
+        for h in range(scores['n'].shape[0]):
+            for k, (sess, trial) in enumerate(zip(scores['session'], scores['trial'])):
+                for d in range(scores['n'].shape[2]):
+                    writer.writerow([h + 1, int(sess), int(trial), d, int(scores['n'][h, k, d])]
+                                    + [field(scores[name][h, k, d]) for name in _PREDICTION_MEASURES])
+
+
+def check_export_arhmm_forecasts(who, kwargs, export_arhmm=True):
+    """``hparams['export_arhmm_forecasts']``: a dict with ``horizons`` (an int from 1 to 32) and, if wanted, ``dtype``;
+    it scores the model that ``hparams['export_arhmm']`` fits, so that key has to be there (``export_arhmm``: its
+    value)."""
+    from behavenet_amd._hip import check_arhmm_horizons
+    if not isinstance(kwargs, dict) or 'horizons' not in kwargs or not set(kwargs) <= {'horizons', 'dtype'}:
+        raise ValueError("%s: expected a dict with horizons and, if wanted, dtype, got %r" % (who, kwargs))
+    check_arhmm_horizons(who, kwargs['horizons'])
+    _splits(who, kwargs.get('dtype', 'test'))
+    if not export_arhmm:
+        raise ValueError("%s scores the model that hparams['export_arhmm'] fits, and that key is not set" % who)
+
+
 # ------------------------------------------------------------------------------------------ ARHMM samples
 def sample_arhmm(data_generator, model, arhmm, n_samples=50, conditional=True, dtype='test', sess_idx=None,
                  data_key='ae_latents', seed=0):

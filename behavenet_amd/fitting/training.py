@@ -599,6 +599,11 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
         # (a state count or a transition type that is not served: an error now, not after the last epoch)
         from behavenet_amd.fitting.eval import check_export_arhmm
         check_export_arhmm("fit: hparams['export_arhmm']", hparams['export_arhmm'])
+    if method == 'ae' and hparams.get('export_arhmm_forecasts'):
+        # (a bad dict, too many horizons or no model to score: an error now, as above)
+        from behavenet_amd.fitting.eval import check_export_arhmm_forecasts
+        check_export_arhmm_forecasts("fit: hparams['export_arhmm_forecasts']", hparams['export_arhmm_forecasts'],
+                                     hparams.get('export_arhmm'))
     if method == 'ae' and hparams.get('export_arhmm_grid'):
         # (a bad dict, a configuration that is not served or a broken limit: an error now, as above)
         from behavenet_amd.fitting.eval import check_export_arhmm_grid
@@ -871,7 +876,16 @@ def _fit(hparams, model, data_generator, exp, method='ae', optimizer=None, write
         if is_main:
             print('fitting an ARHMM on the latents and exporting its states')
         from behavenet_amd.fitting.eval import export_arhmm
-        export_arhmm(data_generator, best_val_model, **hparams['export_arhmm'])
+        fitted = export_arhmm(data_generator, best_val_model, **hparams['export_arhmm'])
+        if hparams.get('export_arhmm_forecasts'):
+            if is_main:
+                print('exporting the forecast scores of the ARHMM per horizon')
+            from behavenet_amd.fitting.eval import export_arhmm_forecasts
+            labels = hparams['export_arhmm'].get('data_key', 'ae_latents') == 'labels'
+            export_arhmm_forecasts({'expt_dir': best_val_model.hparams['expt_dir'], 'version': best_val_model.version,
+                                    'model_class': 'arhmm-labels' if labels else 'arhmm'}, data_generator,
+                                   fitted[0] if fitted is not None else None, model=best_val_model,
+                                   **hparams['export_arhmm_forecasts'])
     if method == 'ae' and hparams.get('export_arhmm_grid'):
         if is_main:
             print('fitting a grid of ARHMMs on the latents and exporting its selection table and states')

@@ -11,7 +11,8 @@ Host side: numpy float64 only -- the M-step, the fold of the parameters for the 
 iteration): ``bn_arhmm_loglik`` -> ``bn_hmm_forward_backward`` -> ``bn_arhmm_moments`` on one fp32 table that holds
 every trial, one transfer of ``K (P^2 + K + 1)`` doubles.  A fitted model predicts the next latent
 (``table_predictions``, ``prediction_sums``, ``predict``, ``smooth``): ``bn_hmm_predictive`` or the posterior marginals
-for the state weights, ``bn_arhmm_predict`` for the mixture of the states' regressions.
+for the state weights, ``bn_arhmm_predict`` for the mixture of the states' regressions; and the latents up to 32 frames
+ahead (``forecast_maps``, ``forecast_sums``, ``table_forecast``, ``forecast``): ``bn_arhmm_forecast_sums``.
 
 Model, with ``x_t`` the row, ``L = lags`` and state ``k`` at time ``t``:
 
@@ -405,6 +406,102 @@ class ARHMM(object):
     def smooth(self, x):
         """The posterior-weighted mean of the observation model for one trial (the library's ``smooth``)."""
         return self.predict(x, 'smoothed')
+
+    # ------------------------------------------------------------------------------------------------------
+    # exact multi-step forecasts (bn_arhmm_forecast_sums; bn_arhmm_predict for one horizon)
+    # ------------------------------------------------------------------------------------------------------
+    def forecast_maps(self, H):
+        """``N (H, K, D, Q)``, ``Q = 1 + L D``, host float64: ``E[x_{t+h-1} | z_t = k, phi_t] = N[h - 1, k] phi_t``
+        with ``phi_t = (1, x_{t-1}, .., x_{t-L})``, so that the exact h-step conditional mean is
+        ``sum_k w_t[k] N[h - 1, k] phi_t`` with the causal weights ``w_t``.  Given a state path the mean is an affine
+        recursion in ``phi_t`` and the path probabilities given ``z_t`` do not depend on ``phi_t``, so the maps are
+        ``B_1[k][k'] = delta_kk' C_k``, ``B_{h+1}[k][k''] = C_k'' sum_k' P[k'][k''] B_h[k][k']`` with ``C_k`` the
+        (Q, Q) companion matrix of state k (row 0 ``e_0``, rows 1 .. D ``[b_k | A_k]``, the lag blocks shifted down
+        below) and ``N_h[k]`` rows 1 .. D of ``sum_k' B_h[k][k']``.  ``N[0]`` is ``generative()[0]`` element for
+        element.  Without lags ``N_h[k] = sum_k' (P^{h-1})[k][k'] b_k'``.  The entries grow like the spectral radius
+        of the ``A_k`` to the power h: a map that is not finite is a ValueError that names the horizon."""
+        from behavenet_amd._hip import check_arhmm_horizons
+        check_arhmm_horizons('ARHMM.forecast_maps', H)
+        H, K, D, L = int(H), self.K, self.D, self.lags
+        Q = 1 + L * D
+        W = np.ascontiguousarray(np.concatenate([self.bs[:, :, None], self.As], axis=2).astype(np.float64))
+        P = np.exp(np.asarray(self.log_Ps, dtype=np.float64))
+        N = np.zeros((H, K, D, Q))
+        N[0] = W
+        with np.errstate(all='ignore'):
+            if L == 0:
+                reach = np.eye(K)                               # P^{h-1}
+                for h in range(1, H):
+                    reach = reach @ P
+                    N[h, :, :, 0] = reach @ W[:, :, 0]
+            else:
+                C = np.zeros((K, Q, Q))
+                C[:, 0, 0] = 1.0
+                C[:, 1:1 + D, :] = W
+                for i in range((L - 1) * D):
+                    C[:, 1 + D + i, 1 + i] = 1.0
+                B = np.zeros((K, K, Q, Q))
+                B[np.arange(K), np.arange(K)] = C
+                for h in range(1, H):
+                    # sum_k' P[k'][k''] B[k][k'] for all (k, k'') as one product, then C_k'' from the left (batched)
+                    B = np.matmul(C[None], np.matmul(P.T[None], B.reshape(K, K, Q * Q)).reshape(K, K, Q, Q))
+                    N[h] = B.sum(axis=1)[:, 1:1 + D, :]
+        for h in range(H):
+            if not np.all(np.isfinite(N[h])):
+                raise ValueError('ARHMM.forecast_maps: the map of horizon %d is not finite' % (h + 1))
+        return N
+
+    def forecast_sums(self, table, offsets, horizons=10, weights='predictive'):
+        """The sums behind R^2 per horizon: a float64 host array ``(2, H, S, D, 4)``, ``[0]`` the model's exact h-step
+        forecast ``E[x_{t+h-1} | x_0 .. x_{t-1}]``, ``[1]`` the persistence baseline ``x_{t-1}``, the last axis that
+        of ``prediction_sums`` (count, ``sum y``, ``sum y^2``, ``sum (y - pred)^2`` with ``y = x_{t+h-1}``), over the
+        origin rows ``t - beg >= max(lags, 1)`` with ``t + h - 1`` inside the trial.  The log-likelihoods, the causal
+        weights and ONE launch for all horizons, scored in float64 in its epilogue (the forecasts are never written),
+        then one transfer.  Only the causal weights are served: smoothed weights have seen the rows being forecast."""
+        from behavenet_amd import _hip
+        if weights != 'predictive':
+            raise ValueError('ARHMM.forecast_sums: weights %r are not served (predictive are: smoothed weights have '
+                             'seen the rows that are forecast)' % (weights,))
+        N = self.forecast_maps(horizons)
+        w = self.table_weights(table, offsets, 'predictive')
+        five = _hip.arhmm_forecast_sums(table, self._offsets_d(table, offsets), N, w, self.lags).cpu().numpy()
+        return np.stack([five[..., :4], five[..., [0, 1, 2, 4]]])
+
+    def table_forecast(self, table, offsets, horizon):
+        """``(xhat, valid)`` aligned with the TARGET row, device tensors float64 (n, D) and bool (n,): row t holds
+        the forecast of ``x_t`` made ``horizon`` steps back, from the history before row ``t - horizon + 1``.  A row
+        with no such origin in its trial (``t - beg < max(lags, 1) + horizon - 1``) holds its own values and is not
+        valid; zeros outside the trials.  The unfused route: ``bn_arhmm_predict`` with the map of this horizon in
+        place of ``[b_k | A_k]``, then a shift inside the trials -- what ``real_vs_sampled_movie`` gets laid beside the
+        real latents."""
+        import torch
+        from behavenet_amd import _hip
+        N = self.forecast_maps(horizon)[-1]
+        back = int(horizon) - 1
+        w = self.table_weights(table, offsets, 'predictive')
+        offsets_d = self._offsets_d(table, offsets)
+        at_origin = _hip.arhmm_predict(table, offsets_d, N, w, self.lags)
+        n = int(table.shape[0])
+        e = offsets_d.clamp(0, n)
+        one = torch.ones_like(e[:-1], dtype=torch.int32)
+
+        def rows_from(beg):                                 # the rows [beg[s], e[s + 1]) of every trial
+            steps = torch.zeros((n + 1,), dtype=torch.int32, device=table.device)
+            steps.index_add_(0, beg, one)
+            steps.index_add_(0, torch.maximum(e[1:], beg), -one)
+            return steps.cumsum(0)[:n] > 0
+        inside = rows_from(e[:-1])
+        valid = rows_from(torch.minimum(e[:-1] + max(self.lags, 1) + back, e[1:]))
+        xhat = torch.zeros((n, self.D), dtype=torch.float64, device=table.device)
+        xhat[inside] = table[inside].to(torch.float64)
+        rows = valid.nonzero()[:, 0]
+        xhat[rows] = at_origin[rows - back]
+        return xhat, valid
+
+    def forecast(self, x, horizon):
+        """``table_forecast`` for ONE host trial (T, D): a float64 host array (T, D)."""
+        table, offsets = self.as_table(x)
+        return self.table_forecast(table, offsets, horizon)[0].cpu().numpy()
 
     # ------------------------------------------------------------------------------------------------------
     # the generative process (bn_arhmm_sample)

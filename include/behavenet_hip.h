@@ -943,6 +943,28 @@ size_t bn_arhmm_predict_ws_bytes(int n, int S, int D, int L, int K);
 int bn_arhmm_predict(const float* z, int ld, const long long* offsets, int S, int D, int L, int K, int n,
                      const double* W, const double* w, double* xhat, void* ws, size_t ws_bytes, bn_stream_t stream);
 
+/* Exact multi-step forecasts of the same model and their sums.  Origin row t of a trial forecasts the rows
+ * t .. t + H - 1 of its trial from the history before t:  xhat_{t,h} = E[x_{t+h-1} | x_0 .. x_{t-1}]
+ * = sum_k w_t[k] N_h[k] phi_t,  phi_t = (1, x_{t-1}, .., x_{t-L}), with N: (H, K, D, 1 + L D) the forecast maps
+ * (N_1[k] = [b_k | A_k]; models/arhmm.py forecast_maps) and w: (n, K) the causal weights of bn_hmm_predictive.  The
+ * pair
+ * (t, h) counts iff t - beg >= max(L, 1) and t + h - 1 < end.
+ * -> sums (H, S, D, 5): per horizon, trial and dimension over the pairs that count, with y = x_{t+h-1}: the count,
+ * sum y, sum y^2, sum (y - xhat_{t,h})^2 and sum (y - x_{t-1})^2 (the h-step persistence baseline).  The forecasts
+ * themselves are not written.  H <= 32; the other limits, alignment and error rules as above.  The
+ * (n x K Q) (K Q x H D) product on v_mfma_f64_16x16x4_f64; the targets are widened and the five terms formed in
+ * float64.
+ * Row blocks of at most 256 origin rows never cross a trial; a block's rows are added in a fixed order and a trial's
+ * blocks in block order, no atomics: the same bits on every call and for every ld.  Rows outside [e[0], e[S]) are
+ * never read, and w is read for origin rows only.  A NaN or Inf in a row of z or of w makes sums of its own trial
+ * non-finite and touches no other trial.  A trial without a pair gets zeros.  ws: bn_arhmm_forecast_sums_ws_bytes
+ * bytes (the offsets, the block plan, N as a padded operand and one (H, D, 5) partial a row block: (n / 256 + S) of
+ * them at most); 0 for sizes that are not served.  BN_E_SHAPE also for ld < D. */
+size_t bn_arhmm_forecast_sums_ws_bytes(int n, int S, int D, int L, int K, int H);
+int bn_arhmm_forecast_sums(const float* z, int ld, const long long* offsets, int S, int D, int L, int K, int H, int n,
+                           const double* N, const double* w, double* sums, void* ws, size_t ws_bytes,
+                           bn_stream_t stream);
+
 /* The runs of a table of discrete states (get_discrete_chunks / get_state_durations of plotting/arhmm_utils.py:24-99,
  * which pad and difference every trial on the host): states int32 (n), the output of bn_hmm_viterbi; offsets int64
  * (S + 1) made safe as above (clamped into [0, n], ascending), empty trials allowed; rows outside [e[0], e[S]) are
