@@ -16,6 +16,8 @@ under ``torch.distributed`` shards trials round-robin over ranks and gathers on 
 """
 
 import contextlib
+import csv
+import inspect
 import os
 import pickle
 
@@ -237,7 +239,6 @@ def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn=None,
     # generators that can be told to pass over a trial (this package's) are asked not to read,
     # copy or convert the other ranks' trials -- round 4 fetched every trial on every rank -- and to
     # hand out stored uint8 frames as they are (the first conv layer converts in flight)
-    import inspect
     try:
         can_skip = 'skip' in inspect.signature(data_generator.next_batch).parameters
     except (TypeError, ValueError):
@@ -311,18 +312,39 @@ def _export_per_trial(who, data_generator, model, on_device_fn, on_host_fn=None,
     return results
 
 
-def _session_filename(model, dataset, filename, suffix):
-    """``filename``, or ``<lab>_<expt>_<animal>_<session>_<suffix>`` in the model's version directory."""
+def _version_path(src, *names):
+    """``<expt_dir>/version_<n>/<names ...>`` of ``src``: a model (``hparams['expt_dir']``, ``version``) or an hparams
+    dict (``['expt_dir']``, ``['version']``)."""
+    expt_dir, version = (src['expt_dir'], src['version']) if isinstance(src, dict) \
+        else (src.hparams['expt_dir'], src.version)
+    return os.path.join(expt_dir, 'version_%i' % version, *names)
+
+
+def _session_filename(src, dataset, filename, suffix, *dirs):
+    """``filename``, or ``<lab>_<expt>_<animal>_<session>_<suffix>`` in the version directory of ``src`` (a model or
+    an hparams dict, ``_version_path``), below its directories ``dirs``."""
     if filename is not None:
         return filename
     sess_id = '%s_%s_%s_%s_%s' % (dataset.lab, dataset.expt, dataset.animal, dataset.session, suffix)
-    return os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, sess_id)
+    return _version_path(src, *dirs, sess_id)
 
 
-def _write_per_session(data_generator, model, filename, suffix, key, results, what):
+def _write_csv(filename, header, rows):
+    """``header`` and ``rows`` as a table written with the ``csv`` module: a NaN float is an empty field (as pandas
+    writes it), any other float ``repr(float(v))``, ints and strings as they are.  -> ``filename``."""
+    def field(v):
+        return v if not isinstance(v, (float, np.floating)) else '' if np.isnan(v) else repr(float(v))
+    with open(filename, 'w', newline='') as f:
+        writer = csv.writer(f, lineterminator='\n')
+        writer.writerow(header)
+        writer.writerows([field(v) for v in row] for row in rows)
+    return filename
+
+
+def _write_per_session(data_generator, src, filename, suffix, key, results, what):
     filenames = []
     for sess, dataset in enumerate(data_generator.datasets):
-        out = _session_filename(model, dataset, filename, suffix + '.pkl')
+        out = _session_filename(src, dataset, filename, suffix + '.pkl')
         print('saving %s %i of %i:\n%s' % (what, sess + 1, data_generator.n_datasets, out))
         with open(out, 'wb') as f:
             pickle.dump({key: results[sess], 'trials': dataset.batch_idxs}, f)
@@ -1447,6 +1469,53 @@ def _wanted_sessions(who, data_generator, sess_idx):
     return wanted
 
 
+def _latent_trials(who, data_generator, model, dtypes, wanted, per_trial=None, keep_empty=False, upload=True):
+    """``{(session, int(trial)): fp32 device tensor (T, D)}`` of the trials of the splits ``dtypes`` of the sessions
+    ``wanted``, in walk order: the latents, walked and encoded as ``export_latents`` walks and encodes them (the same
+    per-trial encoder and batch fields; trials served on the host go through ``encode_trial`` and are uploaded to the
+    model's device one by one -- or, with ``upload=False``, stay the numpy arrays they are for a caller that uploads
+    them at once).  The one-process sink form of the trial walk: the caller runs it on ONE rank.  A trial without
+    rows is left out unless ``keep_empty``.  ``per_trial(sess, trial, z, data)`` sees every kept trial with its batch
+    as soon as it is encoded; what it raises ends the walk there."""
+    device = next(model.parameters()).device
+    encode = _GraphedTrialEncoder(model)
+    parts = {}
+
+    def on_device(images, sess, data, trial):
+        if sess not in wanted:
+            return None
+        return encode(images, sess, _batch_fields(model, data)[2]).to(torch.float32), data
+
+    def on_host(images, sess, data, trial):
+        if sess not in wanted:
+            return None
+        z = encode_trial(model, images, sess, _batch_fields(model, data)[2])
+        return (torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(device) if upload else z), data
+
+    def sink(sess, trial, result):
+        if result is not None and (keep_empty or len(result[0])):
+            if per_trial is not None:
+                per_trial(sess, int(trial), *result)
+            parts[(sess, int(trial))] = result[0]
+    _export_per_trial(who, data_generator, model, on_device, on_host, sink=sink, dtypes=dtypes)
+    return parts
+
+
+def _parts_table(parts, data_generator, dtypes, wanted, cols):
+    """``(keys, table)``: the trials of ``parts`` (``_latent_trials``) that lie in the splits ``dtypes`` of the sessions
+    ``wanted``, in ``_corr_trial_order`` -- the generator serves the trials in its own order, the table is put together
+    in the reference's -- and their columns ``cols`` (``_corr_columns``: a range is read in place, an index array is
+    gathered once on the device) as one table; None without trials."""
+    keys = [k for k in _corr_trial_order([ds.batch_idxs for ds in data_generator.datasets], dtypes, wanted)
+            if k in parts]
+    if not keys:
+        return keys, None
+    table = torch.cat([parts[k] for k in keys], dim=0)
+    if isinstance(cols, tuple):
+        return keys, table[:, cols[0]:cols[1]]
+    return keys, table[:, torch.from_numpy(cols).to(table.device)]
+
+
 def _latent_table(data_generator, model, sess_idx):
     """The latents of every train / val / test trial of the sessions ``sess_idx`` as ONE device table, encoded as
     ``export_latents`` encodes them; None on the ranks other than 0."""
@@ -1454,22 +1523,11 @@ def _latent_table(data_generator, model, sess_idx):
     if bdist.world_size() > 1 and bdist.rank() != 0:
         return None
     wanted = _wanted_sessions('latent_ranges', data_generator, sess_idx)
-    encode = _GraphedTrialEncoder(model)
-    parts = []
-
-    def on_device(images, sess, data, trial):
-        return encode(images, sess, _batch_fields(model, data)[2]) if sess in wanted else None
-
-    def on_host(images, sess, data, trial):
-        return encode_trial(model, images, sess, _batch_fields(model, data)[2]) if sess in wanted else None
-
-    def sink(sess, trial, result):
-        if result is not None and len(result):
-            parts.append(result)
-    _export_per_trial('latent_ranges', data_generator, model, on_device, on_host, sink=sink)
+    # (trials encoded on the host stay there: ``stack_for_ranges`` uploads them once, not one by one)
+    parts = _latent_trials('latent_ranges', data_generator, model, ('train', 'val', 'test'), wanted, upload=False)
     if not parts:
         raise ValueError('latent_ranges: the sessions %s have no train, val or test trial' % sorted(wanted))
-    return stack_for_ranges(parts, device=next(model.parameters()).device)
+    return stack_for_ranges(list(parts.values()), device=next(model.parameters()).device)
 
 
 def latent_ranges(data_generator, model, sess_idx=None, min_p=5, max_p=95):
@@ -1594,28 +1652,15 @@ def label_r2(data_generator, model, dtype='val', sess_idx=None):
     wanted = _wanted_sessions('label_r2', data_generator, sess_idx)
     n_labels = int(model.hparams['n_labels'])
     device = next(model.parameters()).device
-    encode = _GraphedTrialEncoder(model)
     # (the trial encoder returns U z for an AE-MSP, ``_encode_trial_device``: the transformed space already)
     transformed = model.hparams['model_class'] == 'cond-ae-msp'
     preds, truths, masks, sessions, trials = [], [], [], [], []
-
-    def on_device(images, sess, data, trial):
-        return (encode(images, sess, _batch_fields(model, data)[2]), data) if sess in wanted else None
-
-    def on_host(images, sess, data, trial):
-        if sess not in wanted:
-            return None
-        z = encode_trial(model, images, sess, _batch_fields(model, data)[2])
-        return torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(device), data
 
     def table(value):
         value = value[0]
         return (value if torch.is_tensor(value) else torch.from_numpy(np.asarray(value))).to(device, torch.float32)
 
-    def sink(sess, trial, result):
-        if result is None:
-            return
-        z, data = result
+    def per_trial(sess, trial, z, data):
         if 'labels' not in data:
             raise ValueError('label_r2: the generator serves no labels (session %d, trial %d)' % (sess, trial))
         if transformed:
@@ -1632,7 +1677,7 @@ def label_r2(data_generator, model, dtype='val', sess_idx=None):
         masks.append(table(data['labels_masks']) if 'labels_masks' in data else None)
         sessions.append(sess)
         trials.append(trial)
-    _export_per_trial('label_r2', data_generator, model, on_device, on_host, sink=sink, dtypes=dtypes)
+    _latent_trials('label_r2', data_generator, model, dtypes, wanted, per_trial=per_trial, keep_empty=True)
     if not preds:
         raise ValueError('label_r2: the sessions %s have no %s trial' % (sorted(wanted), ' or '.join(dtypes)))
     offsets = np.concatenate(([0], np.cumsum([p.shape[0] for p in preds]))).astype(np.int64)
@@ -1654,7 +1699,6 @@ def export_label_r2(data_generator, model, label_names=None, dtype='val', filena
     and one trailing column ``Session``, the session's index (the reference's table cannot tell two sessions' trials
     apart).  ``label_names`` defaults to ``label_0, label_1, ...``; a NaN is an empty field, as pandas writes it.
     Written with the ``csv`` module.  -> the path (None on the ranks other than 0)."""
-    import csv
     scores = label_r2(data_generator, model, dtype=dtype)
     if scores is None:
         return None
@@ -1664,18 +1708,11 @@ def export_label_r2(data_generator, model, label_names=None, dtype='val', filena
     if len(label_names) != n_labels:
         raise ValueError('export_label_r2: %d label names for %d labels' % (len(label_names), n_labels))
     if filename is None:
-        filename = os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, 'r2_supervised.csv')
-
-    def field(v):
-        return '' if np.isnan(v) else repr(float(v))
-    with open(filename, 'w', newline='') as f:
-        writer = csv.writer(f, lineterminator='\n')
-        writer.writerow(['Trial', 'Label', 'R2', 'MSE', 'Model', 'Session'])
-        for k, (sess, trial) in enumerate(zip(scores['session'], scores['trial'])):
-            for i, name in enumerate(label_names):
-                writer.writerow([int(trial), name, field(scores['r2'][k, i]), field(scores['mse'][k, i]),
-                                 LABEL_R2_MODEL, int(sess)])
-    return filename
+        filename = _version_path(model, 'r2_supervised.csv')
+    return _write_csv(filename, ['Trial', 'Label', 'R2', 'MSE', 'Model', 'Session'],
+                      ([int(trial), name, scores['r2'][k, i], scores['mse'][k, i], LABEL_R2_MODEL, int(sess)]
+                       for k, (sess, trial) in enumerate(zip(scores['session'], scores['trial']))
+                       for i, name in enumerate(label_names)))
 
 
 # ------------------------------------------------------------------------------------------ latent correlations
@@ -1828,34 +1865,11 @@ def latent_correlations(data_generator, model, dtype='train', sess_idx=None, seg
     if bdist.world_size() > 1 and bdist.rank() != 0:
         return None
     wanted = _wanted_sessions(who, data_generator, sess_idx)
-    device = next(model.parameters()).device
-    encode = _GraphedTrialEncoder(model)
-    parts = {}
-
-    def on_device(images, sess, data, trial):
-        return encode(images, sess, _batch_fields(model, data)[2]) if sess in wanted else None
-
-    def on_host(images, sess, data, trial):
-        if sess not in wanted:
-            return None
-        z = encode_trial(model, images, sess, _batch_fields(model, data)[2])
-        return torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(device)
-
-    def sink(sess, trial, result):
-        if result is not None and len(result):
-            parts[(sess, int(trial))] = result
-    _export_per_trial(who, data_generator, model, on_device, on_host, sink=sink, dtypes=dtypes)
-    # (the generator serves the trials in its own order: the table is put together in the reference's)
-    keys = [k for k in _corr_trial_order([ds.batch_idxs for ds in data_generator.datasets], dtypes, wanted)
-            if k in parts]
+    parts = _latent_trials(who, data_generator, model, dtypes, wanted)
+    keys, selected = _parts_table(parts, data_generator, dtypes, wanted, cols)
     if not keys:
         raise ValueError('%s: the sessions %s have no %s trial' % (who, sorted(wanted), ' or '.join(dtypes)))
-    table = torch.cat([parts[k] for k in keys], dim=0).to(torch.float32)
     offsets, sessions, trials = _corr_segments(who, keys, [parts[k].shape[0] for k in keys], segments)
-    if isinstance(cols, tuple):
-        selected = table[:, cols[0]:cols[1]]
-    else:
-        selected = table[:, torch.from_numpy(cols).to(device)]
     shift = selected[0].contiguous()
     gram = _hip.segment_gram(selected, offsets, shift)
     host = torch.cat([gram.reshape(-1), shift.to(torch.float64)]).cpu().numpy()          # one transfer
@@ -1872,17 +1886,9 @@ def latent_correlations(data_generator, model, dtype='train', sess_idx=None, seg
 
 
 def _write_latent_corr_csv(filename, scores):
-    import csv
-
-    def field(v):
-        return '' if np.isnan(v) else repr(float(v))
-    with open(filename, 'w', newline='') as f:
-        writer = csv.writer(f, lineterminator='\n')
-        writer.writerow(['Segment', 'RowBegin', 'RowEnd', 'N', 'AbsCorr01', 'MeanAbsCorr'])
-        for k, (begin, end) in enumerate(scores['rows']):
-            writer.writerow([k, int(begin), int(end), int(scores['n'][k]), field(scores['abs_corr_01'][k]),
-                             field(scores['mean_abs_offdiag'][k])])
-    return filename
+    return _write_csv(filename, ['Segment', 'RowBegin', 'RowEnd', 'N', 'AbsCorr01', 'MeanAbsCorr'],
+                      ([k, int(begin), int(end), int(scores['n'][k]), scores['abs_corr_01'][k],
+                        scores['mean_abs_offdiag'][k]] for k, (begin, end) in enumerate(scores['rows'])))
 
 
 def export_latent_correlations(data_generator, model, dtype='train', segments=None, columns=None, filename=None):
@@ -1895,7 +1901,7 @@ def export_latent_correlations(data_generator, model, dtype='train', segments=No
     if scores is None:
         return None
     if filename is None:
-        filename = os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, 'corr_unsupervised.csv')
+        filename = _version_path(model, 'corr_unsupervised.csv')
     return _write_latent_corr_csv(filename, scores)
 
 
@@ -1944,33 +1950,13 @@ def session_classifier(data_generator, model, dtype='val', columns=None, Cs=_clf
     _export_setup(model)
     if bdist.world_size() > 1 and bdist.rank() != 0:
         return None
-    device = next(model.parameters()).device
-    encode = _GraphedTrialEncoder(model)
-    parts = {}
-    wanted_set = set(wanted)
-
-    def on_device(images, sess, data, trial):
-        return encode(images, sess, _batch_fields(model, data)[2]) if sess in wanted_set else None
-
-    def on_host(images, sess, data, trial):
-        if sess not in wanted_set:
-            return None
-        z = encode_trial(model, images, sess, _batch_fields(model, data)[2])
-        return torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(device)
-
-    def sink(sess, trial, result):
-        if result is not None and len(result):
-            parts[(sess, int(trial))] = result
     dtypes = ['train'] + [d for d in splits if d != 'train']
-    _export_per_trial(who, data_generator, model, on_device, on_host, sink=sink, dtypes=dtypes)
+    parts = _latent_trials(who, data_generator, model, dtypes, set(wanted))
 
     def table(split):
-        keys = [k for k in _corr_trial_order([ds.batch_idxs for ds in data_generator.datasets], [split], wanted_set)
-                if k in parts]
+        keys, z = _parts_table(parts, data_generator, [split], set(wanted), cols)
         if not keys:
             raise ValueError('%s: the sessions %s have no %s trial' % (who, wanted, split))
-        z = torch.cat([parts[k] for k in keys], dim=0).to(torch.float32)
-        z = z[:, cols[0]:cols[1]] if isinstance(cols, tuple) else z[:, torch.from_numpy(cols).to(device)]
         y = np.concatenate([np.full(parts[k].shape[0], wanted.index(k[0]), dtype=np.int32) for k in keys])
         return z, y
     z_train, y_train = table('train')
@@ -2030,7 +2016,7 @@ def export_session_classifier(data_generator, model, dtype='val', columns=None, 
     if out is None:
         return None
     if filename is None:
-        filename = os.path.join(model.hparams['expt_dir'], 'version_%i' % model.version, SESSION_CLASSIFIER_FILE)
+        filename = _version_path(model, SESSION_CLASSIFIER_FILE)
     np.save(filename, np.array([out[0]]))
     return filename, out[0], out[1]
 
@@ -2066,23 +2052,7 @@ def _arhmm_trials(who, data_generator, model, data_key, dtypes, wanted):
         raise ValueError("%s: data_key must be 'ae_latents' or 'labels', got %r" % (who, data_key))
     if model is None:
         raise ValueError('%s: latents need the model that encodes them' % who)
-    device = next(model.parameters()).device
-    encode = _GraphedTrialEncoder(model)
-
-    def on_device(images, sess, data, trial):
-        return encode(images, sess, _batch_fields(model, data)[2]) if sess in wanted else None
-
-    def on_host(images, sess, data, trial):
-        if sess not in wanted:
-            return None
-        z = encode_trial(model, images, sess, _batch_fields(model, data)[2])
-        return torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(device)
-
-    def sink(sess, trial, result):
-        if result is not None and len(result):
-            parts[(sess, int(trial))] = result.to(torch.float32)
-    _export_per_trial(who, data_generator, model, on_device, on_host, sink=sink, dtypes=dtypes)
-    return parts
+    return _latent_trials(who, data_generator, model, dtypes, wanted)
 
 
 def _arhmm_split(parts, keys):
@@ -2092,6 +2062,37 @@ def _arhmm_split(parts, keys):
     table = torch.cat([parts[k] for k in keys], dim=0).contiguous() if keys and offsets[-1] else None
     return (table, offsets, np.asarray([k[0] for k in keys], dtype=np.int64),
             np.asarray([k[1] for k in keys], dtype=np.int64))
+
+
+def _arhmm_data_key(hparams):
+    """What an ARHMM of ``hparams['model_class']`` was fitted on: the labels for a class with ``label`` in its name
+    (``arhmm-labels``), the latents otherwise."""
+    return 'labels' if str(hparams.get('model_class', 'arhmm')).find('label') > -1 else 'ae_latents'
+
+
+def _arhmm_stage(who, data_generator, model, data_key, dtypes, sess_idx, per_split, gate=True, every=False,
+                 parts=None):
+    """How the entry points of the ARHMM stage open: an invalid dtype key of the model that encodes the latents is an
+    error before any trial is read; the ranks other than 0 stop here (``gate``; ``sample_arhmm`` has none); the
+    sessions ``sess_idx`` are checked; their trials of the splits ``dtypes`` are gathered ONCE (``_arhmm_trials``;
+    ``parts``: gathered already) and put into device tables (``_arhmm_split``) in ``_corr_trial_order``: one per
+    split (``per_split``: a dict by split) or one over all of them.  ``every`` is the states exporters' form: every
+    session whatever ``sess_idx`` says, a model that may be None even for latents (``_arhmm_trials`` refuses it), and
+    ONE table with the trials in ``sorted`` order -- the states files are indexed by it.
+    -> ``(wanted, parts, tables)``, or None on a rank that stops."""
+    if data_key == 'ae_latents' and not (every and model is None):
+        _export_setup(model)
+    if gate and bdist.world_size() > 1 and bdist.rank() != 0:
+        return None
+    wanted = set(range(len(data_generator.datasets))) if every else _wanted_sessions(who, data_generator, sess_idx)
+    if parts is None:
+        parts = _arhmm_trials(who, data_generator, model, data_key, dtypes, wanted)
+    if every:
+        return wanted, parts, _arhmm_split(parts, sorted(parts))
+    idxs = [ds.batch_idxs for ds in data_generator.datasets]
+    if per_split:
+        return wanted, parts, {dt: _arhmm_split(parts, _corr_trial_order(idxs, [dt], wanted)) for dt in dtypes}
+    return wanted, parts, _arhmm_split(parts, _corr_trial_order(idxs, dtypes, wanted))
 
 
 def _arhmm_loss(lls, offsets, sel, D):
@@ -2306,14 +2307,10 @@ def fit_arhmm_grid(data_generator, model, grid, n_iters=150, tol=0, sess_idx=Non
     grid = [_arhmm_grid_config(cfg) for cfg in grid]
     for c in grid:                                          # (types and limits that need no table)
         _new_arhmm(1, c['n_states'], 0, c['transitions'], c['kappa'], c['noise_type'])
-    if data_key == 'ae_latents':
-        _export_setup(model)
-    if bdist.world_size() > 1 and bdist.rank() != 0:
+    stage = _arhmm_stage(who, data_generator, model, data_key, ('train', 'val', 'test'), sess_idx, True)
+    if stage is None:
         return None
-    wanted = _wanted_sessions(who, data_generator, sess_idx)
-    parts = _arhmm_trials(who, data_generator, model, data_key, ('train', 'val', 'test'), wanted)
-    idxs = [ds.batch_idxs for ds in data_generator.datasets]
-    splits = {dt: _arhmm_split(parts, _corr_trial_order(idxs, [dt], wanted)) for dt in ('train', 'val', 'test')}
+    wanted, _, splits = stage
     return _fit_arhmm_grid_splits(splits, sorted(wanted), grid, n_iters, tol)
 
 
@@ -2343,15 +2340,10 @@ def fit_arhmm(data_generator, model, n_states, n_lags=1, transitions='stationary
     relabelled by their usage in the Viterbi paths of the training trials.
     -> ``(arhmm, rows)``: the ``models.arhmm.ARHMM`` and the list of dicts the reference hands to ``exp.log``.
     Under ``torch.distributed`` rank 0 fits and the other ranks return None."""
-    who = 'fit_arhmm'
-    if data_key == 'ae_latents':
-        _export_setup(model)
-    if bdist.world_size() > 1 and bdist.rank() != 0:
+    stage = _arhmm_stage('fit_arhmm', data_generator, model, data_key, ('train', 'val', 'test'), sess_idx, True)
+    if stage is None:
         return None
-    wanted = _wanted_sessions(who, data_generator, sess_idx)
-    parts = _arhmm_trials(who, data_generator, model, data_key, ('train', 'val', 'test'), wanted)
-    idxs = [ds.batch_idxs for ds in data_generator.datasets]
-    splits = {dt: _arhmm_split(parts, _corr_trial_order(idxs, [dt], wanted)) for dt in ('train', 'val', 'test')}
+    wanted, _, splits = stage
     return _fit_arhmm_splits(splits, sorted(wanted), n_states, n_lags, transitions, kappa, n_iters, tol,
                              rng_seed_model, noise_type)
 
@@ -2385,37 +2377,21 @@ def export_states(hparams, data_generator, arhmm, model=None, filename=None):
     ``filename``): the reference's ``export_states`` (fitting/eval.py:121-188).  The trials' latents (encoded by
     ``model``) or, for a ``model_class`` with ``label`` in it, their labels go into ONE device table and ONE Viterbi
     launch.  -> the file names (an empty list on the ranks other than 0)."""
-    who = 'export_states'
-    data_key = 'labels' if str(hparams.get('model_class', 'arhmm')).find('label') > -1 else 'ae_latents'
-    if data_key == 'ae_latents' and model is not None:
-        _export_setup(model)
-    if bdist.world_size() > 1 and bdist.rank() != 0:
+    stage = _arhmm_stage('export_states', data_generator, model, _arhmm_data_key(hparams), ('train', 'val', 'test'),
+                         None, False, every=True)
+    if stage is None:
         return []
-    wanted = set(range(len(data_generator.datasets)))
-    parts = _arhmm_trials(who, data_generator, model, data_key, ('train', 'val', 'test'), wanted)
-    keys = sorted(parts)
-    table, offsets, _, _ = _arhmm_split(parts, keys)
+    table, offsets, sessions, trials = stage[2]
     states = [[np.array([]) for _ in range(ds.n_trials)] for ds in data_generator.datasets]
     if table is not None:
         path = arhmm.table_states(table, offsets)
-        for i, (sess, trial) in enumerate(keys):
+        for i, (sess, trial) in enumerate(zip(sessions, trials)):
             states[sess][trial] = path[offsets[i]:offsets[i + 1]].copy()
-    filenames = []
-    for sess, dataset in enumerate(data_generator.datasets):
-        out = filename
-        if out is None:
-            sess_id = '%s_%s_%s_%s_states.pkl' % (dataset.lab, dataset.expt, dataset.animal, dataset.session)
-            out = os.path.join(hparams['expt_dir'], 'version_%i' % hparams['version'], sess_id)
-        print('saving states %i of %i:\n%s' % (sess + 1, data_generator.n_datasets, out))
-        with open(out, 'wb') as f:
-            pickle.dump({'states': states[sess], 'trials': dataset.batch_idxs}, f)
-        filenames.append(out)
-    return filenames
+    return _write_per_session(data_generator, hparams, filename, 'states', 'states', states, 'states')
 
 
 def check_export_arhmm(who, kwargs):
     """``hparams['export_arhmm']``: a dict of ``fit_arhmm``'s keyword arguments with ``n_states`` among them."""
-    import inspect
     known = set(inspect.signature(fit_arhmm).parameters) - {'data_generator', 'model'}
     if not isinstance(kwargs, dict) or 'n_states' not in kwargs or not set(kwargs) <= known:
         raise ValueError('%s: expected a dict with n_states and any of %s, got %r' % (who, sorted(known), kwargs))
@@ -2435,7 +2411,7 @@ def export_arhmm(data_generator, model, **kwargs):
     labels = kwargs.get('data_key', 'ae_latents') == 'labels'
     hparams = {'expt_dir': model.hparams['expt_dir'], 'version': model.version,
                'model_class': ('arhmm' if kwargs.get('n_lags', 1) > 0 else 'hmm') + ('-labels' if labels else '')}
-    path = os.path.join(hparams['expt_dir'], 'version_%i' % hparams['version'], ARHMM_MODEL_FILE)
+    path = _version_path(hparams, ARHMM_MODEL_FILE)
     with open(path, 'wb') as f:
         pickle.dump(arhmm, f)
     return arhmm, rows, path, export_states(hparams, data_generator, arhmm, model=model)
@@ -2490,14 +2466,10 @@ def arhmm_grid_states(data_generator, model, fits, dtype='test', sess_idx=None, 
     who = 'arhmm_grid_states'
     dtypes = _splits(who, dtype)
     models = _grid_models(who, fits)
-    if data_key == 'ae_latents':
-        _export_setup(model)
-    if bdist.world_size() > 1 and bdist.rank() != 0:
+    stage = _arhmm_stage(who, data_generator, model, data_key, dtypes, sess_idx, False)
+    if stage is None:
         return None
-    wanted = _wanted_sessions(who, data_generator, sess_idx)
-    parts = _arhmm_trials(who, data_generator, model, data_key, dtypes, wanted)
-    idxs = [ds.batch_idxs for ds in data_generator.datasets]
-    table, offsets, _, _ = _arhmm_split(parts, _corr_trial_order(idxs, dtypes, wanted))
+    table, offsets, _, _ = stage[2]
     if table is None:
         return [None] * len(models)
     return arhmm_grid_runs(models, table, offsets)
@@ -2567,7 +2539,7 @@ def arhmm_grid_selection(grid, fits, stats, test_frames=None):
 
 
 def _grid_model_dir(hparams, i):
-    return os.path.join(hparams['expt_dir'], 'version_%i' % hparams['version'], ARHMM_GRID_DIR, 'model_%03i' % i)
+    return _version_path(hparams, ARHMM_GRID_DIR, 'model_%03i' % i)
 
 
 def export_states_grid(hparams, data_generator, fits, model=None, _parts=None):
@@ -2578,17 +2550,11 @@ def export_states_grid(hparams, data_generator, fits, model=None, _parts=None):
     list of its file names (an empty list on the ranks other than 0)."""
     who = 'export_states_grid'
     models = _grid_models(who, fits)
-    data_key = 'labels' if str(hparams.get('model_class', 'arhmm')).find('label') > -1 else 'ae_latents'
-    if data_key == 'ae_latents' and model is not None:
-        _export_setup(model)
-    if bdist.world_size() > 1 and bdist.rank() != 0:
+    stage = _arhmm_stage(who, data_generator, model, _arhmm_data_key(hparams), ('train', 'val', 'test'), None, False,
+                         every=True, parts=_parts)
+    if stage is None:
         return []
-    parts = _parts
-    if parts is None:
-        parts = _arhmm_trials(who, data_generator, model, data_key, ('train', 'val', 'test'),
-                              set(range(len(data_generator.datasets))))
-    keys = sorted(parts)
-    table, offsets, _, _ = _arhmm_split(parts, keys)
+    table, offsets, sessions, trials = stage[2]
     paths = [None] * len(models)
     if table is not None:
         for members, group in _grid_groups_of(models, int(table.shape[0])):
@@ -2598,14 +2564,12 @@ def export_states_grid(hparams, data_generator, fits, model=None, _parts=None):
     for i in range(len(models)):
         states = [[np.array([]) for _ in range(ds.n_trials)] for ds in data_generator.datasets]
         if paths[i] is not None:
-            for t, (sess, trial) in enumerate(keys):
+            for t, (sess, trial) in enumerate(zip(sessions, trials)):
                 states[sess][trial] = paths[i][offsets[t]:offsets[t + 1]].copy()
-        out_dir = _grid_model_dir(hparams, i)
-        os.makedirs(out_dir, exist_ok=True)
+        os.makedirs(_grid_model_dir(hparams, i), exist_ok=True)
         names = []
         for sess, dataset in enumerate(data_generator.datasets):
-            out = os.path.join(out_dir, '%s_%s_%s_%s_states.pkl' % (dataset.lab, dataset.expt, dataset.animal,
-                                                                     dataset.session))
+            out = _session_filename(hparams, dataset, None, 'states.pkl', ARHMM_GRID_DIR, 'model_%03i' % i)
             with open(out, 'wb') as f:
                 pickle.dump({'states': states[sess], 'trials': dataset.batch_idxs}, f)
             names.append(out)
@@ -2618,7 +2582,6 @@ def check_export_arhmm_grid(who, kwargs):
     """``hparams['export_arhmm_grid']``: a dict of ``export_arhmm_grid``'s keyword arguments with ``grid``, a
     non-empty list of configurations, among them.  Every configuration is built -- a type or a limit that is not
     served is ``fit_arhmm``'s error -- and ``dtype`` is checked, before any epoch."""
-    import inspect
     known = set(inspect.signature(export_arhmm_grid).parameters) - {'data_generator', 'model'}
     if not isinstance(kwargs, dict) or 'grid' not in kwargs or not set(kwargs) <= known:
         raise ValueError('%s: expected a dict with grid and any of %s, got %r' % (who, sorted(known), kwargs))
@@ -2647,14 +2610,10 @@ def export_arhmm_grid(data_generator, model, grid, n_iters=150, tol=0, sess_idx=
     who = 'export_arhmm_grid'
     check_export_arhmm_grid(who, {'grid': grid, 'dtype': dtype, 'data_key': data_key})
     full = [_arhmm_grid_config(cfg) for cfg in grid]
-    if data_key == 'ae_latents':
-        _export_setup(model)
-    if bdist.world_size() > 1 and bdist.rank() != 0:
+    stage = _arhmm_stage(who, data_generator, model, data_key, ('train', 'val', 'test'), sess_idx, True)
+    if stage is None:
         return None
-    wanted = _wanted_sessions(who, data_generator, sess_idx)
-    parts = _arhmm_trials(who, data_generator, model, data_key, ('train', 'val', 'test'), wanted)
-    idxs = [ds.batch_idxs for ds in data_generator.datasets]
-    splits = {dt: _arhmm_split(parts, _corr_trial_order(idxs, [dt], wanted)) for dt in ('train', 'val', 'test')}
+    wanted, parts, splits = stage
     fits = _fit_arhmm_grid_splits(splits, sorted(wanted), full, n_iters, tol)
     table, offsets, _, _ = splits[dtype]
     stats = arhmm_grid_runs(fits, table, offsets) if table is not None else None
@@ -2679,6 +2638,18 @@ def export_arhmm_grid(data_generator, model, grid, n_iters=150, tol=0, sess_idx=
 # ------------------------------------------------------------------------------------------ ARHMM predictions
 ARHMM_PREDICTIONS_FILE = 'arhmm_predictions.csv'
 _PREDICTION_MEASURES = ('mse', 'r2', 'mse_persistence', 'r2_persistence')
+
+
+def _arhmm_scored_table(who, data_generator, model, data_key, dtype, sess_idx):
+    """``_arhmm_stage``'s ONE table over the splits ``dtype`` for the scores of a fitted ARHMM, which need frames:
+    a table without any is a ValueError.  -> ``_arhmm_split``'s tuple, or None on the ranks other than 0."""
+    dtypes = _splits(who, dtype)
+    stage = _arhmm_stage(who, data_generator, model, data_key, dtypes, sess_idx, False)
+    if stage is None:
+        return None
+    if stage[2][0] is None:
+        raise ValueError('%s: the sessions %s have no %s frames' % (who, sorted(stage[0]), ' or '.join(dtypes)))
+    return stage[2]
 
 
 def summarise_prediction_sums(sums, min_valid=10):
@@ -2720,18 +2691,10 @@ def arhmm_predictions(data_generator, model, arhmm, dtype='test', weights='predi
     order, and ``'sums'``; with ``return_latents`` also ``'latents'`` and ``'latents_pred'``, lists of host (T, D)
     arrays per trial -- the operands of ``real_vs_sampled_movie(model, latents, latents_pred)`` for a
     real-versus-predicted movie.  Under ``torch.distributed`` rank 0 works and the other ranks return None."""
-    who = 'arhmm_predictions'
-    dtypes = _splits(who, dtype)
-    if data_key == 'ae_latents':
-        _export_setup(model)
-    if bdist.world_size() > 1 and bdist.rank() != 0:
+    stage = _arhmm_scored_table('arhmm_predictions', data_generator, model, data_key, dtype, sess_idx)
+    if stage is None:
         return None
-    wanted = _wanted_sessions(who, data_generator, sess_idx)
-    parts = _arhmm_trials(who, data_generator, model, data_key, dtypes, wanted)
-    idxs = [ds.batch_idxs for ds in data_generator.datasets]
-    table, offsets, sessions, trials = _arhmm_split(parts, _corr_trial_order(idxs, dtypes, wanted))
-    if table is None:
-        raise ValueError('%s: the sessions %s have no %s frames' % (who, sorted(wanted), ' or '.join(dtypes)))
+    table, offsets, sessions, trials = stage
     xhat, valid = arhmm.table_predictions(table, offsets, weights)
     sums = arhmm.sums_of_predictions(table, offsets, xhat, valid)
     out = summarise_prediction_sums(sums)
@@ -2750,24 +2713,17 @@ def export_arhmm_predictions(hparams, data_generator, arhmm, model=None, dtype='
     table's order with the columns ``Session, Trial, Dim, N, MSE, R2, MSE_persistence, R2_persistence``; a NaN is an
     empty field, as in ``export_label_r2``'s table.  Latents or labels by ``hparams['model_class']`` as
     ``export_states`` chooses.  Written with the ``csv`` module.  -> the path (None on the ranks other than 0)."""
-    import csv
-    data_key = 'labels' if str(hparams.get('model_class', 'arhmm')).find('label') > -1 else 'ae_latents'
-    scores = arhmm_predictions(data_generator, model, arhmm, dtype=dtype, weights=weights, data_key=data_key)
+    scores = arhmm_predictions(data_generator, model, arhmm, dtype=dtype, weights=weights,
+                               data_key=_arhmm_data_key(hparams))
     if scores is None:
         return None
     if filename is None:
-        filename = os.path.join(hparams['expt_dir'], 'version_%i' % hparams['version'], ARHMM_PREDICTIONS_FILE)
-
-    def field(v):
-        return '' if np.isnan(v) else repr(float(v))
-    with open(filename, 'w', newline='') as f:
-        writer = csv.writer(f, lineterminator='\n')
-        writer.writerow(['Session', 'Trial', 'Dim', 'N', 'MSE', 'R2', 'MSE_persistence', 'R2_persistence'])
-        for k, (sess, trial) in enumerate(zip(scores['session'], scores['trial'])):
-            for d in range(scores['n'].shape[1]):
-                writer.writerow([int(sess), int(trial), d, int(scores['n'][k, d])]
-                                + [field(scores[name][k, d]) for name in _PREDICTION_MEASURES])
-    return filename
+        filename = _version_path(hparams, ARHMM_PREDICTIONS_FILE)
+    return _write_csv(filename, ['Session', 'Trial', 'Dim', 'N', 'MSE', 'R2', 'MSE_persistence', 'R2_persistence'],
+                      ([int(sess), int(trial), d, int(scores['n'][k, d])]
+                       + [scores[name][k, d] for name in _PREDICTION_MEASURES]
+                       for k, (sess, trial) in enumerate(zip(scores['session'], scores['trial']))
+                       for d in range(scores['n'].shape[1])))
 
 
 # ------------------------------------------------------------------------------------------ ARHMM forecasts
@@ -2803,18 +2759,10 @@ def arhmm_forecasts(data_generator, model, arhmm, horizons=10, dtype='test', ses
     ``ARHMM.forecast_sums`` scores all horizons in one launch and ``(2, H, S, D, 4)`` doubles cross to the host.
     -> ``summarise_forecast_sums``'s dict plus ``'session'`` and ``'trial'``, int arrays ``(S,)`` in the table's
     order, and ``'sums'``.  Under ``torch.distributed`` rank 0 works and the other ranks return None."""
-    who = 'arhmm_forecasts'
-    dtypes = _splits(who, dtype)
-    if data_key == 'ae_latents':
-        _export_setup(model)
-    if bdist.world_size() > 1 and bdist.rank() != 0:
+    stage = _arhmm_scored_table('arhmm_forecasts', data_generator, model, data_key, dtype, sess_idx)
+    if stage is None:
         return None
-    wanted = _wanted_sessions(who, data_generator, sess_idx)
-    parts = _arhmm_trials(who, data_generator, model, data_key, dtypes, wanted)
-    idxs = [ds.batch_idxs for ds in data_generator.datasets]
-    table, offsets, sessions, trials = _arhmm_split(parts, _corr_trial_order(idxs, dtypes, wanted))
-    if table is None:
-        raise ValueError('%s: the sessions %s have no %s frames' % (who, sorted(wanted), ' or '.join(dtypes)))
+    table, offsets, sessions, trials = stage
     sums = arhmm.forecast_sums(table, offsets, horizons)
     out = summarise_forecast_sums(sums)
     out.update({'session': sessions, 'trial': trials, 'sums': sums})
@@ -2827,30 +2775,24 @@ def export_arhmm_forecasts(hparams, data_generator, arhmm, model=None, horizons=
     with the columns ``Horizon, Session, Trial, Dim, N, MSE, R2, MSE_persistence, R2_persistence``; a NaN is an empty
     field.  Latents or labels by ``hparams['model_class']`` as ``export_states`` chooses.  -> the path (None on the
     ranks other than 0)."""
-    data_key = 'labels' if str(hparams.get('model_class', 'arhmm')).find('label') > -1 else 'ae_latents'
-    scores = arhmm_forecasts(data_generator, model, arhmm, horizons=horizons, dtype=dtype, data_key=data_key)
+    scores = arhmm_forecasts(data_generator, model, arhmm, horizons=horizons, dtype=dtype,
+                             data_key=_arhmm_data_key(hparams))
     if scores is None:
         return None
     if filename is None:
-        filename = os.path.join(hparams['expt_dir'], 'version_%i' % hparams['version'], ARHMM_FORECASTS_FILE)
+        filename = _version_path(hparams, ARHMM_FORECASTS_FILE)
     write_forecasts_csv(filename, scores)
     return filename
 
 
 def write_forecasts_csv(filename, scores):
     """The rows of ``export_arhmm_forecasts`` from ``arhmm_forecasts``'s dict."""
-    import csv
-
-    def field(v):
-        return '' if np.isnan(v) else repr(float(v))
-    with open(filename, 'w', newline='') as f:
-        writer = csv.writer(f, lineterminator='\n')
-        writer.writerow(['Horizon', 'Session', 'Trial', 'Dim', 'N', 'MSE', 'R2', 'MSE_persistence', 'R2_persistence'])
-        for h in range(scores['n'].shape[0]):
-            for k, (sess, trial) in enumerate(zip(scores['session'], scores['trial'])):
-                for d in range(scores['n'].shape[2]):
-                    writer.writerow([h + 1, int(sess), int(trial), d, int(scores['n'][h, k, d])]
-                                    + [field(scores[name][h, k, d]) for name in _PREDICTION_MEASURES])
+    _write_csv(filename, ['Horizon', 'Session', 'Trial', 'Dim', 'N', 'MSE', 'R2', 'MSE_persistence', 'R2_persistence'],
+               ([h + 1, int(sess), int(trial), d, int(scores['n'][h, k, d])]
+                + [scores[name][h, k, d] for name in _PREDICTION_MEASURES]
+                for h in range(scores['n'].shape[0])
+                for k, (sess, trial) in enumerate(zip(scores['session'], scores['trial']))
+                for d in range(scores['n'].shape[2])))
 
 
 def check_export_arhmm_forecasts(who, kwargs, export_arhmm=True):
@@ -2886,14 +2828,10 @@ def sample_arhmm(data_generator, model, arhmm, n_samples=50, conditional=True, d
     the ``ssm`` library is unchecked."""
     who = 'sample_arhmm'
     _splits(who, dtype)
-    if data_key == 'ae_latents':
-        _export_setup(model)
-    wanted = _wanted_sessions(who, data_generator, sess_idx)
-    parts = _arhmm_trials(who, data_generator, model, data_key, ('train', 'val', 'test'), wanted)
-    idxs = [ds.batch_idxs for ds in data_generator.datasets]
+    wanted, _, splits = _arhmm_stage(who, data_generator, model, data_key, ('train', 'val', 'test'), sess_idx, True,
+                                     gate=False)
     out = {'latents': {}, 'states': {}, 'trial_idxs': {}, 'latents_gen': [], 'states_gen': []}
-    for dt in ('train', 'val', 'test'):
-        table, offsets, sess, trials = _arhmm_split(parts, _corr_trial_order(idxs, [dt], wanted))
+    for dt, (table, offsets, sess, trials) in splits.items():
         n = len(sess)
         if table is not None:
             path = arhmm.table_states(table, offsets)
